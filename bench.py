@@ -15,9 +15,15 @@ With N > 1 the same job is split by kNN query rows over the ranks (strong scalin
 are all-gathered with RCCL; every rank ends with the full result.
 
 Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel knn_topk_f16: algorithmic
-FLOPs / HIP-event time of its launches vs the dense fp16 MFMA peak), `streaming` (the HBM-bound rest of the merges
-against the HBM peak), `value_host_to_host` (upload, run, download and pairs included) and, at N = 1, `cpu_baseline`
-(two CPU statements of the dominant step timed on a bounded sample of the same workload on this box's host cores).
+FLOPs / HIP-event time of its launches vs the dense fp16 MFMA peak) and `streaming` (the HBM-bound rest of the merges
+against the HBM peak), both read from the timed steps themselves.  With `--full` the line also holds
+`value_host_to_host` (upload, run, download and pairs included, timed in runs of their own) and, at N = 1,
+`cpu_baseline` (CPU statements of the dominant step timed on a bounded sample of the same workload on the host cores);
+a plain run does neither.
+
+`--dump-outputs DIR` writes what the last timed step computed, as the caller of MnnEngine.download receives it, to
+DIR/<name>.npy (float64, or float32 for cell indices; a fixed, seeded sample of the corrected rows; 64 MB at most), so
+that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -73,6 +79,40 @@ def synth_batches(config, sizes, d, shift=1.0):
         mu += 0.5 * b / np.sqrt(d)
         out.append(rng.standard_normal((n, d)) * s + mu)
     return out
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: an MnnResult as DIR/<name>.npy, DUMP_BYTES at most in all.  The corrected matrix is too large to
+    write whole (800 000 x 50 doubles at config 3): a fixed, seeded sample of its rows (~12 MB) goes out with the row
+    numbers.  The MNN pairs are 1-based cell indices below 2^24, exact in float32; a merge with more pairs than its
+    share of ~48 MB is sampled the same way."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, d = res.corrected.shape
+    info = res.merge_info
+
+    def sample(count, cap, seed):
+        if count <= cap:
+            return np.arange(count)
+        return np.sort(np.random.default_rng(seed).choice(count, cap, replace=False))
+
+    rows = sample(n, 12_000_000 // (8 * (d + 2)), 0)
+    arrays = {"corrected_rows": rows.astype(np.float64), "corrected_sample": res.corrected[rows],
+              "batch_sample": res.batch[rows].astype(np.float64),
+              "batch_size": info.batch_size.astype(np.float64), "skipped": info.skipped.astype(np.float64),
+              "lost_var": info.lost_var.astype(np.float64),
+              "pair_counts": np.array([p[0].size for p in info.pairs], dtype=np.float64)}
+    pair_cap = 48_000_000 // (8 * max(1, len(info.pairs)))
+    for m, (left, right) in enumerate(info.pairs):
+        assert max(left.max(initial=0), right.max(initial=0)) < 2 ** 24
+        keep = sample(left.size, pair_cap, 1 + m)
+        arrays[f"pairs_merge{m + 1}"] = np.stack([left[keep], right[keep]], axis=1).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def measured_traffic(workload, kernel):
@@ -604,9 +644,18 @@ def main():
     ap.add_argument("--emulate-ranks", default="all", help="--emulate-world: which ranks to measure (all, or e.g. 0,3,7)")
     ap.add_argument("--measure-exchange", action="store_true",
                     help="--emulate-world: measure the per-call term of the exchange model with a one-rank RCCL communicator")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-to-host", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="engine workloads: also time the CPU baselines and the host-to-host runs (off: the timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="no CPU baselines (they run with --full, and in --workload sgk)")
+    ap.add_argument("--no-host-to-host", action="store_true", help="--full without the host-to-host runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="engine workloads: write the last timed step's results to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.emulate_world or args.workload in ("config4", "sgk")):
+        ap.error("--dump-outputs is for the engine workloads (config1/2/3/5) without --emulate-world")
 
     if args.dev:
         from batchelor_amd import _lib as _bl
@@ -706,9 +755,12 @@ def main():
     dom_ms, dom_launches = acc[dom + "_ms"], acc[dom + "_launches"]
     xst = eng.exchange_stats() if world > 1 else {"calls": 0, "bytes": 0}
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng.download(with_pairs=True, c_order=False), args.dump_outputs)
+
     # host to host: column-major host inputs -> host outputs, upload, run, download and pairs included
     h2h = None
-    if world == 1 and not args.no_host_to_host:
+    if world == 1 and args.full and not args.no_host_to_host:
         eng.set_profiling(False)
         reps = []
         fbatches = [np.asfortranarray(b) for b in batches]  # what the boundary is handed: column-major matrices
@@ -842,7 +894,7 @@ def main():
             line["value_host_to_host"] = n_cells / h2h
             line["host_to_host_ms"] = 1e3 * h2h
             line["host_to_host_stages_ms"] = h2h_stages
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"], line["cpu_baseline_variants"] = cpu_baselines(batches, stats, d, k)
                 line["host_cores"] = os.cpu_count()

@@ -18,10 +18,11 @@ rm -rf gpurun_out/pmc_asv1 gpurun_out/pmc_asv2 gpurun_out/pmc_asv3
 scripts/prof.sh r04c4 bench.py --workload config4 --cells 200000 --gen-threads 12 2>&1 | tail -3
 cp gpurun_out/prof_r04c4/p_kernel_stats.csv gpurun_out/r04_bench_config4_full_kernel_stats.csv
 grep -E '^\{' gpurun_out/prof_r04c4/stdout.txt | tail -1 > gpurun_out/r04_bench_config4_full.json
-# the bench lines
-python3 bench.py > gpurun_out/r04_bench_config3.json 2> gpurun_out/r04_bench_config3.err
-python3 bench.py --workload config2 --no-cpu-baseline > gpurun_out/r04_bench_config2.json 2>/dev/null
-python3 bench.py --workload config5 --no-cpu-baseline --steps 5 --warmup 1 > gpurun_out/r04_bench_config5.json 2>/dev/null
+# the bench lines (--full: with the CPU baselines and host-to-host figures)
+res=$(dirname "$out")
+python3 bench.py --full > $res/r04_bench_config3.json 2> $res/r04_bench_config3.err
+python3 bench.py --full --workload config2 --no-cpu-baseline > $res/r04_bench_config2.json 2>/dev/null
+python3 bench.py --full --workload config5 --no-cpu-baseline --steps 5 --warmup 1 > $res/r04_bench_config5.json 2>/dev/null
 python3 bench.py --workload sgk > gpurun_out/r04_bench_sgk.json 2>/dev/null
 find gpurun_out -name "*kernel_trace.csv" -size +5M -delete
 ls -la gpurun_out | tail -30

@@ -26,11 +26,12 @@ cp gpurun_out/prof_${R}sgk/p_kernel_stats.csv gpurun_out/${R}_bench_sgk_kernel_s
 scripts/prof.sh ${R}c4 bench.py --workload config4 --cells 200000 --gen-threads 12 2>&1 | tail -3
 cp gpurun_out/prof_${R}c4/p_kernel_stats.csv gpurun_out/${R}_bench_config4_full_kernel_stats.csv
 grep -E '^\{' gpurun_out/prof_${R}c4/stdout.txt | tail -1 > gpurun_out/${R}_bench_config4_full.json
-# the bench lines, un-profiled
-python3 bench.py > gpurun_out/${R}_bench_config3.json 2> gpurun_out/${R}_bench_config3.err
-python3 bench.py --workload config2 --no-cpu-baseline > gpurun_out/${R}_bench_config2.json 2>/dev/null
-python3 bench.py --workload config5 --no-cpu-baseline --steps 5 --warmup 1 > gpurun_out/${R}_bench_config5.json 2>/dev/null
-python3 bench.py --workload config5 --var-adj --sigma 1.0 --steps 2 --warmup 1 --no-host-to-host > gpurun_out/${R}_bench_config5_varadj_sigma1.0.json 2>/dev/null
+# the bench lines, un-profiled (--full: with the CPU baselines and host-to-host figures)
+res=$(dirname "$out")
+python3 bench.py --full > $res/${R}_bench_config3.json 2> $res/${R}_bench_config3.err
+python3 bench.py --full --workload config2 --no-cpu-baseline > $res/${R}_bench_config2.json 2>/dev/null
+python3 bench.py --full --workload config5 --no-cpu-baseline --steps 5 --warmup 1 > $res/${R}_bench_config5.json 2>/dev/null
+python3 bench.py --full --workload config5 --var-adj --sigma 1.0 --steps 2 --warmup 1 --no-host-to-host > $res/${R}_bench_config5_varadj_sigma1.0.json 2>/dev/null
 python3 bench.py --workload config5 --var-adj --sigma 0.1 --steps 2 --warmup 1 --no-cpu-baseline --no-host-to-host > gpurun_out/${R}_bench_config5_varadj_sigma0.1.json 2>/dev/null
 python3 bench.py --workload sgk > gpurun_out/${R}_bench_sgk.json 2>/dev/null
 python3 bench.py --emulate-world 2,4,8 --measure-exchange --steps 5 --warmup 2 > gpurun_out/${R}_emulate_config3.jsonl 2>/dev/null
