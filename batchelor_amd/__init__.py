@@ -9,3 +9,4 @@ from .reduced_mnn import MnnEngine, MnnResult, divideIntoBatches, reducedMNN  # 
 from .natives import (adjust_shift_variance, find_mutual_nn, find_mutual_nns, smooth_gaussian_kernel)  # noqa: F401
 from .multi_batch_pca import DevicePCA, cosineNorm, multiBatchPCA, multiBatchPCA_host, project  # noqa: F401
 from .fast_mnn import fastMNN  # noqa: F401
+from .mnn_correct import mnnCorrect  # noqa: F401

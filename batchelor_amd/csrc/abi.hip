@@ -17,10 +17,15 @@
 #include "bmx_ops.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
+#include "mnn_correct.hpp"
 #include "rccl_dyn.hpp"
 
 struct bmx_engine {
     std::unique_ptr<bmx::Engine> impl;
+};
+struct bmx_mnn_result {
+    int B = 0;
+    bmx::MnnCorrectResult r;
 };
 
 namespace {
@@ -191,6 +196,8 @@ int32_t bmx_dev_set(const char* name, int32_t value) {
     else if (n == "tau_replay") k.tau_replay = value;
     else if (n == "exchange_always") k.exchange_always = value;
     else if (n == "refine_wave") k.refine_wave = value;
+    else if (n == "asv_wide") k.asv_wide = value;
+    else if (n == "asv_chunk") k.asv_chunk = value;
     else if (n == "reset") k = bmx::DevKnobs();
     else {
         g_last_error = "bmx_dev_set: unknown knob '" + n + "'";
@@ -423,6 +430,95 @@ int32_t bmx_mnn_average_correction(const double* refdata, int32_t n1, const doub
     });
 }
 
+int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* data, const int32_t* ncells,
+                        const int32_t* const* restrict_idx, const int32_t* n_restrict, const bmx_mnn_params_t* params,
+                        bmx_mnn_result_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null result pointer");
+        *out = nullptr;
+        if (!params) throw bmx::Error(BMX_ERR_ARG, "null params");
+        bmx_mnn_params_t p;
+        std::memset(&p, 0, sizeof(p));
+        const int32_t sz = params->struct_size;
+        if (sz < (int32_t)(offsetof(bmx_mnn_params_t, tree_len) + sizeof(int32_t)))
+            throw bmx::Error(BMX_ERR_ARG, "bmx_mnn_params_t.struct_size is not set (expected sizeof(bmx_mnn_params_t))");
+        if ((size_t)sz > sizeof(p)) {
+            const unsigned char* extra = reinterpret_cast<const unsigned char*>(params) + sizeof(p);
+            for (size_t i = 0; i < (size_t)sz - sizeof(p); ++i)
+                if (extra[i]) throw bmx::Error(BMX_ERR_ARG, "bmx_mnn_params_t carries fields this library version does not know");
+        }
+        std::memcpy(&p, params, std::min((size_t)sz, sizeof(p)));
+        if (nbatches < 2) throw bmx::Error(BMX_ERR_ARG, "at least two batches must be specified");
+        if (!data || !ncells) throw bmx::Error(BMX_ERR_ARG, "null batch arrays");
+        bmx::MnnCorrectArgs a;
+        a.B = nbatches;
+        a.G = n_genes;
+        a.data = data;
+        a.ncells = ncells;
+        a.restrict_idx = restrict_idx;
+        a.n_restrict = n_restrict;
+        a.k = p.k;
+        a.prop_k = p.prop_k;
+        a.sigma = p.sigma;
+        a.cos_in = p.cos_norm_in;
+        a.cos_out = p.cos_norm_out;
+        a.var_adj = p.var_adj;
+        a.correct_all = p.correct_all;
+        a.svd_dim = p.svd_dim;
+        a.auto_merge = p.auto_merge;
+        a.subset = p.subset_row;
+        a.nsubset = p.n_subset_row;
+        a.tree = p.tree;
+        a.tree_len = p.tree_len;
+        if (!a.tree) throw bmx::Error(BMX_ERR_TREE, "invalid leaf nodes specified in 'merge.order'");
+        bmx::mnn_correct_check(a);  // (before any device work)
+        auto res = std::make_unique<bmx_mnn_result>();
+        res->B = nbatches;
+        bmx::mnn_correct_run(a, res->r);
+        *out = res.release();
+    });
+}
+
+int32_t bmx_mnn_result_sizes(const bmx_mnn_result_t* r, int32_t* n_genes_out, int64_t* ncells, int64_t* npairs) {
+    return guarded([&] {
+        if (!r) throw bmx::Error(BMX_ERR_ARG, "null result");
+        if (n_genes_out) *n_genes_out = r->r.Gout;
+        if (ncells) *ncells = (int64_t)r->r.batch.size();
+        if (npairs)
+            for (size_t m = 0; m < r->r.pairs_left.size(); ++m) npairs[m] = (int64_t)r->r.pairs_left[m].size();
+    });
+}
+
+int32_t bmx_mnn_result_into(const bmx_mnn_result_t* r, double* corrected, int32_t* batch, int32_t* merge_left,
+                            int32_t* merge_right, int32_t* const* pairs_left, int32_t* const* pairs_right) {
+    return guarded([&] {
+        if (!r) throw bmx::Error(BMX_ERR_ARG, "null result");
+        const bmx::MnnCorrectResult& x = r->r;
+        if (corrected && !x.corrected.empty()) std::memcpy(corrected, x.corrected.data(), x.corrected.size() * sizeof(double));
+        if (batch && !x.batch.empty()) std::memcpy(batch, x.batch.data(), x.batch.size() * sizeof(int32_t));
+        const int B = r->B;
+        for (size_t m = 0; m < x.left.size(); ++m) {
+            for (int j = 0; j < B; ++j) {
+                if (merge_left) merge_left[m * B + j] = j < (int)x.left[m].size() ? x.left[m][j] : 0;
+                if (merge_right) merge_right[m * B + j] = j < (int)x.right[m].size() ? x.right[m][j] : 0;
+            }
+            if (pairs_left && pairs_left[m] && !x.pairs_left[m].empty())
+                std::memcpy(pairs_left[m], x.pairs_left[m].data(), x.pairs_left[m].size() * sizeof(int32_t));
+            if (pairs_right && pairs_right[m] && !x.pairs_right[m].empty())
+                std::memcpy(pairs_right[m], x.pairs_right[m].data(), x.pairs_right[m].size() * sizeof(int32_t));
+        }
+    });
+}
+
+int32_t bmx_mnn_result_stage_ms(const bmx_mnn_result_t* r, double* out5) {
+    return guarded([&] {
+        if (!r || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        for (int i = 0; i < 5; ++i) out5[i] = r->r.stage_ms[i];
+    });
+}
+
+void bmx_mnn_result_free(bmx_mnn_result_t* r) { delete r; }
+
 int32_t bmx_center_along_batch_vector(double* mat, int32_t n, int32_t d, const double* batch_vec,
                                       const int32_t* restrict_idx, int32_t n_restrict) {
     return guarded([&] {
@@ -616,7 +712,8 @@ int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, c
 }
 
 int32_t bmx_adjust_shift_variance_form(int32_t n2, int32_t nr1, int32_t nr2) {
-    return bmx::adjust_shift_variance_plan(1, n2, nr1, nr2, 1).exact ? 1 : 2;
+    const bmx::AsvPlan pl = bmx::adjust_shift_variance_plan(1, n2, nr1, nr2, 1);
+    return pl.exact ? 1 : (pl.wide ? 3 : 2);
 }
 
 int32_t bmx_cosine_norm(const double* x, int32_t G, int32_t n, double* l2, double* normalized) {

@@ -63,6 +63,8 @@ struct DevKnobs {
     int sample_split = -1;    // ranges of the threshold sample of a search with few query blocks (-1: automatic, 0: never, n: that many)
     int exchange_always = 0;  // a single rank goes through its exchange transport too (an all-gather of one)
     int refine_wave = 0;      // the exact re-rank takes a whole wave for every query (no half-wave form)
+    int asv_wide = 0;         // adjust_shift_variance: the literal wide form (asv_wide_pairs + asv_wide_cells) whatever the size
+    int asv_chunk = 0;        // wide form: at most this many cells a chunk (0: as many as 1 GiB of scratch holds)
 };
 DevKnobs& dev_knobs();
 bool debug_prints();   // BMX_DEBUG=1 in the environment (read once)

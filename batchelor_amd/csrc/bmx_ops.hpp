@@ -179,6 +179,8 @@ void smooth_gaussian_kernel_device(hipStream_t stream, const double* averaged, i
 // the caller reserves main_doubles + extra_doubles of scratch and hands the same plan to the launch.
 struct AsvPlan {
     int exact = 1;   // 1: asv_exact_kernel (the reference's order of operations literally), 0: the tiled FP64-MFMA form
+    int wide = 0;    // 1 (with exact = 0): the literal wide form -- pair values in LDS-tiled passes, then the exact per-cell phase
+    int chunk = 0;   // wide form: cells whose pair values sit in scratch at once
     int blocks = 1;  // workgroups
     int npad = 1;    // exact form: nr1 rounded up to a power of two
     int lcap = 0;    // tiled form: addends a chain of the literal re-run of a flagged cell may keep (0: no re-run)

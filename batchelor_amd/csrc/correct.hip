@@ -155,6 +155,57 @@ __global__ __launch_bounds__(256) void average_correction_kernel(
     }
 }
 
+// The same for d > 256 (gene space, R/mnnCorrect.R:451-456): one workgroup per MNN-involved right cell and block of 256
+// columns, one column per thread; the cell's partner rows (its whole dup chain) go to the LDS once and every thread adds
+// its column over them in ascending order, then divides by their number -- average_correction_kernel's sums, bit for bit.
+// L and R may be any matrices the pair lists index (the output genes when they differ from the searched ones).
+constexpr int AVW_P = 512;  // partners staged at a time
+__global__ __launch_bounds__(256) void average_correction_wide(
+    const double* __restrict__ L, const int32_t* __restrict__ lrows, const double* __restrict__ R,
+    const int32_t* __restrict__ rrows, int d, const int32_t* __restrict__ second_u, const int32_t* __restrict__ partR,
+    const int32_t* __restrict__ cntR, int k1, double* __restrict__ averaged, const int32_t* __restrict__ dup_next) {
+    __shared__ int64_t prow[AVW_P];
+    __shared__ int sh_q, sh_p, sh_n;
+    const int u = blockIdx.x;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    const int r = second_u[u];
+    const double rc = c < d ? R[(int64_t)(rrows ? rrows[r] : r) * d + c] : 0.0;
+    double s = 0.0;
+    int m = 0;
+    // (dup_next: the right cell is named by several positions of the restrict list -- its pairs are those of all of them)
+    // walk the chain of positions (q, and p = next partner of q) in steps of at most AVW_P partners
+    int q = r, p = 0;
+    while (q >= 0) {
+        if (threadIdx.x == 0) {
+            int n = 0;
+            while (q >= 0 && n < AVW_P) {
+                const int mq = cntR[q];
+                const int32_t* part = partR + (int64_t)q * k1;
+                while (p < mq && n < AVW_P) {
+                    const int l = part[p++];
+                    prow[n++] = lrows ? lrows[l] : l;
+                }
+                if (p >= mq) {
+                    q = dup_next ? dup_next[q] : -1;
+                    p = 0;
+                }
+            }
+            sh_q = q;
+            sh_p = p;
+            sh_n = n;
+        }
+        __syncthreads();
+        const int n = sh_n;
+        q = sh_q;
+        p = sh_p;
+        if (c < d)
+            for (int e = 0; e < n; ++e) s += L[prow[e] * d + c] - rc;
+        m += n;
+        __syncthreads();  // (prow is refilled by the next step)
+    }
+    if (c < d) averaged[(int64_t)u * d + c] = s / (double)m;
+}
+
 // The same for an even d <= 64 and k1 <= 32: half a wave per MNN-involved right cell, 16-byte pieces, the partner rows of
 // four partners in flight at a time; the sum runs over the partners in ascending order, as above.  The workgroups stride
 // over the cells; with `partial` each leaves the column sums and sums of squares of what it wrote ([grid][2][d], combined
@@ -742,8 +793,12 @@ bool average_correction(hipStream_t stream, ReduceWorkspace& ws, const double* L
         }
         return true;
     }
-    hipLaunchKernelGGL(average_correction_kernel, dim3(cdiv(U, 4)), dim3(256), 0, stream, L, lrows, R, rrows, d, second_u, U,
-                       partR, cntR, k1, averaged, dup_next);
+    if (d > 256)
+        hipLaunchKernelGGL(average_correction_wide, dim3(U, cdiv(d, 256)), dim3(256), 0, stream, L, lrows, R, rrows, d, second_u,
+                           partR, cntR, k1, averaged, dup_next);
+    else
+        hipLaunchKernelGGL(average_correction_kernel, dim3(cdiv(U, 4)), dim3(256), 0, stream, L, lrows, R, rrows, d, second_u, U,
+                           partR, cntR, k1, averaged, dup_next);
     BMX_LAUNCH_CHECK();
     return false;  // (the caller takes the column sums / the row list in passes of their own)
 }

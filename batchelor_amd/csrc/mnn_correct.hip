@@ -1,0 +1,442 @@
+// mnnCorrect() on the device: .mnn_correct / .mnn_correct_core (R/mnnCorrect.R:179-393) with .prepare_input_data
+// (:398-445), in gene space.  The host decides the merge order and sizes; every cell x gene value stays in HBM from upload
+// to download.
+//
+// Memory: the input-gene matrix In [N][Gs] (and, when the output genes differ -- same.set false -- the output-gene matrix
+// Out [N][Go]) is one pool whose rows are the cells in the binarised tree's left-to-right leaf order.  Every node of the
+// predefined tree is then a contiguous slice, the two children of a merge are adjacent slices, and rbind(left, right)
+// (:357) costs nothing.  A merge:
+//   1. .restricted_mnn (R/MNN_tree.R:113-138) through Engine::find_mnn on views of the two slices;
+//   2. the pairs (:298), 1-based rows in the nodes;
+//   3. .compute_correction_vectors (:451-460): averaging (average_correction, the wide form above 256 genes), then
+//      smooth_gaussian_kernel_device with the weights from the right node's input-gene rows, for correction.in and
+//      correction.out alike (:300-304);
+//   4. var.adj (:331-342, :462-481): adjust_shift_variance_device on the input genes, and on the subset.row genes of the
+//      output matrix for correction.out; both take the nodes' restrict lists;
+//   5. right += pmax(scaling, 1) * correction in place (:345-348), .combine_restrict on the host.
+// The pairs are reindexed and the rows put back in input order at the end (:364-381).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "bmx_common.hpp"
+#include "bmx_ops.hpp"
+#include "engine.hpp"
+#include "host_xfer.hpp"
+#include "mnn_correct.hpp"
+
+namespace bmx {
+namespace {
+
+// out [n][ns] = X [n][ld] restricted to the columns cols [ns] (0-based): the subset.row genes of the output matrix
+// (R/mnnCorrect.R:466-471).  One thread per output element.
+__global__ void gather_cols_kernel(const double* __restrict__ X, int64_t n, int ld, const int32_t* __restrict__ cols, int ns,
+                                   double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * ns) return;
+    const int64_t r = e / ns;
+    out[e] = X[r * ld + cols[e % ns]];
+}
+
+// out [dst[r]] = X [r] for rows of d doubles: the pool's leaf order back to the caller's batch order
+// (.restore_original_order, R/mnnCorrect.R:373-378).  One thread per element.
+__global__ void permute_rows_kernel(const double* __restrict__ X, int64_t n, int d, const int32_t* __restrict__ dst,
+                                    double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * d) return;
+    const int64_t r = e / d;
+    out[(int64_t)dst[r] * d + e % d] = X[e];
+}
+
+void gather_cols(hipStream_t s, const double* X, int64_t n, int ld, const int32_t* cols, int ns, double* out) {
+    if (n * ns <= 0) return;
+    hipLaunchKernelGGL(gather_cols_kernel, dim3((unsigned)((n * ns + 255) / 256)), dim3(256), 0, s, X, n, ld, cols, ns, out);
+    BMX_LAUNCH_CHECK();
+}
+
+template <class T>
+T* put(DevBuf<T>& b, const T* host, size_t n, hipStream_t s) {
+    T* p = b.reserve(std::max<size_t>(n, 1));
+    if (n) BMX_HIP(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return p;
+}
+
+struct TNode {
+    int left = -1, right = -1;  // children (indices), -1: a leaf or a finished merge
+    int row0 = 0, n = 0;        // slice of the pool
+    std::vector<int> index;     // batch ids (1-based), in row order
+    bool has_restrict = false;
+    std::vector<int32_t> restrict_rows;  // 0-based rows of the node, in the caller's order
+    bool done() const { return left < 0; }
+};
+
+// .get_next_merge (R/MNN_tree.R:61-69): the right subtree first
+int next_merge(const std::vector<TNode>& t, int at) {
+    const TNode& x = t[at];
+    if (t[x.left].done() && t[x.right].done()) return at;
+    if (!t[x.right].done()) return next_merge(t, x.right);
+    return next_merge(t, x.left);
+}
+
+// a Node view of a slice, with the restrict list and its dup chains (as Engine::upload builds them)
+void make_view(Node& v, double* base, const TNode& t, int d, hipStream_t s) {
+    v.n = t.n;
+    v.data.alias(base + (int64_t)t.row0 * d, (size_t)std::max(1, t.n) * d);
+    v.has_restrict = t.has_restrict;
+    v.restrict_dups = false;
+    if (!t.has_restrict) return;
+    const int m = (int)t.restrict_rows.size();
+    v.n_restrict = m;
+    std::vector<int32_t> last((size_t)t.n, -1), next((size_t)m, -1), head((size_t)m, 0);
+    for (int i = 0; i < m; ++i) {
+        const int32_t c = t.restrict_rows[i];
+        head[i] = last[c] < 0 ? 1 : 0;
+        if (last[c] >= 0) {
+            next[last[c]] = i;
+            v.restrict_dups = true;
+        }
+        last[c] = i;
+    }
+    put(v.restrict_rows, t.restrict_rows.data(), (size_t)m, s);
+    if (v.restrict_dups) {
+        put(v.dup_next, next.data(), (size_t)m, s);
+        put(v.dup_head, head.data(), (size_t)m, s);
+    }
+    BMX_HIP(hipStreamSynchronize(s));  // (the host vectors go out of scope)
+}
+
+}  // namespace
+
+void mnn_correct_check(const MnnCorrectArgs& a) {
+    if (a.B < 2) throw Error(BMX_ERR_ARG, "at least two batches must be specified");  // R/mnnCorrect.R:187
+    if (a.svd_dim > 0) throw Error(BMX_ERR_ARG, "svd.dim > 0 is not supported (the biological subspace, R/mnnCorrect.R:313-329)");
+    if (a.auto_merge) throw Error(BMX_ERR_ARG, "auto.merge=TRUE is not supported by mnnCorrect on the device");
+    if (a.G < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one gene");
+    for (int b = 0; b < a.B; ++b) {
+        if (a.ncells[b] < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
+        if (!a.data[b]) throw Error(BMX_ERR_ARG, "null batch matrix");
+        const bool has = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
+        if (!has) continue;
+        if (a.n_restrict[b] == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
+        for (int i = 0; i < a.n_restrict[b]; ++i)
+            if (a.restrict_idx[b][i] < 1 || a.restrict_idx[b][i] > a.ncells[b])
+                throw Error(BMX_ERR_SUBSET, "subset indices out of range");
+    }
+    if (a.subset)
+        for (int i = 0; i < a.nsubset; ++i)
+            if (a.subset[i] < 1 || a.subset[i] > a.G) throw Error(BMX_ERR_SUBSET, "subset indices out of range");
+    if (a.subset && a.nsubset < 1) throw Error(BMX_ERR_ARG, "'subset.row' selects no genes");
+    if (a.subset && !a.correct_all && (a.cos_in != 0) != (a.cos_out != 0) && a.var_adj)
+        // R/mnnCorrect.R:466-471 indexes the already subset output genes with subset.row again
+        for (int i = 0; i < a.nsubset; ++i)
+            if (a.subset[i] > a.nsubset) throw Error(BMX_ERR_SUBSET, "subscript out of bounds");
+    if (a.k < 1) throw Error(BMX_ERR_ARG, "'k' must be positive");
+    if (!(a.sigma > 0.0)) throw Error(BMX_ERR_ARG, "'sigma' must be positive");
+    // the tree: post-order code, leaf = batch id, 0 = merge
+    std::vector<int> seen((size_t)a.B, 0);
+    int depth = 0;
+    for (int i = 0; i < a.tree_len; ++i) {
+        const int c = a.tree[i];
+        if (c == 0) {
+            if (depth < 2) throw Error(BMX_ERR_TREE, "merge tree structure should contain two children per node");
+            --depth;
+        } else {
+            if (c < 1 || c > a.B || seen[c - 1]) throw Error(BMX_ERR_TREE, "invalid leaf nodes specified in 'merge.order'");
+            seen[c - 1] = 1;
+            ++depth;
+        }
+    }
+    if (depth != 1 || a.tree_len != 2 * a.B - 1) throw Error(BMX_ERR_TREE, "invalid leaf nodes specified in 'merge.order'");
+}
+
+void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
+    mnn_correct_check(a);
+    const int B = a.B, G = a.G;
+    int dev = 0;
+    BMX_HIP(hipGetDevice(&dev));
+    Engine e(dev);
+    CacheScope cache_scope(e.cache());
+    hipStream_t s = e.stream();
+
+    // ---- the tree and the pool's row order (leaves left to right) ----
+    std::vector<TNode> t;
+    std::vector<int> stack, leaf_order;
+    for (int i = 0; i < a.tree_len; ++i) {
+        TNode x;
+        if (a.tree[i] != 0) {
+            x.index = {a.tree[i]};
+            leaf_order.push_back(a.tree[i] - 1);
+        } else {
+            x.right = stack.back();
+            stack.pop_back();
+            x.left = stack.back();
+            stack.pop_back();
+        }
+        t.push_back(std::move(x));
+        stack.push_back((int)t.size() - 1);
+    }
+    const int root = stack.back();
+    std::vector<int64_t> in_off((size_t)B + 1, 0), pool_off((size_t)B, 0);
+    for (int b = 0; b < B; ++b) in_off[b + 1] = in_off[b] + a.ncells[b];
+    const int64_t N = in_off[B];
+    if (N > (int64_t)1 << 30) throw Error(BMX_ERR_ARG, "too many cells for int32 indices");
+    {
+        int64_t r = 0;
+        for (int b : leaf_order) {
+            pool_off[b] = r;
+            r += a.ncells[b];
+        }
+    }
+    for (TNode& x : t) {
+        if (x.index.empty()) continue;
+        const int b = x.index[0] - 1;
+        x.row0 = (int)pool_off[b];
+        x.n = a.ncells[b];
+        const bool has = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
+        x.has_restrict = has;
+        if (has)
+            for (int i = 0; i < a.n_restrict[b]; ++i) x.restrict_rows.push_back(a.restrict_idx[b][i] - 1);
+    }
+
+    // ---- .prepare_input_data (R/mnnCorrect.R:398-445) ----
+    DevBuf<double> raw, subb, inb, outb, l2b;
+    double* X = raw.reserve((size_t)N * G);  // the caller's genes, pool order: a cell's G genes are contiguous in R's layout
+    for (int b = 0; b < B; ++b)
+        upload_pageable(X + pool_off[b] * G, a.data[b], (size_t)a.ncells[b] * G * sizeof(double), s);
+    // subset.row equal to every gene in order is no subset (:404)
+    bool subset = a.subset != nullptr && a.nsubset > 0;
+    if (subset && a.nsubset == G) {
+        bool ident = true;
+        for (int i = 0; i < G && ident; ++i) ident = a.subset[i] == i + 1;
+        if (ident) subset = false;
+    }
+    std::vector<int32_t> sub0;
+    DevBuf<int32_t> subd;
+    const int32_t* cols = nullptr;
+    if (subset) {
+        for (int i = 0; i < a.nsubset; ++i) sub0.push_back(a.subset[i] - 1);
+        cols = put(subd, sub0.data(), sub0.size(), s);
+    }
+    const int Gs = subset ? a.nsubset : G;
+    // S: the subset genes; In = S cosine-normalised with cos.norm.in; Out = all genes (correct.all) or S, cosine-normalised with
+    // cos.norm.out by the l2 norms of S (:419-431).  same.set: one matrix serves both.
+    double* S = X;
+    if (subset) {
+        S = subb.reserve((size_t)N * Gs);
+        gather_cols(s, X, N, G, cols, Gs, S);
+    }
+    const bool same = !(subset && a.correct_all) && (a.cos_in != 0) == (a.cos_out != 0);
+    double* l2 = l2b.reserve((size_t)N);
+    if (a.cos_in || a.cos_out) cosine_l2_device(s, S, Gs, (int)N, l2);
+    double* In = S;
+    if (a.cos_in) {
+        In = inb.reserve((size_t)N * Gs);
+        apply_cosine_norm_device(s, S, Gs, (int)N, l2, In);
+    }
+    double* Out = In;
+    int Go = Gs;
+    if (!same) {
+        Out = subset && a.correct_all ? X : S;
+        Go = subset && a.correct_all ? G : Gs;
+        if (a.cos_out) {
+            double* o = outb.reserve((size_t)N * Go);
+            apply_cosine_norm_device(s, Out, Go, (int)N, l2, o);
+            Out = o;
+        }
+    }
+
+    // ---- the merges ----
+    const int nm = B - 1;
+    res.left.assign(nm, {});
+    res.right.assign(nm, {});
+    res.pairs_left.assign(nm, {});
+    res.pairs_right.assign(nm, {});
+    std::vector<int> pl0(nm), pr0(nm);
+    DevBuf<double> avg, avg_out, corr_in, corr_out, dens, dens_out, scal, scal2, asv_ws, subL, subR, subC;
+    DevBuf<int32_t> first, second, idx, iota1, iota2;
+    std::vector<double> ones;
+    // per-stage HIP events of a merge (search + pairs, averaging, smoothing, var.adj, apply), read after its final wait
+    hipEvent_t ev[6];
+    for (hipEvent_t& x : ev) BMX_HIP(hipEventCreate(&x));
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 6; ++i) (void)hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    for (int mdx = 0; mdx < nm; ++mdx) {
+        const int at = next_merge(t, root);
+        TNode& L = t[t[at].left];
+        TNode& R = t[t[at].right];
+        if (R.row0 != L.row0 + L.n) throw Error(BMX_ERR_ARG, "internal: merge of non-adjacent nodes");
+        res.left[mdx] = L.index;
+        res.right[mdx] = R.index;
+        pl0[mdx] = L.row0;
+        pr0[mdx] = R.row0;
+        const int nl = L.n, nr = R.n;
+        Node Lv, Rv;
+        make_view(Lv, In, L, Gs, s);
+        make_view(Rv, In, R, Gs, s);
+        e.d_ = Gs;
+        // 1. .restricted_mnn
+        BMX_HIP(hipEventRecord(ev[0], s));
+        const Engine::MnnOut mo = e.find_mnn(Lv, Rv, a.k, a.prop_k);
+        const int nLs = L.has_restrict ? (int)L.restrict_rows.size() : nl;
+        const int nRs = R.has_restrict ? (int)R.restrict_rows.size() : nr;
+        const int32_t* lrows = L.has_restrict ? Lv.restrict_rows.p : nullptr;
+        const int32_t* rrows = R.has_restrict ? Rv.restrict_rows.p : nullptr;
+        const int32_t* rnext = Rv.restrict_dups ? Rv.dup_next.p : nullptr;
+        // 2. the pairs: 1-based rows of the nodes
+        int32_t* f = first.reserve((size_t)std::max<int64_t>(1, mo.P));
+        int32_t* sc = second.reserve((size_t)std::max<int64_t>(1, mo.P));
+        if (mo.P > 0)
+            emit_pairs(s, e.idxLR_.p, mo.nsel, mo.k2, e.idxRL_.p, mo.k1, e.offL_.p, lrows, rrows, f, sc, e.lsel_.p, e.maskL_.p,
+                       &e.sorted_);
+        res.pairs_left[mdx].resize((size_t)mo.P);
+        res.pairs_right[mdx].resize((size_t)mo.P);
+        if (mo.P > 0) {
+            BMX_HIP(hipMemcpyAsync(res.pairs_left[mdx].data(), f, (size_t)mo.P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            BMX_HIP(hipMemcpyAsync(res.pairs_right[mdx].data(), sc, (size_t)mo.P * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        // 3. averaging + smoothing (the kernel weights from the right node's input-gene rows)
+        BMX_HIP(hipEventRecord(ev[1], s));
+        const int U = mo.U;
+        int32_t* ix = idx.reserve((size_t)std::max(1, U));
+        if (U > 0) {
+            if (rrows)
+                compose_row_list(s, e.second_u_.p, U, rrows, ix);
+            else
+                BMX_HIP(hipMemcpyAsync(ix, e.second_u_.p, (size_t)U * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        }
+        double* dw = dens.reserve((size_t)nr + std::max(1, U));
+        double* av = avg.reserve((size_t)std::max(1, U) * Gs);
+        double* ci = corr_in.reserve((size_t)nr * Gs);
+        double* Lin = In + (int64_t)L.row0 * Gs;
+        double* Rin = In + (int64_t)R.row0 * Gs;
+        average_correction(s, e.red_ws_, Lin, lrows, Rin, rrows, Gs, e.second_u_.p, U, e.partR_.p, e.cntR_.p, mo.k1, av, false,
+                           nullptr, nullptr, nullptr, nullptr, rnext);
+        double* co = nullptr;
+        double* avo = nullptr;
+        double* Lout = Out + (int64_t)L.row0 * Go;
+        double* Rout = Out + (int64_t)R.row0 * Go;
+        if (!same) {
+            avo = avg_out.reserve((size_t)std::max(1, U) * Go);
+            average_correction(s, e.red_ws_, Lout, lrows, Rout, rrows, Go, e.second_u_.p, U, e.partR_.p, e.cntR_.p, mo.k1, avo,
+                               false, nullptr, nullptr, nullptr, nullptr, rnext);
+        }
+        BMX_HIP(hipEventRecord(ev[2], s));
+        smooth_gaussian_kernel_device(s, av, Gs, U, ix, Rin, Gs, nr, a.sigma, ci, dw);
+        if (!same) {
+            co = corr_out.reserve((size_t)nr * Go);
+            double* dwo = dens_out.reserve((size_t)nr + std::max(1, U));
+            smooth_gaussian_kernel_device(s, avo, Go, U, ix, Rin, Gs, nr, a.sigma, co, dwo);
+        }
+        // 4. var.adj
+        BMX_HIP(hipEventRecord(ev[3], s));
+        double* sv = scal.reserve((size_t)nr);
+        if (a.var_adj) {
+            const int32_t* r1 = lrows;
+            const int32_t* r2 = rrows;
+            std::vector<int32_t> io;
+            if (!r1) {
+                io.resize((size_t)nl);
+                for (int i = 0; i < nl; ++i) io[i] = i;
+                r1 = put(iota1, io.data(), io.size(), s);
+                BMX_HIP(hipStreamSynchronize(s));
+            }
+            if (!r2) {
+                io.resize((size_t)nr);
+                for (int i = 0; i < nr; ++i) io[i] = i;
+                r2 = put(iota2, io.data(), io.size(), s);
+                BMX_HIP(hipStreamSynchronize(s));
+            }
+            const AsvPlan plan = adjust_shift_variance_plan(Gs, nr, nLs, nRs, 1);
+            double* ws = asv_ws.reserve(plan.main_doubles + plan.extra_doubles);
+            adjust_shift_variance_device(s, Lin, Gs, nl, Rin, nr, ci, a.sigma, r1, nLs, r2, nRs, sv, ws, plan, 1);
+            double* sv2 = nullptr;
+            if (!same) {
+                // locations from the subset.row genes of the output matrix (R/mnnCorrect.R:466-471).  R keeps subset.row
+                // whenever it is not all genes, also when the output matrix is already the subset (correct.all = FALSE with
+                // cos.norm.in != cos.norm.out): its indices then pick columns of that matrix, as R's cell.vect[, subset.row]
+                // does (mnn_correct_check refuses indices beyond its width, where R fails with "subscript out of bounds").
+                const double* l1 = Lout;
+                const double* l2p = Rout;
+                const double* cv = co;
+                if (subset) {
+                    double* a1 = subL.reserve((size_t)nl * Gs);
+                    double* a2 = subR.reserve((size_t)nr * Gs);
+                    double* a3 = subC.reserve((size_t)nr * Gs);
+                    gather_cols(s, Lout, nl, Go, cols, Gs, a1);
+                    gather_cols(s, Rout, nr, Go, cols, Gs, a2);
+                    gather_cols(s, co, nr, Go, cols, Gs, a3);
+                    l1 = a1;
+                    l2p = a2;
+                    cv = a3;
+                }
+                sv2 = scal2.reserve((size_t)nr);
+                adjust_shift_variance_device(s, l1, Gs, nl, l2p, nr, cv, a.sigma, r1, nLs, r2, nRs, sv2, ws, plan, 1);
+            }
+            BMX_HIP(hipEventRecord(ev[4], s));
+            add_scaled_rows(s, Rin, nr, Gs, ci, sv);
+            if (!same) add_scaled_rows(s, Rout, nr, Go, co, sv2);
+        } else {
+            BMX_HIP(hipEventRecord(ev[4], s));
+            // right + correction: pmax(1, 1) * c = c exactly
+            if ((int)ones.size() < nr) ones.assign((size_t)nr, 1.0);
+            put(scal, ones.data(), (size_t)nr, s);
+            add_scaled_rows(s, Rin, nr, Gs, ci, sv);
+            if (!same) add_scaled_rows(s, Rout, nr, Go, co, sv);
+        }
+        BMX_HIP(hipEventRecord(ev[5], s));
+        BMX_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < 5; ++i) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) res.stage_ms[i] += ms;
+        }
+        // 5. UPDATE: rbind (the slices are adjacent), .combine_restrict (R/fastMNN.R:610-622)
+        TNode m;
+        m.row0 = L.row0;
+        m.n = nl + nr;
+        m.index = L.index;
+        m.index.insert(m.index.end(), R.index.begin(), R.index.end());
+        m.has_restrict = L.has_restrict || R.has_restrict;
+        if (m.has_restrict) {
+            if (L.has_restrict)
+                m.restrict_rows = L.restrict_rows;
+            else
+                for (int i = 0; i < nl; ++i) m.restrict_rows.push_back(i);
+            if (R.has_restrict)
+                for (int32_t v : R.restrict_rows) m.restrict_rows.push_back(v + nl);
+            else
+                for (int i = 0; i < nr; ++i) m.restrict_rows.push_back(nl + i);
+        }
+        t[at] = std::move(m);
+    }
+
+    // ---- outputs: input order (R/mnnCorrect.R:364-381) ----
+    std::vector<int32_t> dst((size_t)N);
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < a.ncells[b]; ++i) dst[(size_t)(pool_off[b] + i)] = (int32_t)(in_off[b] + i);
+    DevBuf<int32_t> dstd;
+    DevBuf<double> fin;
+    const int32_t* dd = put(dstd, dst.data(), dst.size(), s);
+    double* fo = fin.reserve((size_t)N * Go);
+    hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)((N * Go + 255) / 256)), dim3(256), 0, s, (const double*)Out, N, Go,
+                       dd, fo);
+    BMX_LAUNCH_CHECK();
+    res.Gout = Go;
+    res.corrected.resize((size_t)N * Go);
+    download_pageable(res.corrected.data(), fo, (size_t)N * Go * sizeof(double), s);
+    BMX_HIP(hipStreamSynchronize(s));
+    res.batch.resize((size_t)N);
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < a.ncells[b]; ++i) res.batch[(size_t)(in_off[b] + i)] = b + 1;
+    for (int mdx = 0; mdx < nm; ++mdx) {
+        for (int32_t& v : res.pairs_left[mdx]) v = dst[(size_t)(v - 1 + pl0[mdx])] + 1;
+        for (int32_t& v : res.pairs_right[mdx]) v = dst[(size_t)(v - 1 + pr0[mdx])] + 1;
+    }
+}
+
+}  // namespace bmx

@@ -69,7 +69,9 @@ int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, c
 /* Which form of adjust_shift_variance a call of these sizes takes (a pure function of the sizes): 1 = the reference's order
  * of operations literally (bit-equal to the CPU restatement, every cell; up to 4e7 (cell, restricted cell) pairs), 2 =
  * 16-cell tiles on the FP64 matrix cores with a histogram quantile (beyond that: a cell whose quantile walk is decided on
- * the last bits may land on the neighbouring quantile).  The engine's var_adj merges go through the same switch. */
+ * the last bits may land on the neighbouring quantile), 3 = the literal wide form (bit-equal to form 1; taken instead of
+ * form 2 above 256 genes, whatever the size, and at any size under the testing hook "asv_wide" -- this query knows no
+ * gene count, so it reports 3 only under the hook).  The engine's var_adj merges go through the same switch. */
 int32_t bmx_adjust_shift_variance_form(int32_t n2, int32_t nr1, int32_t nr2);
 
 /* ------------------------------------------------------------------------------------------------------------------
@@ -269,6 +271,45 @@ int32_t bmx_fast_mnn(int32_t nbatches, int32_t d, const double* const* data, con
                      const int32_t* tree, int32_t tree_len, double* corrected, int32_t* batch, int32_t* merge_left,
                      int32_t* merge_right, double* batch_size, int32_t* skipped, double* lost_var,
                      bmx_engine_t** out_engine);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * mnnCorrect() in gene space (R/mnnCorrect.R:125-393): the classic method end to end on the device, in place of the R
+ * shim's .mnn_correct.  Batches are R matrices: genes x cells, column-major; restrict and subset.row are 1-based.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t struct_size;      /* sizeof(bmx_mnn_params_t) as the caller's header has it (fields are only ever appended) */
+    int32_t k;                /* k = 20 */
+    double prop_k;            /* NaN = NULL */
+    double sigma;             /* sigma = 0.1 (handed to smooth_gaussian_kernel and adjust_shift_variance as is) */
+    int32_t cos_norm_in;      /* cos.norm.in = TRUE */
+    int32_t cos_norm_out;     /* cos.norm.out = TRUE */
+    int32_t var_adj;          /* var.adj = TRUE */
+    int32_t correct_all;      /* correct.all = FALSE */
+    int32_t svd_dim;          /* must be 0: svd.dim > 0 is refused (BMX_ERR_ARG) */
+    int32_t auto_merge;       /* must be 0: auto.merge = TRUE is refused (BMX_ERR_ARG) */
+    const int32_t* subset_row;  /* 1-based genes, or NULL */
+    int32_t n_subset_row;
+    const int32_t* tree;      /* the binarised merge tree in post-order: leaf = batch id, 0 = merge (as bmx_fast_mnn) */
+    int32_t tree_len;
+} bmx_mnn_params_t;
+typedef struct bmx_mnn_result bmx_mnn_result_t;
+/* Runs mnnCorrect on the calling thread's current device; every argument is checked before any device work.  *out holds
+ * the result until bmx_mnn_result_free. */
+int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* data, const int32_t* ncells,
+                        const int32_t* const* restrict_idx, const int32_t* n_restrict, const bmx_mnn_params_t* params,
+                        bmx_mnn_result_t** out);
+/* Sizes: genes of the corrected matrix (all genes with correct.all and a subset, else the subset's), cells, and the
+ * pairs of every merge (npairs [nbatches - 1], NULL to skip). */
+int32_t bmx_mnn_result_sizes(const bmx_mnn_result_t* r, int32_t* n_genes_out, int64_t* ncells, int64_t* npairs);
+/* Caller-allocated: corrected [n_genes_out x ncells] column-major, cells in input order; batch [ncells] 1-based;
+ * merge_left / merge_right [(nbatches - 1) x nbatches] row-major, batch ids zero-padded; pairs_left[m] / pairs_right[m]
+ * npairs[m] 1-based columns of `corrected` each (any pointer may be NULL to skip that output). */
+int32_t bmx_mnn_result_into(const bmx_mnn_result_t* r, double* corrected, int32_t* batch, int32_t* merge_left,
+                            int32_t* merge_right, int32_t* const* pairs_left, int32_t* const* pairs_right);
+/* Diagnostics: device time (HIP events, ms) over all merges of the stages search + pairs, averaging, smoothing,
+ * adjust_shift_variance (both calls), apply. */
+int32_t bmx_mnn_result_stage_ms(const bmx_mnn_result_t* r, double* out5);
+void bmx_mnn_result_free(bmx_mnn_result_t* r);
 
 /* Row range [begin, end) of `n` query rows owned by `rank` of `world` (pure host arithmetic, no GPU). */
 void bmx_shard_range(int64_t n, int32_t rank, int32_t world, int64_t* begin, int64_t* end);
