@@ -10,3 +10,4 @@ from .natives import (adjust_shift_variance, find_mutual_nn, find_mutual_nns, sm
 from .multi_batch_pca import DevicePCA, cosineNorm, multiBatchPCA, multiBatchPCA_host, project  # noqa: F401
 from .fast_mnn import fastMNN  # noqa: F401
 from .mnn_correct import mnnCorrect  # noqa: F401
+from .cluster_mnn import ClusterMnnResult, clusterMNN  # noqa: F401

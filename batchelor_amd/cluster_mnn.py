@@ -1,0 +1,329 @@
+"""clusterMNN() (R/clusterMNN.R:101-169): MNN correction of cluster centroids, propagated to every cell.
+
+The MNN search runs on a few hundred centroids (`reducedMNN(k=1)` on their full-rank PCs); the per-cell work is two
+streaming passes over each genes x cells matrix -- the centroid means and the projection -- plus a Gaussian smoothing of
+the centroids' correction vectors, all on the device behind the bmx_cluster_* entry points (csrc/cluster_mnn.hip).  The
+batches are uploaded once and stay in HBM between the two passes.  The full-rank PCA of the centroids (`.full_rank_pca`,
+:171-181) runs on the host: its input is genes x (number of clusters).
+
+Out of scope (a clear error): clustering itself (BlusterParam, cluster.d), more than 257 clusters in total (the merge
+engine takes at most 256 columns), SingleCellExperiment inputs.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Any, List, Optional
+
+import numpy as np
+
+from . import _lib
+from .mnn_correct import _subset_index
+from .reduced_mnn import reducedMNN
+
+MAX_DIMS = 256          # columns the merge engine takes (csrc/engine.hip)
+BLOCK_BYTES = 1 << 28   # a batch above this size goes to the device in column blocks of about this many bytes
+
+
+@dataclass
+class ClusterMnnResult:
+    """What clusterMNN() returns: the corrected low-rank coordinates of every cell and the metadata of R/clusterMNN.R:153-164."""
+    corrected: np.ndarray      # cells x d, cells in the caller's order
+    batch: np.ndarray          # batch id (1-based) or name per cell
+    cluster: np.ndarray        # each cell's cluster label
+    rotation: np.ndarray       # genes x d (all genes with correct_all, else the subset's)
+    centers: np.ndarray        # genes
+    merge_info: Any            # of the centroid-level reducedMNN; pairs index the rows of cluster_info
+    sigma: np.ndarray          # per batch: the bandwidth of the smoothing
+    cluster_info: dict         # columns "cluster", "batch", "meta", one row per centroid
+    stats: Optional[dict] = None   # "stage_ms": upload, centroids, projection, nearest_median, smoothing; "merge": per merge sizes
+
+
+def _as_index(restrict, n):
+    """One batch's restrict as 1-based int32 positions (None = all cells)."""
+    if restrict is None:
+        return None
+    r = np.asarray(restrict)
+    if r.dtype == bool:
+        if r.size != n:
+            raise ValueError("'restrict' indices out of range")
+        r = np.flatnonzero(r) + 1
+    r = np.ascontiguousarray(r, dtype=np.int64)
+    if r.size == 0:
+        raise ValueError("no cells remaining in a batch after restriction")  # R/checkInputs.R:116
+    if r.min() < 1 or r.max() > n:
+        raise ValueError("'restrict' indices out of range")
+    return r.astype(np.int32)
+
+
+def _format_clusters(ncells, clusters):
+    """.format_clusters (R/clusterMNN.R:185-227), the list branch."""
+    if not isinstance(clusters, (list, tuple)):
+        raise ValueError("'clusters' must be either a list or a BlusterParam object")
+    if len(clusters) != len(ncells):
+        raise ValueError("'...' and 'clusters' should be of the same length")
+    out = []
+    for n, c in zip(ncells, clusters):
+        c = np.asarray(c)
+        if c.ndim != 1 or c.shape[0] != n:
+            raise ValueError("corresponding entries of '...' and 'clusters' should have the same number of cells")
+        out.append(c)
+    return out
+
+
+def _levels(labels, restrict, which):
+    """Sorted unique labels of a batch (the order of sumCountsAcrossCells), each cell's 0-based level; every level needs a
+    restricted cell."""
+    levels, ids = np.unique(labels, return_inverse=True)
+    ids = ids.astype(np.int32)
+    kept = ids if restrict is None else ids[restrict - 1]
+    present = np.zeros(levels.size, dtype=bool)
+    present[kept] = True
+    if not present.all():
+        raise ValueError(f"cluster '{levels[np.flatnonzero(~present)[0]]}' of batch {which} has no cells remaining after "
+                         "restriction")
+    return levels, ids
+
+
+def _concat_labels(arrs):
+    if len({a.dtype.kind for a in arrs}) == 1:
+        return np.concatenate(arrs)
+    return np.concatenate([a.astype(object) for a in arrs])
+
+
+def full_rank_pca(centroids, subset_row=None, correct_all=False):
+    """.full_rank_pca (R/clusterMNN.R:171-181): multiBatchPCA(ExactParam, d = sum(ncol) - 1) of the centroid matrices
+    (genes x clusters each, all genes).  Centre: the grand mean of the batch means; every batch scaled by 1/sqrt(C_b); an
+    exact SVD.  Returns the rotation / centres over the genes used (`rotation_used`, `centers_used`: what the projection
+    takes), over the genes reported (`rotation`, `centers`: all genes with correct_all, R/multiBatchPCA.R:401-414), and the
+    centroids' coordinates `pcs` (C_b x d each)."""
+    G = centroids[0].shape[0]
+    sub = None if subset_row is None else np.asarray(subset_row, dtype=np.int64) - 1
+
+    def scale(rows):
+        cs = [c if rows is None else c[rows] for c in centroids]
+        grand = sum(c.mean(axis=1) for c in cs) / len(cs)
+        return cs, grand, np.concatenate([(c - grand[:, None]) / np.sqrt(c.shape[1]) for c in cs], axis=1)
+
+    cs, grand, scaled = scale(sub)
+    d = min(sum(c.shape[1] for c in cs) - 1, scaled.shape[0])
+    u, s, vt = np.linalg.svd(scaled, full_matrices=False)
+    u = np.ascontiguousarray(u[:, :d])
+    pcs = [(c - grand[:, None]).T @ u for c in cs]
+    rotation, centers = u, grand
+    if correct_all and sub is not None:
+        left = np.setdiff1d(np.arange(G), sub)
+        _, lgrand, lscaled = scale(left)
+        rotation = np.zeros((G, d))
+        rotation[sub] = u
+        rotation[left] = (lscaled @ vt[:d].T) / s[:d]
+        centers = np.zeros(G)
+        centers[sub] = grand
+        centers[left] = lgrand
+    return {"rotation_used": u, "centers_used": grand, "rotation": rotation, "centers": centers, "pcs": pcs, "d": d}
+
+
+def meta_clusters(pairs, nrows):
+    """components(make_graph(rbind(left, right), n))$membership (R/clusterMNN.R:162-164): connected components of the
+    graph of all MNN pairs over the centroid rows, numbered from 1 by each component's lowest row."""
+    parent = np.arange(nrows)
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    for left, right in pairs:
+        for a, b in zip(np.asarray(left).tolist(), np.asarray(right).tolist()):
+            ra, rb = find(a - 1), find(b - 1)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+    roots = np.array([find(i) for i in range(nrows)])
+    _, first, inverse = np.unique(roots, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first)] = np.arange(1, first.size + 1)
+    return rank[inverse]
+
+
+class _ClusterHandle:
+    """bmx_cluster_t: the batches stay in HBM between centroids() and propagate()."""
+
+    def __init__(self, n_genes, subset, device):
+        L = _lib.lib()
+        L.bmx_cluster_destroy.argtypes = [ctypes.c_void_p]
+        L.bmx_cluster_destroy.restype = None
+        self._h = ctypes.c_void_p()
+        self.G = int(n_genes)
+        self.rows = self.G if subset is None else int(subset.size)
+        _lib.check(L.bmx_cluster_create(ctypes.c_int32(int(device)), ctypes.c_int32(self.G),
+                                        None if subset is None else _lib.i32p(subset),
+                                        ctypes.c_int32(0 if subset is None else int(subset.size)), ctypes.byref(self._h)))
+        self.ncells, self.nclusters = [], []
+
+    def close(self):
+        if self._h:
+            _lib.lib().bmx_cluster_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_batch(self, x, ids, n_clusters, restrict, cos_norm, block_bytes=BLOCK_BYTES):
+        """x: genes x cells.  Above block_bytes the batch goes over in column blocks, converted to column-major one
+        block at a time (the whole matrix never exists twice on the host)."""
+        L = _lib.lib()
+        n = int(x.shape[1])
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        rp = None if restrict is None else _lib.i32p(restrict)
+        rn = ctypes.c_int64(-1 if restrict is None else int(restrict.size))
+        block = max(1, int(block_bytes) // (8 * self.G))
+        if n <= block:
+            xf = _lib.as_f(x)
+            _lib.check(L.bmx_cluster_add_batch(self._h, _lib.f64p(xf), ctypes.c_int64(n), _lib.i32p(ids),
+                                               ctypes.c_int32(int(n_clusters)), rp, rn, ctypes.c_int32(int(bool(cos_norm)))))
+        else:
+            _lib.check(L.bmx_cluster_begin_batch(self._h, ctypes.c_int64(n), _lib.i32p(ids), ctypes.c_int32(int(n_clusters)),
+                                                 rp, rn, ctypes.c_int32(int(bool(cos_norm)))))
+            for a in range(0, n, block):
+                xb = _lib.as_f(x[:, a:a + block])
+                _lib.check(L.bmx_cluster_add_block(self._h, _lib.f64p(xb), ctypes.c_int64(xb.shape[1])))
+        self.ncells.append(n)
+        self.nclusters.append(int(n_clusters))
+
+    def centroids(self, b):
+        out = np.empty((self.G, self.nclusters[b]), dtype=np.float64, order="F")
+        _lib.check(_lib.lib().bmx_cluster_centroids(self._h, ctypes.c_int32(b), _lib.f64p(out)))
+        return out
+
+    def propagate(self, b, rotation, centers, centroid_pcs, corrected_pcs):
+        rotation = _lib.as_f(rotation)
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        cp, cc = _lib.as_f(centroid_pcs), _lib.as_f(corrected_pcs)
+        d = int(rotation.shape[1])
+        if rotation.shape[0] != self.rows or centers.shape != (self.rows,):
+            raise ValueError("'rotation' and 'centers' must cover the genes in use")
+        if cp.shape != (self.nclusters[b], d) or cc.shape != cp.shape:
+            raise ValueError("the centroids' coordinates must be (number of clusters) x d")
+        out = np.empty((self.ncells[b], d), dtype=np.float64, order="F")
+        sigma = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().bmx_cluster_propagate(self._h, ctypes.c_int32(b), _lib.f64p(rotation), ctypes.c_int32(d),
+                                                    _lib.f64p(centers), _lib.f64p(cp), _lib.f64p(cc), _lib.f64p(out),
+                                                    ctypes.byref(sigma)))
+        return out, float(sigma.value)
+
+    def stage_ms(self):
+        st = np.zeros(5, dtype=np.float64)
+        _lib.check(_lib.lib().bmx_cluster_stage_ms(self._h, _lib.f64p(st)))
+        return dict(zip(("upload", "centroids", "projection", "nearest_median", "smoothing"), st.tolist()))
+
+
+def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
+                 names, device):
+    """The body of clusterMNN() from .format_clusters on (R/clusterMNN.R:134-164), for a list of batches."""
+    if len(mats) < 2:
+        raise ValueError("at least two batches must be specified")
+    G = mats[0].shape[0]
+    for m in mats:
+        if m.ndim != 2 or m.shape[0] != G:
+            raise ValueError("number of rows is not the same across batches")  # R/checkInputs.R:64
+    if restrict is not None and len(restrict) != len(mats):
+        raise ValueError("'restrictions' must of length equal to the number of batches")  # R/checkInputs.R:101
+    clusters = _format_clusters([m.shape[1] for m in mats], clusters)
+    restrict = [None] * len(mats) if restrict is None else [_as_index(r, m.shape[1]) for r, m in zip(restrict, mats)]
+    sub = _subset_index(subset_row, G)
+    if sub is not None and sub.size == 0:
+        raise ValueError("'subset_row' selects no genes")
+    lev = [_levels(c, r, b + 1) for b, (c, r) in enumerate(zip(clusters, restrict))]
+    total = sum(lv.size for lv, _ in lev)
+    if total - 1 > MAX_DIMS:
+        raise ValueError(f"clusterMNN works in sum(number of clusters) - 1 = {total - 1} dimensions; the merge engine takes "
+                         f"at most {MAX_DIMS}")
+    _lib.require_gpu()
+    h = _ClusterHandle(G, sub, device)
+    try:
+        for m, (lv, ids), r in zip(mats, lev, restrict):
+            h.add_batch(m, ids, lv.size, r, cos_norm)
+        cents = [h.centroids(b) for b in range(len(mats))]                                   # :143
+        pca = full_rank_pca(cents, sub, correct_all)                                          # :145
+        merged = reducedMNN(*pca["pcs"], k=1, merge_order=merge_order, auto_merge=auto_merge,
+                            min_batch_skip=min_batch_skip, names=names, device=device)       # :147
+        parts, sigma, last = [], [], 0
+        for b, p in enumerate(pca["pcs"]):                                                    # .propagate_to_cells
+            after = merged.corrected[last:last + p.shape[0]]
+            out, s = h.propagate(b, pca["rotation_used"], pca["centers_used"], p, after)
+            parts.append(out)
+            sigma.append(s)
+            last += p.shape[0]
+        stage_ms = h.stage_ms()
+    finally:
+        h.close()
+    ends = np.cumsum([p.shape[0] for p in pca["pcs"]])
+    cbatch = merged.batch
+    info = {"cluster": _concat_labels([lv for lv, _ in lev]), "batch": cbatch,
+            "meta": meta_clusters(merged.merge_info.pairs, int(ends[-1]))}
+    batch = np.concatenate([np.repeat(cbatch[e - 1:e], m.shape[1]) for e, m in zip(ends, mats)])
+    return ClusterMnnResult(corrected=np.concatenate(parts, axis=0), batch=batch, cluster=_concat_labels(clusters),
+                            rotation=pca["rotation"], centers=pca["centers"], merge_info=merged.merge_info,
+                            sigma=np.asarray(sigma), cluster_info=info, stats={"stage_ms": stage_ms, "merge": merged.stats})
+
+
+def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, merge_order=None, auto_merge=False,
+               min_batch_skip=0.0, subset_row=None, correct_all=False, device=0) -> ClusterMnnResult:
+    """clusterMNN(..., batch=, restrict=, clusters=, cos.norm=, merge.order=, auto.merge=, min.batch.skip=, subset.row=,
+    correct.all=) (R/clusterMNN.R:101-169).  Each batch is genes x cells; `clusters` is a list with one vector of labels
+    (integers or strings) per batch, or of length 1 for a single object that `batch=` splits."""
+    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
+        batches = tuple(batches[0])
+    if len(batches) == 0:
+        raise ValueError("at least two batches must be specified")
+    mats: List[np.ndarray] = [np.asarray(b) for b in batches]
+    if len(mats) > 1:
+        return _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row,
+                            correct_all, None, device)
+    # one object: divideIntoBatches(byrow=FALSE) and split(clusters[[1]], batch) (:121-132)
+    x = mats[0]
+    if batch is None:
+        raise ValueError("'batch' must be specified if '...' has only one object")  # R/checkInputs.R:128
+    batch = np.asarray(batch)
+    if x.ndim != 2 or batch.shape[0] != x.shape[1]:
+        raise ValueError("'length(batch)' and 'ncol(x)' are not the same")
+    if restrict is not None and len(restrict) != 1:
+        raise ValueError("'restrictions' must of length equal to the number of batches")
+    if isinstance(clusters, (list, tuple)):
+        if len(clusters) != 1:
+            raise ValueError("'clusters' must be a list of length 1 when '...' contains one element")
+        call = np.asarray(clusters[0])
+        if call.ndim != 1 or call.shape[0] != x.shape[1]:
+            raise ValueError("corresponding entries of '...' and 'clusters' should have the same number of cells")
+    else:
+        raise ValueError("'clusters' must be either a list or a BlusterParam object")
+    levels = sorted(set(batch.tolist()))
+    mask = None
+    if restrict is not None and restrict[0] is not None:
+        mask = np.zeros(x.shape[1], dtype=bool)
+        mask[_as_index(restrict[0], x.shape[1]) - 1] = True
+    parts, cparts, rparts = [], [], (None if mask is None else [])
+    reorder = np.zeros(x.shape[1], dtype=np.int64)
+    last = 0
+    for lv in levels:
+        keep = batch == lv
+        parts.append(x[:, keep])
+        cparts.append(call[keep])
+        if mask is not None:
+            cr = np.flatnonzero(mask[keep]) + 1
+            if cr.size == 0:
+                raise ValueError("no cells remaining in a batch after restriction")
+            rparts.append(cr.astype(np.int32))
+        cnt = int(keep.sum())
+        reorder[keep] = last + np.arange(1, cnt + 1)
+        last += cnt
+    out = _cluster_mnn(parts, rparts, cparts, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
+                       [str(lv) for lv in levels], device)
+    out.corrected = out.corrected[reorder - 1]  # output[, divided$reorder] (:166-168)
+    out.batch = out.batch[reorder - 1]
+    out.cluster = out.cluster[reorder - 1]
+    return out

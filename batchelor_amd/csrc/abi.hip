@@ -15,6 +15,7 @@
 
 #include "bmx_common.hpp"
 #include "bmx_ops.hpp"
+#include "cluster_mnn.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
 #include "mnn_correct.hpp"
@@ -810,6 +811,74 @@ int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, 
 
 int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out) {
     return guarded([&] { bmx::pca_project(p->impl, batch, out); });
+}
+
+/* ---------------------------------------------------------------- clusterMNN ------------------------------------ */
+struct bmx_cluster {
+    bmx::Cluster* impl = nullptr;
+    ~bmx_cluster() { bmx::cluster_destroy(impl); }
+};
+
+int32_t bmx_cluster_create(int32_t device, int32_t G, const int32_t* subset_row, int32_t n_subset_row, bmx_cluster_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "clusterMNN needs at least one gene");
+        if (n_subset_row < 0 || (n_subset_row > 0 && !subset_row)) throw bmx::Error(BMX_ERR_ARG, "invalid 'subset_row'");
+        for (int32_t i = 0; i < n_subset_row; ++i)
+            if (subset_row[i] < 1 || subset_row[i] > G) throw bmx::Error(BMX_ERR_SUBSET, "subset indices out of range");
+        auto h = std::make_unique<bmx_cluster>();
+        h->impl = bmx::cluster_create(device, G, subset_row, n_subset_row);
+        *out = h.release();
+    });
+}
+
+void bmx_cluster_destroy(bmx_cluster_t* h) { delete h; }
+
+int32_t bmx_cluster_begin_batch(bmx_cluster_t* h, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                                const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::cluster_begin_batch(h->impl, n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
+    });
+}
+
+int32_t bmx_cluster_add_block(bmx_cluster_t* h, const double* x_block, int64_t n_block) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::cluster_add_block(h->impl, x_block, n_block);
+    });
+}
+
+int32_t bmx_cluster_add_batch(bmx_cluster_t* h, const double* x, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                              const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        if (!x) throw bmx::Error(BMX_ERR_ARG, "the batch is missing");
+        bmx::cluster_begin_batch(h->impl, n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
+        bmx::cluster_add_block(h->impl, x, n);
+    });
+}
+
+int32_t bmx_cluster_centroids(bmx_cluster_t* h, int32_t batch, double* out) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::cluster_centroids(h->impl, batch, out);
+    });
+}
+
+int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rotation, int32_t d, const double* centers,
+                              const double* centroid_pcs, const double* corrected_pcs, double* out, double* sigma_out) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::cluster_propagate(h->impl, batch, rotation, d, centers, centroid_pcs, corrected_pcs, out, sigma_out);
+    });
+}
+
+int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5) {
+    return guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        bmx::cluster_stage_ms(h->impl, out5);
+    });
 }
 
 /* ---------------------------------------------------------------- engine ---------------------------------------- */

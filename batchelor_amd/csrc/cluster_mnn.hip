@@ -1,0 +1,570 @@
+// clusterMNN() on the device (R/clusterMNN.R:101-312): the two per-cell stages around the centroid-level merge.
+//   a. .compute_centroids (:231-244): the mean of every cluster's restricted cells, of cosineNorm(x) when asked for.
+//      The host sorts the restricted cells by cluster (a counting sort, ascending cell within a cluster) and cuts every
+//      cluster's list into chunks of CCH cells.  centroid_partial_kernel: one workgroup per (chunk, tile of 256 genes),
+//      lanes along the genes so that every cell's column is read coalesced, the chunk's cells added in list order;
+//      centroid_reduce_kernel adds a cluster's chunk sums in ascending chunk order and divides by the count.  No
+//      floating-point atomics anywhere: the result is the same bit for bit from run to run.  x is read once.
+//   b. .propagate_to_cells (:262-282) + .smooth_gaussian_from_centroids (:286-312) for one batch:
+//      cur = crossprod(cosineNorm(x)[subset,], rotation) - centers %*% rotation through cosnorm_project_device (the
+//      rotation scattered to all genes, zero outside the subset, so that x is again read once);
+//      nearest_kernel: every squared distance ||cur_i - centroid_j||^2 by differences, added over the columns in
+//      ascending order (contraction is off: each is the double a plain loop gives), kept as D2 [C][n], and the distance
+//      to the nearest centroid; median_select_kernel: sigma = median of those over the restricted cells by an exact
+//      radix selection on the doubles' bit patterns (the two middle values' mean for an even count, as numpy.median);
+//      smooth_kernel: w_ij = -D2_ij / sigma^2, softmax over j with the row maximum taken off, cur_i += sum_j w_ij delta_j
+//      in ascending j, the deltas staged through LDS sixteen columns at a time.
+// All FP64 vector arithmetic: the work is n C d multiply-adds, small next to the two streaming reads of x.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "bmx_ops.hpp"
+#include "cluster_mnn.hpp"
+#include "host_xfer.hpp"
+
+namespace bmx {
+namespace {
+
+constexpr int CCH = 256;  // cells per chunk of the centroid pass
+constexpr int JT = 16;    // centroids (nearest_kernel) / columns (smooth_kernel) per LDS tile
+constexpr int DMAX = 256;  // columns cosnorm_project_device and the merge engine take
+constexpr int MSEL_T = 1024;
+
+// l2 over the subset's genes only (cosineNorm(x, mode="l2norm", subset.row=), R/clusterMNN.R:140): one wave per cell
+__global__ __launch_bounds__(256) void colnorm_subset_kernel(const double* __restrict__ x, int G, int n,
+                                                             const int32_t* __restrict__ sub0, int ns,
+                                                             double* __restrict__ l2) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (c >= n) return;
+    const double* col = x + (int64_t)c * G;
+    double s = 0.0;
+    for (int i = lane; i < ns; i += 64) {
+        const double v = col[sub0[i]];
+        s += v * v;
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) l2[c] = sqrt(s);
+}
+
+// part[chunk][g] = sum over the chunk's cells, in list order, of x[g, cell] (/ pmax(1e-8, l2[cell]))
+__global__ __launch_bounds__(256) void centroid_partial_kernel(const double* __restrict__ x, int G,
+                                                               const double* __restrict__ l2,
+                                                               const int32_t* __restrict__ order,
+                                                               const int32_t* __restrict__ chunk_begin,
+                                                               double* __restrict__ part) {
+    const int g = blockIdx.y * 256 + threadIdx.x;
+    if (g >= G) return;
+    const int ch = blockIdx.x;
+    const int b = chunk_begin[ch], e = chunk_begin[ch + 1];
+    double s = 0.0;
+    int i = b;
+    for (; i + 4 <= e; i += 4) {  // four loads in flight, added in list order
+        const int c0 = order[i], c1 = order[i + 1], c2 = order[i + 2], c3 = order[i + 3];
+        double v0 = x[(int64_t)c0 * G + g], v1 = x[(int64_t)c1 * G + g];
+        double v2 = x[(int64_t)c2 * G + g], v3 = x[(int64_t)c3 * G + g];
+        if (l2) {
+            const double L0 = l2[c0], L1 = l2[c1], L2 = l2[c2], L3 = l2[c3];
+            v0 = v0 / (L0 < 1e-8 ? 1e-8 : L0);
+            v1 = v1 / (L1 < 1e-8 ? 1e-8 : L1);
+            v2 = v2 / (L2 < 1e-8 ? 1e-8 : L2);
+            v3 = v3 / (L3 < 1e-8 ? 1e-8 : L3);
+        }
+        s += v0;
+        s += v1;
+        s += v2;
+        s += v3;
+    }
+    for (; i < e; ++i) {
+        const int c = order[i];
+        double v = x[(int64_t)c * G + g];
+        if (l2) {
+            const double L = l2[c];
+            v = v / (L < 1e-8 ? 1e-8 : L);
+        }
+        s += v;
+    }
+    part[(int64_t)ch * G + g] = s;
+}
+
+// out[g, cl] = (sum of the cluster's chunk sums, ascending chunk) / count
+__global__ __launch_bounds__(256) void centroid_reduce_kernel(const double* __restrict__ part, int G, int C,
+                                                              const int32_t* __restrict__ cluster_chunk0,
+                                                              const int32_t* __restrict__ count,
+                                                              double* __restrict__ out) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int cl = blockIdx.y;
+    if (g >= G || cl >= C) return;
+    const int f = cluster_chunk0[cl], l = cluster_chunk0[cl + 1];
+    double s = part[(int64_t)f * G + g];
+    for (int ch = f + 1; ch < l; ++ch) s += part[(int64_t)ch * G + g];
+    out[(int64_t)cl * G + g] = s / (double)count[cl];
+}
+
+// cur[c, t] = acc[c, t] / pmax(1e-8, l2[c]) - cu[t], in place ([n x d] column-major)
+__global__ void finish_projection_kernel(double* __restrict__ cur, int n, int d, const double* __restrict__ l2,
+                                         const double* __restrict__ cu) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)n * d) return;
+    const int t = (int)(e / n);
+    const int c = (int)(e - (int64_t)t * n);
+    double v = cur[e];
+    if (l2) {
+        const double L = l2[c];
+        v = v / (L < 1e-8 ? 1e-8 : L);
+    }
+    cur[e] = v - cu[t];
+}
+
+// One thread per cell, 256 cells a workgroup, JT centroids staged in LDS at a time (every lane reads the same words: a
+// broadcast).  D2[j][c] = sum_t (cur[c, t] - cp[j, t])^2 with t ascending; dist[c] = sqrt(min_j D2[j][c]).
+__global__ __launch_bounds__(256) void nearest_kernel(const double* __restrict__ cur, int n, int d,
+                                                      const double* __restrict__ cp, int C, double* __restrict__ D2,
+                                                      double* __restrict__ dist) {
+    __shared__ double ps[DMAX * JT];  // [t][jj]
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int cc = c < n ? c : n - 1;
+    double best = 0.0;
+    for (int j0 = 0; j0 < C; j0 += JT) {
+        const int jn = min(JT, C - j0);
+        for (int e = threadIdx.x; e < d * JT; e += 256) {
+            const int t = e / JT, jj = e - t * JT;
+            ps[e] = jj < jn ? cp[(int64_t)t * C + j0 + jj] : 0.0;
+        }
+        __syncthreads();
+        double acc[JT];
+#pragma unroll
+        for (int jj = 0; jj < JT; ++jj) acc[jj] = 0.0;
+        for (int t = 0; t < d; ++t) {
+            const double xv = cur[(int64_t)t * n + cc];
+            const double* p = ps + t * JT;
+#pragma unroll
+            for (int jj = 0; jj < JT; ++jj) {
+                const double df = xv - p[jj];
+                acc[jj] += df * df;
+            }
+        }
+        if (c < n) {
+#pragma unroll
+            for (int jj = 0; jj < JT; ++jj)
+                if (jj < jn) {
+                    D2[(int64_t)(j0 + jj) * n + c] = acc[jj];
+                    if ((j0 == 0 && jj == 0) || acc[jj] < best) best = acc[jj];
+                }
+        }
+        __syncthreads();
+    }
+    if (c < n) dist[c] = sqrt(best);
+}
+
+// out[0] = numpy.median of dist[rows[i]] (rows null: dist[i]), i < m: one workgroup, eight passes of an 8-bit radix
+// selection over the bit patterns (non-negative doubles order as their unsigned patterns; a NaN, whose pattern sorts above
+// +Inf, makes the result NaN as numpy does), then one pass for the upper middle value of an even count.  Integer LDS
+// counters only: exact and the same from run to run.
+__global__ __launch_bounds__(MSEL_T) void median_select_kernel(const double* __restrict__ dist,
+                                                               const int32_t* __restrict__ rows, int64_t m,
+                                                               double* __restrict__ out) {
+    __shared__ unsigned int hist[256];
+    __shared__ unsigned long long s_prefix, s_k, s_cnt_le, s_min_gt;
+    __shared__ int s_nan;
+    const int tid = threadIdx.x;
+    const int64_t klo = (m - 1) / 2;  // 0-based rank of the lower middle value
+    if (tid == 0) {
+        s_prefix = 0ull;
+        s_k = (unsigned long long)klo;
+        s_cnt_le = 0ull;
+        s_min_gt = ~0ull;
+        s_nan = 0;
+    }
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0u;
+        __syncthreads();
+        const unsigned long long prefix = s_prefix;
+        int last = -1;
+        unsigned int run = 0u;  // a run of keys in one bucket costs one atomic
+        for (int64_t i = tid; i < m; i += MSEL_T) {
+            const double v = dist[rows ? rows[i] : i];
+            const unsigned long long key = (unsigned long long)__double_as_longlong(v);
+            if (shift == 56 && v != v) s_nan = 1;
+            if (shift == 56 || ((key ^ prefix) >> (shift + 8)) == 0ull) {
+                const int bkt = (int)((key >> shift) & 255ull);
+                if (bkt == last) {
+                    ++run;
+                } else {
+                    if (run) atomicAdd(&hist[last], run);
+                    last = bkt;
+                    run = 1u;
+                }
+            }
+        }
+        if (run) atomicAdd(&hist[last], run);
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long k = s_k;
+            int b = 0;
+            for (; b < 255; ++b) {
+                if (k < hist[b]) break;
+                k -= hist[b];
+            }
+            s_k = k;
+            s_prefix = prefix | ((unsigned long long)b << shift);
+        }
+        __syncthreads();
+    }
+    const unsigned long long lo = s_prefix;
+    unsigned long long cnt = 0ull, mn = ~0ull;
+    for (int64_t i = tid; i < m; i += MSEL_T) {
+        const unsigned long long key = (unsigned long long)__double_as_longlong(dist[rows ? rows[i] : i]);
+        if (key <= lo)
+            ++cnt;
+        else if (key < mn)
+            mn = key;
+    }
+    atomicAdd(&s_cnt_le, cnt);
+    atomicMin(&s_min_gt, mn);
+    __syncthreads();
+    if (tid == 0) {
+        const double a = __longlong_as_double((long long)lo);
+        double r = a;
+        if ((m & 1) == 0) {
+            const unsigned long long hi = s_cnt_le >= (unsigned long long)(klo + 2) ? lo : s_min_gt;
+            r = (a + __longlong_as_double((long long)hi)) / 2.0;
+        }
+        if (s_nan) r = __longlong_as_double(0x7ff8000000000000ll);
+        out[0] = r;
+    }
+}
+
+// .smooth_gaussian_from_centroids (R/clusterMNN.R:286-312), one thread per cell.  W [C][n] holds the squared distances on
+// entry and the normalised weights on exit; cur [n x d] column-major is updated in place.
+__global__ __launch_bounds__(256) void smooth_kernel(double* __restrict__ cur, int n, int d, double* __restrict__ W, int C,
+                                                     const double* __restrict__ cp, const double* __restrict__ corr,
+                                                     const double* __restrict__ sigma) {
+    extern __shared__ __attribute__((aligned(16))) char smem_s[];
+    double* ds = reinterpret_cast<double*>(smem_s);  // [C][JT]
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int cc = c < n ? c : n - 1;
+    const double sg = sigma[0];
+    const double s2 = sg * sg;
+    double top = 0.0;
+    for (int j = 0; j < C; ++j) {
+        const double w = -W[(int64_t)j * n + cc] / s2;
+        if (j == 0 || w > top) top = w;
+    }
+    double sum = 0.0;
+    if (c < n) {
+        for (int j = 0; j < C; ++j) {
+            const double e = exp(-W[(int64_t)j * n + c] / s2 - top);
+            W[(int64_t)j * n + c] = e;
+            sum += e;
+        }
+        for (int j = 0; j < C; ++j) W[(int64_t)j * n + c] = W[(int64_t)j * n + c] / sum;
+    }
+    for (int t0 = 0; t0 < d; t0 += JT) {
+        const int tn = min(JT, d - t0);
+        __syncthreads();  // (the previous tile has been read)
+        for (int e = threadIdx.x; e < C * JT; e += 256) {
+            const int j = e / JT, tt = e - j * JT;
+            const int64_t at = (int64_t)(t0 + tt) * C + j;
+            ds[e] = tt < tn ? corr[at] - cp[at] : 0.0;
+        }
+        __syncthreads();
+        double acc[JT];
+#pragma unroll
+        for (int tt = 0; tt < JT; ++tt) acc[tt] = tt < tn ? cur[(int64_t)(t0 + tt) * n + cc] : 0.0;
+        for (int j = 0; j < C; ++j) {
+            const double w = W[(int64_t)j * n + cc];
+            const double* p = ds + j * JT;
+#pragma unroll
+            for (int tt = 0; tt < JT; ++tt) acc[tt] += w * p[tt];
+        }
+        if (c < n) {
+#pragma unroll
+            for (int tt = 0; tt < JT; ++tt)
+                if (tt < tn) cur[(int64_t)(t0 + tt) * n + c] = acc[tt];
+        }
+    }
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+}  // namespace
+
+void cluster_check_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t n_restrict) {
+    if (n < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
+    if (n > 0x7fffffffll) throw Error(BMX_ERR_ARG, "a batch holds at most 2^31 - 1 cells");
+    if (C < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cluster");
+    if (C > 65535) throw Error(BMX_ERR_ARG, "a batch holds at most 65 535 clusters");
+    if (!clusters0) throw Error(BMX_ERR_ARG, "'clusters' is missing");
+    for (int64_t i = 0; i < n; ++i)
+        if (clusters0[i] < 0 || clusters0[i] >= C) throw Error(BMX_ERR_ARG, "cluster ids out of range");
+    std::vector<char> seen((size_t)C, 0);
+    if (restrict_idx && n_restrict >= 0) {
+        if (n_restrict == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
+        for (int64_t i = 0; i < n_restrict; ++i) {
+            if (restrict_idx[i] < 1 || restrict_idx[i] > n) throw Error(BMX_ERR_ARG, "'restrict' indices out of range");
+            seen[(size_t)clusters0[restrict_idx[i] - 1]] = 1;
+        }
+    } else {
+        for (int64_t i = 0; i < n; ++i) seen[(size_t)clusters0[i]] = 1;
+    }
+    for (int cl = 0; cl < C; ++cl)
+        if (!seen[(size_t)cl]) throw Error(BMX_ERR_ARG, "a cluster has no cells remaining after restriction");
+}
+
+struct ClusterBatch {
+    DevBuf<double> x;         // [n][G] (= genes x cells column-major)
+    DevBuf<double> l2;        // [n] column norms over the handle's genes, empty without cosine normalisation
+    DevBuf<int32_t> order;    // restricted cells (0-based) sorted by cluster, ascending within a cluster
+    DevBuf<int32_t> chunk_begin, cluster_chunk0, count;
+    DevBuf<int32_t> rows;     // restricted cells (0-based) in the caller's order, empty without restriction
+    int64_t n = 0, filled = 0, n_rows = 0;
+    int C = 0, nchunks = 0;
+    bool cos_norm = false;
+};
+
+class Cluster {
+  public:
+    Cluster(int device, int G, const int32_t* subset, int ns) : device_(device), G_(G) {
+        if (subset && ns > 0) sub0_host_.assign(subset, subset + ns);
+        for (int32_t& s : sub0_host_) s -= 1;
+        BMX_HIP(hipSetDevice(device_));
+        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        for (hipEvent_t& e : ev_) BMX_HIP(hipEventCreate(&e));
+        if (!sub0_host_.empty()) {
+            CacheScope scope(&cache_);
+            BMX_HIP(hipMemcpyAsync(sub0_.reserve(sub0_host_.size()), sub0_host_.data(), sub0_host_.size() * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, stream_));
+            BMX_HIP(hipStreamSynchronize(stream_));
+        }
+    }
+    ~Cluster() {
+        (void)hipSetDevice(device_);
+        if (stream_) {
+            (void)hipStreamSynchronize(stream_);
+            (void)hipStreamDestroy(stream_);
+        }
+        for (hipEvent_t e : ev_)
+            if (e) (void)hipEventDestroy(e);
+        DevBlockCache::current() = &cache_;  // the members' blocks go back to this handle's cache, which frees them
+    }
+
+    void begin_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t nr, bool cos_norm) {
+        cluster_check_batch(n, clusters0, C, restrict_idx, nr);
+        if (!batches_.empty() && batches_.back()->filled != batches_.back()->n)
+            throw Error(BMX_ERR_ARG, "the previous batch has not received all its cells");
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        const bool restricted = restrict_idx && nr >= 0;
+        // counting sort of the restricted cells by cluster (a cell named twice counts twice, as R's subsetting would)
+        std::vector<int32_t> cells;
+        if (restricted) {
+            cells.assign(restrict_idx, restrict_idx + nr);
+            for (int32_t& v : cells) v -= 1;
+        }
+        std::vector<int32_t> sorted_cells = cells;
+        std::sort(sorted_cells.begin(), sorted_cells.end());
+        const int64_t m = restricted ? nr : n;
+        std::vector<int32_t> count((size_t)C, 0), start((size_t)C + 1, 0);
+        for (int64_t i = 0; i < m; ++i) ++count[(size_t)clusters0[restricted ? sorted_cells[i] : i]];
+        for (int cl = 0; cl < C; ++cl) start[cl + 1] = start[cl] + count[cl];
+        std::vector<int32_t> order((size_t)m), fill(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < m; ++i) {
+            const int32_t cell = restricted ? sorted_cells[i] : (int32_t)i;
+            order[(size_t)fill[(size_t)clusters0[cell]]++] = cell;
+        }
+        std::vector<int32_t> chunk_begin, cluster_chunk0((size_t)C + 1, 0);
+        for (int cl = 0; cl < C; ++cl) {
+            cluster_chunk0[cl] = (int32_t)chunk_begin.size();
+            for (int32_t b = start[cl]; b < start[cl + 1]; b += CCH) chunk_begin.push_back(b);
+        }
+        cluster_chunk0[C] = (int32_t)chunk_begin.size();
+        chunk_begin.push_back(start[C]);
+
+        auto nb = std::make_unique<ClusterBatch>();
+        ClusterBatch& b = *nb;
+        b.n = n;
+        b.C = C;
+        b.cos_norm = cos_norm;
+        b.nchunks = cluster_chunk0[C];
+        b.n_rows = restricted ? nr : 0;
+        b.x.reserve((size_t)n * G_);
+        if (cos_norm) b.l2.reserve((size_t)n);
+        auto put = [&](DevBuf<int32_t>& dst, const std::vector<int32_t>& src) {
+            if (src.empty()) return;
+            BMX_HIP(hipMemcpyAsync(dst.reserve(src.size()), src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                   stream_));
+        };
+        put(b.order, order);
+        put(b.chunk_begin, chunk_begin);
+        put(b.cluster_chunk0, cluster_chunk0);
+        put(b.count, count);
+        put(b.rows, cells);
+        BMX_HIP(hipStreamSynchronize(stream_));  // the host vectors go out of scope
+        batches_.push_back(std::move(nb));
+    }
+
+    void add_block(const double* x_block, int64_t m) {
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        if (batches_.empty()) throw Error(BMX_ERR_ARG, "bmx_cluster_begin_batch has not been called");
+        ClusterBatch& b = *batches_.back();
+        if (m < 1 || b.filled + m > b.n) throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
+        if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
+        const double t0 = now_ms();
+        double* p = b.x.p + b.filled * G_;
+        upload_pageable(p, x_block, (size_t)m * G_ * sizeof(double), stream_);
+        if (b.cos_norm) {
+            if (sub0_host_.empty()) {
+                cosine_l2_device(stream_, p, G_, (int)m, b.l2.p + b.filled);
+            } else {
+                hipLaunchKernelGGL(colnorm_subset_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, (const double*)p,
+                                   G_, (int)m, (const int32_t*)sub0_.p, (int)sub0_host_.size(), b.l2.p + b.filled);
+                BMX_LAUNCH_CHECK();
+            }
+        }
+        b.filled += m;
+        if (b.filled == b.n) BMX_HIP(hipStreamSynchronize(stream_));
+        ms_[0] += now_ms() - t0;
+    }
+
+    ClusterBatch& batch(int bi) {
+        if (bi < 0 || bi >= (int)batches_.size()) throw Error(BMX_ERR_ARG, "batch index out of range");
+        ClusterBatch& b = *batches_[bi];
+        if (b.filled != b.n) throw Error(BMX_ERR_ARG, "the batch has not received all its cells");
+        return b;
+    }
+    int nrot() const { return sub0_host_.empty() ? G_ : (int)sub0_host_.size(); }
+
+    void centroids(int bi, double* out) {
+        ClusterBatch& b = batch(bi);
+        if (!out) throw Error(BMX_ERR_ARG, "'out' is missing");
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        const int G = G_;
+        double* part = part_.reserve((size_t)b.nchunks * G);
+        double* cen = cen_.reserve((size_t)b.C * G);
+        BMX_HIP(hipEventRecord(ev_[0], stream_));
+        hipLaunchKernelGGL(centroid_partial_kernel, dim3((unsigned)b.nchunks, (unsigned)cdiv(G, 256)), dim3(256), 0, stream_,
+                           (const double*)b.x.p, G, (const double*)(b.cos_norm ? b.l2.p : nullptr),
+                           (const int32_t*)b.order.p, (const int32_t*)b.chunk_begin.p, part);
+        BMX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(centroid_reduce_kernel, dim3((unsigned)cdiv(G, 256), (unsigned)b.C), dim3(256), 0, stream_,
+                           (const double*)part, G, b.C, (const int32_t*)b.cluster_chunk0.p, (const int32_t*)b.count.p, cen);
+        BMX_LAUNCH_CHECK();
+        BMX_HIP(hipEventRecord(ev_[1], stream_));
+        BMX_HIP(hipMemcpyAsync(out, cen, (size_t)b.C * G * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        BMX_HIP(hipStreamSynchronize(stream_));
+        add_span(1, 0, 1);
+    }
+
+    void propagate(int bi, const double* rotation, int d, const double* centers, const double* cpcs, const double* corr,
+                   double* out, double* sigma_out) {
+        ClusterBatch& b = batch(bi);
+        if (d < 1 || d > DMAX) throw Error(BMX_ERR_ARG, "the propagation takes 1 <= d <= 256 columns");
+        if (!rotation || !centers || !cpcs || !corr || !out)
+            throw Error(BMX_ERR_ARG, "'rotation', 'centers', the centroids' coordinates and 'out' must be given");
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        const int G = G_, n = (int)b.n, C = b.C;
+        const int ns = nrot();
+        // the rotation over all genes (zero outside the subset) and pca.center %*% pca.rotation (:271), on the host
+        std::vector<double> ufull((size_t)G * d, 0.0), cu((size_t)d, 0.0);
+        for (int j = 0; j < d; ++j) {
+            double s = 0.0;
+            for (int i = 0; i < ns; ++i) {
+                const int g = sub0_host_.empty() ? i : sub0_host_[(size_t)i];
+                ufull[(size_t)j * G + g] += rotation[(size_t)j * ns + i];
+                s += centers[i] * rotation[(size_t)j * ns + i];
+            }
+            cu[(size_t)j] = s;
+        }
+        double* U = u_.reserve((size_t)G * d);
+        double* small = small_.reserve((size_t)G + 3 * (size_t)d + 2 * (size_t)C * d + 8);
+        double* zero = small;                 // [G] centres handed to the projection: 0, the centring follows below
+        double* cu_scratch = zero + G;        // [d]
+        double* cu_dev = cu_scratch + d;      // [d]
+        double* cp_dev = cu_dev + d;          // [C x d]
+        double* corr_dev = cp_dev + (size_t)C * d;
+        double* sigma_dev = corr_dev + (size_t)C * d;
+        upload_pageable(U, ufull.data(), ufull.size() * sizeof(double), stream_);
+        BMX_HIP(hipMemsetAsync(zero, 0, (size_t)G * sizeof(double), stream_));
+        BMX_HIP(hipMemcpyAsync(cu_dev, cu.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream_));
+        BMX_HIP(hipMemcpyAsync(cp_dev, cpcs, (size_t)C * d * sizeof(double), hipMemcpyHostToDevice, stream_));
+        BMX_HIP(hipMemcpyAsync(corr_dev, corr, (size_t)C * d * sizeof(double), hipMemcpyHostToDevice, stream_));
+        double* cur = cur_.reserve((size_t)n * d);
+        double* W = w_.reserve((size_t)n * C);
+        double* dist = dist_.reserve((size_t)n);
+
+        BMX_HIP(hipEventRecord(ev_[0], stream_));
+        cosnorm_project_device(stream_, b.x.p, G, n, U, d, zero, 0, cur, nullptr, cu_scratch);
+        const int64_t total = (int64_t)n * d;
+        hipLaunchKernelGGL(finish_projection_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, cur, n, d,
+                           (const double*)(b.cos_norm ? b.l2.p : nullptr), (const double*)cu_dev);
+        BMX_LAUNCH_CHECK();
+        BMX_HIP(hipEventRecord(ev_[1], stream_));
+        hipLaunchKernelGGL(nearest_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream_, (const double*)cur, n, d,
+                           (const double*)cp_dev, C, W, dist);
+        BMX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(median_select_kernel, dim3(1), dim3(MSEL_T), 0, stream_, (const double*)dist,
+                           (const int32_t*)(b.n_rows ? b.rows.p : nullptr), b.n_rows ? b.n_rows : b.n, sigma_dev);
+        BMX_LAUNCH_CHECK();
+        BMX_HIP(hipEventRecord(ev_[2], stream_));
+        const size_t lds = (size_t)C * JT * sizeof(double);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&smooth_kernel), lds);
+        hipLaunchKernelGGL(smooth_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), lds, stream_, cur, n, d, W, C,
+                           (const double*)cp_dev, (const double*)corr_dev, (const double*)sigma_dev);
+        BMX_LAUNCH_CHECK();
+        BMX_HIP(hipEventRecord(ev_[3], stream_));
+        double sigma = 0.0;
+        BMX_HIP(hipMemcpyAsync(&sigma, sigma_dev, sizeof(double), hipMemcpyDeviceToHost, stream_));
+        download_pageable(out, cur, (size_t)n * d * sizeof(double), stream_);
+        BMX_HIP(hipStreamSynchronize(stream_));
+        if (sigma_out) *sigma_out = sigma;
+        add_span(2, 0, 1);
+        add_span(3, 1, 2);
+        add_span(4, 2, 3);
+    }
+
+    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+
+  private:
+    void add_span(int stage, int a, int b) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, ev_[a], ev_[b]) == hipSuccess) ms_[stage] += (double)ms;
+        (void)hipGetLastError();
+    }
+    DevBlockCache cache_;  // first: outlives the buffers below
+    int device_, G_;
+    hipStream_t stream_ = nullptr;
+    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<int32_t> sub0_host_;
+    DevBuf<int32_t> sub0_;
+    std::vector<std::unique_ptr<ClusterBatch>> batches_;
+    DevBuf<double> part_, cen_, u_, small_, cur_, w_, dist_;
+    double ms_[5] = {0, 0, 0, 0, 0};
+};
+
+Cluster* cluster_create(int device, int G, const int32_t* subset, int nsubset) {
+    return new Cluster(device, G, subset, nsubset);
+}
+void cluster_destroy(Cluster* c) { delete c; }
+void cluster_begin_batch(Cluster* c, int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx,
+                         int64_t n_restrict, int cos_norm) {
+    c->begin_batch(n, clusters0, C, restrict_idx, n_restrict, cos_norm != 0);
+}
+void cluster_add_block(Cluster* c, const double* x, int64_t m) { c->add_block(x, m); }
+void cluster_centroids(Cluster* c, int b, double* out) { c->centroids(b, out); }
+void cluster_propagate(Cluster* c, int b, const double* rotation, int d, const double* centers, const double* cpcs,
+                       const double* corr, double* out, double* sigma_out) {
+    c->propagate(b, rotation, d, centers, cpcs, corr, out, sigma_out);
+}
+void cluster_stage_ms(const Cluster* c, double* out5) { c->stage_ms(out5); }
+
+}  // namespace bmx

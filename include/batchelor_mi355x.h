@@ -378,6 +378,43 @@ int32_t bmx_pca_fit(bmx_pca_t* p, int32_t d, int32_t iters, double* centers, dou
 /* crossprod(cosineNorm(x_b) - centers, rotation) (R/multiBatchPCA.R:236-239): out [n_b x d] column-major. */
 int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * clusterMNN() (R/clusterMNN.R:101-312): the two per-cell stages around the centroid-level merge.  The batches (genes x
+ * cells, column-major) are uploaded once, whole or in column blocks through the pinned staging ring, and stay in HBM
+ * between the centroid pass and the propagation; a batch that does not fit fails with the allocation error.  The
+ * full-rank PCA of the centroids (.full_rank_pca, :171-181) and the merge itself (reducedMNN(k = 1): bmx_fast_mnn) stay
+ * with the caller.  Every argument is checked before any device work.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_cluster bmx_cluster_t;
+/* subset_row: 1-based genes (subset.row) the cosine norms and the projection are taken over (R/clusterMNN.R:140,274), or
+ * NULL / 0 for all genes.  The centroids always cover all n_genes (correct.all needs them). */
+int32_t bmx_cluster_create(int32_t device, int32_t n_genes, const int32_t* subset_row, int32_t n_subset_row,
+                           bmx_cluster_t** out);
+void bmx_cluster_destroy(bmx_cluster_t* h);
+/* x: n_genes x n column-major (host).  clusters0 [n]: 0-based cluster id of every cell, below n_clusters.  restrict_idx:
+ * 1-based cells, n_restrict of them (a cell named twice counts twice, as R's subsetting would), or NULL / n_restrict < 0
+ * for "all cells".  cos_norm != 0: columns over pmax(1e-8, l2) (R/cosineNorm.R:63-82).  A cluster without a restricted
+ * cell is BMX_ERR_ARG. */
+int32_t bmx_cluster_add_batch(bmx_cluster_t* h, const double* x, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                              const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm);
+/* The same batch in column blocks (as bmx_pca_begin_batch / bmx_pca_add_block): announce it, then its cells in order. */
+int32_t bmx_cluster_begin_batch(bmx_cluster_t* h, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                                const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm);
+int32_t bmx_cluster_add_block(bmx_cluster_t* h, const double* x_block, int64_t n_block);
+/* .compute_centroids (R/clusterMNN.R:231-244) of batch `batch` (0-based): out [n_genes x n_clusters] column-major, the
+ * mean of every cluster's restricted cells.  Bitwise the same from run to run (no floating-point atomics). */
+int32_t bmx_cluster_centroids(bmx_cluster_t* h, int32_t batch, double* out);
+/* .propagate_to_cells + .smooth_gaussian_from_centroids (R/clusterMNN.R:262-312) for one batch.  rotation [rows x d]
+ * column-major and centers [rows], rows = n_subset_row (in subset_row's order) or n_genes; centroid_pcs / corrected_pcs
+ * [n_clusters x d] column-major: the batch's centroids before and after the merge; 1 <= d <= 256.  out [n x d]
+ * column-major; *sigma_out (nullable) = the median distance of the restricted cells to their nearest centroid, equal to
+ * numpy.median of those distances bit for bit.  A sigma of 0 is not special-cased (NaN, as in the reference). */
+int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rotation, int32_t d, const double* centers,
+                              const double* centroid_pcs, const double* corrected_pcs, double* out, double* sigma_out);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), then HIP-event
+ * time of the centroid pass, the projection, nearest centroid + median, the smoothing. */
+int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5);
+
 #ifdef __cplusplus
 }
 #endif
