@@ -11,3 +11,4 @@ from .multi_batch_pca import DevicePCA, cosineNorm, multiBatchPCA, multiBatchPCA
 from .fast_mnn import fastMNN  # noqa: F401
 from .mnn_correct import mnnCorrect  # noqa: F401
 from .cluster_mnn import ClusterMnnResult, clusterMNN  # noqa: F401
+from .linear_correct import LinearCorrectResult, regressBatches, rescaleBatches  # noqa: F401

@@ -18,6 +18,7 @@
 #include "cluster_mnn.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
+#include "linear_correct.hpp"
 #include "mnn_correct.hpp"
 #include "rccl_dyn.hpp"
 
@@ -878,6 +879,75 @@ int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5) {
     return guarded([&] {
         if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
         bmx::cluster_stage_ms(h->impl, out5);
+    });
+}
+
+/* ---------------------------------------------------------------- rescaleBatches / regressBatches -------------- */
+struct bmx_linear {
+    bmx::Linear* impl = nullptr;
+    ~bmx_linear() { bmx::linear_destroy(impl); }
+};
+
+int32_t bmx_linear_create(int32_t device, int32_t G, bmx_linear_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "the linear corrections need at least one gene");
+        auto h = std::make_unique<bmx_linear>();
+        h->impl = bmx::linear_create(device, G);
+        *out = h.release();
+    });
+}
+
+void bmx_linear_destroy(bmx_linear_t* h) { delete h; }
+
+int32_t bmx_linear_expect(bmx_linear_t* h, int32_t kind, double log_base, double pseudo_count, int32_t keep_unlogged) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_expect(h->impl, kind, log_base, pseudo_count, keep_unlogged);
+    });
+}
+
+int32_t bmx_linear_begin_batch(bmx_linear_t* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_begin_batch(h->impl, n, restrict_idx, n_restrict);
+    });
+}
+
+int32_t bmx_linear_add_block(bmx_linear_t* h, const double* x_block, int64_t n_block) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_add_block(h->impl, x_block, n_block);
+    });
+}
+
+int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count, double* const* outs, double* avg_out,
+                           double* ref_out) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_rescale(h->impl, log_base, pseudo_count, outs, avg_out, ref_out);
+    });
+}
+
+int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
+                           int32_t n_keep, double* const* outs, double* coef_out) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_regress(h->impl, design, p, w, keep, n_keep, outs, coef_out);
+    });
+}
+
+int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs) {
+    return guarded([&] {
+        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+        bmx::linear_fetch(h->impl, outs);
+    });
+}
+
+int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5) {
+    return guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        bmx::linear_stage_ms(h->impl, out5);
     });
 }
 

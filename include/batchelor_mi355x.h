@@ -415,6 +415,54 @@ int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rot
  * time of the centroid pass, the projection, nearest centroid + median, the smoothing. */
 int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * rescaleBatches() (R/rescaleBatches.R:103-150) and regressBatches() (R/regressBatches.R:93-158): the linear
+ * corrections.  The batches (genes x cells, column-major) are uploaded once, whole or in column blocks through the
+ * pinned staging ring, and stay in HBM between the per-gene statistics and the pass that writes the result; results
+ * come back genes x cells, column-major, cells in input order.  subset.row is applied by the caller: it uploads the rows
+ * it wants corrected, n_genes of them.  Per-gene sums are taken over fixed chunks of a batch's restricted cells in a
+ * fixed order without floating-point atomics: the same input gives the same bits on every run and for every blocking of
+ * the upload.  Every argument is checked before any device work.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_linear bmx_linear_t;
+#define BMX_LINEAR_MAX_DESIGN_COLUMNS 64
+int32_t bmx_linear_create(int32_t device, int32_t n_genes, bmx_linear_t** out);
+void bmx_linear_destroy(bmx_linear_t* h);
+/* Optional, before the first batch: what is going to be asked for, so that the per-gene sums of a column block run
+ * behind the upload of the next block.  kind 0: nothing (the sums run inside bmx_linear_rescale / _regress); 1: plain sums
+ * (bmx_linear_regress without a design); 2: sums of log_base^x - pseudo_count (bmx_linear_rescale with these values).
+ * keep_unlogged != 0 (kind 2, batches without restriction): the unlogged values are kept in HBM and read by the second
+ * pass instead of being recomputed.  The results do not depend on this call. */
+int32_t bmx_linear_expect(bmx_linear_t* h, int32_t kind, double log_base, double pseudo_count, int32_t keep_unlogged);
+/* A batch of n cells.  restrict_idx: 1-based cells the statistics are taken over, n_restrict of them (a cell named twice
+ * counts twice, as R's subsetting would), or NULL / n_restrict < 0 for "all cells".  Its cells follow in one or more
+ * blocks (x_block: n_genes x n_block column-major, host), in order. */
+int32_t bmx_linear_begin_batch(bmx_linear_t* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict);
+int32_t bmx_linear_add_block(bmx_linear_t* h, const double* x_block, int64_t n_block);
+/* .rescale_batches (R/rescaleBatches.R:103-150).  outs[b]: n_genes x n_b column-major (caller-allocated), every cell of
+ * batch b.  avg_out [n_genes x n_batches] column-major (the mean of log_base^x - pseudo_count over each batch's
+ * restricted cells) and ref_out [n_genes] (their minimum over the batches) are nullable.  log(x, log_base) is log2 for 2,
+ * log10 for 10 and log(x) / log(log_base) otherwise, as in R.  At least two batches. */
+int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count, double* const* outs, double* avg_out,
+                           double* ref_out);
+/* regressBatches(): residuals of a per-gene least-squares fit on the restricted cells, for every cell.
+ * design == NULL: one indicator column per batch; outs[b] = x - (mean over batch b's restricted cells);
+ * coef_out [n_genes x n_batches] (nullable) holds the means; p, w, keep are ignored (n_keep must be 0).
+ * Otherwise design [N x p] column-major, N = all cells in upload order, 1 <= p <= 64, and w [R x p] column-major =
+ * the transposed pseudo-inverse of design's restricted rows (R rows: the restricted cells batch by batch, ascending
+ * within a batch), so that coef = X[, restricted] %*% w; the caller factors the design and refuses a rank-deficient
+ * one.  keep: 1-based columns of the design that are NOT regressed out (n_keep of them, may be 0).
+ * outs[b] = x - coef[, dropped] %*% t(design[cells of b, dropped]); coef_out [n_genes x p] (nullable). */
+int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
+                           int32_t n_keep, double* const* outs, double* coef_out);
+/* The batches as they were uploaded, back into outs[b] (n_genes x n_b) through the download ring with no kernel in
+ * between: the least that moving a call's bytes in and out costs (scripts/linear_correct_probe.py measures against it). */
+int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), HIP-event
+ * time of out[1] the first pass (chunk sums / the product with w), out[2] the statistics kernels, out[3] the second pass's
+ * kernels; out[4] = host wall time of the second pass with its downloads. */
+int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5);
+
 #ifdef __cplusplus
 }
 #endif
