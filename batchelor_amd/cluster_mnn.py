@@ -18,7 +18,8 @@ from typing import Any, List, Optional
 import numpy as np
 
 from . import _lib
-from .mnn_correct import _subset_index
+from ._handle import ResidentHandle
+from .inputs import check_restrict_length, check_same_dim, divide_into_batches, restrict_list, subset_index, unpack_batches
 from .reduced_mnn import reducedMNN
 
 MAX_DIMS = 256          # columns the merge engine takes (csrc/engine.hip)
@@ -37,23 +38,6 @@ class ClusterMnnResult:
     sigma: np.ndarray          # per batch: the bandwidth of the smoothing
     cluster_info: dict         # columns "cluster", "batch", "meta", one row per centroid
     stats: Optional[dict] = None   # "stage_ms": upload, centroids, projection, nearest_median, smoothing; "merge": per merge sizes
-
-
-def _as_index(restrict, n):
-    """One batch's restrict as 1-based int32 positions (None = all cells)."""
-    if restrict is None:
-        return None
-    r = np.asarray(restrict)
-    if r.dtype == bool:
-        if r.size != n:
-            raise ValueError("'restrict' indices out of range")
-        r = np.flatnonzero(r) + 1
-    r = np.ascontiguousarray(r, dtype=np.int64)
-    if r.size == 0:
-        raise ValueError("no cells remaining in a batch after restriction")  # R/checkInputs.R:116
-    if r.min() < 1 or r.max() > n:
-        raise ValueError("'restrict' indices out of range")
-    return r.astype(np.int32)
 
 
 def _format_clusters(ncells, clusters):
@@ -146,52 +130,23 @@ def meta_clusters(pairs, nrows):
     return rank[inverse]
 
 
-class _ClusterHandle:
+class _ClusterHandle(ResidentHandle):
     """bmx_cluster_t: the batches stay in HBM between centroids() and propagate()."""
+    PREFIX = "bmx_cluster"
+    STAGES = ("upload", "centroids", "projection", "nearest_median", "smoothing")
 
     def __init__(self, n_genes, subset, device):
-        L = _lib.lib()
-        L.bmx_cluster_destroy.argtypes = [ctypes.c_void_p]
-        L.bmx_cluster_destroy.restype = None
-        self._h = ctypes.c_void_p()
-        self.G = int(n_genes)
-        self.rows = self.G if subset is None else int(subset.size)
-        _lib.check(L.bmx_cluster_create(ctypes.c_int32(int(device)), ctypes.c_int32(self.G),
-                                        None if subset is None else _lib.i32p(subset),
-                                        ctypes.c_int32(0 if subset is None else int(subset.size)), ctypes.byref(self._h)))
-        self.ncells, self.nclusters = [], []
-
-    def close(self):
-        if self._h:
-            _lib.lib().bmx_cluster_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.rows = int(n_genes) if subset is None else int(subset.size)
+        self.nclusters = []
+        super().__init__(n_genes, device, None if subset is None else _lib.i32p(subset),
+                         ctypes.c_int32(0 if subset is None else int(subset.size)))
 
     def add_batch(self, x, ids, n_clusters, restrict, cos_norm, block_bytes=BLOCK_BYTES):
-        """x: genes x cells.  Above block_bytes the batch goes over in column blocks, converted to column-major one
-        block at a time (the whole matrix never exists twice on the host)."""
-        L = _lib.lib()
-        n = int(x.shape[1])
+        """x: genes x cells, `ids` each cell's 0-based cluster; see ResidentHandle._upload for block_bytes."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
-        rp = None if restrict is None else _lib.i32p(restrict)
-        rn = ctypes.c_int64(-1 if restrict is None else int(restrict.size))
-        block = max(1, int(block_bytes) // (8 * self.G))
-        if n <= block:
-            xf = _lib.as_f(x)
-            _lib.check(L.bmx_cluster_add_batch(self._h, _lib.f64p(xf), ctypes.c_int64(n), _lib.i32p(ids),
-                                               ctypes.c_int32(int(n_clusters)), rp, rn, ctypes.c_int32(int(bool(cos_norm)))))
-        else:
-            _lib.check(L.bmx_cluster_begin_batch(self._h, ctypes.c_int64(n), _lib.i32p(ids), ctypes.c_int32(int(n_clusters)),
-                                                 rp, rn, ctypes.c_int32(int(bool(cos_norm)))))
-            for a in range(0, n, block):
-                xb = _lib.as_f(x[:, a:a + block])
-                _lib.check(L.bmx_cluster_add_block(self._h, _lib.f64p(xb), ctypes.c_int64(xb.shape[1])))
-        self.ncells.append(n)
+        self._upload(x, block_bytes, _lib.i32p(ids), ctypes.c_int32(int(n_clusters)),
+                     None if restrict is None else _lib.i32p(restrict),
+                     ctypes.c_int64(-1 if restrict is None else int(restrict.size)), ctypes.c_int32(int(bool(cos_norm))))
         self.nclusters.append(int(n_clusters))
 
     def centroids(self, b):
@@ -215,26 +170,18 @@ class _ClusterHandle:
                                                     ctypes.byref(sigma)))
         return out, float(sigma.value)
 
-    def stage_ms(self):
-        st = np.zeros(5, dtype=np.float64)
-        _lib.check(_lib.lib().bmx_cluster_stage_ms(self._h, _lib.f64p(st)))
-        return dict(zip(("upload", "centroids", "projection", "nearest_median", "smoothing"), st.tolist()))
-
 
 def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
                  names, device):
     """The body of clusterMNN() from .format_clusters on (R/clusterMNN.R:134-164), for a list of batches."""
     if len(mats) < 2:
         raise ValueError("at least two batches must be specified")
-    G = mats[0].shape[0]
-    for m in mats:
-        if m.ndim != 2 or m.shape[0] != G:
-            raise ValueError("number of rows is not the same across batches")  # R/checkInputs.R:64
-    if restrict is not None and len(restrict) != len(mats):
-        raise ValueError("'restrictions' must of length equal to the number of batches")  # R/checkInputs.R:101
-    clusters = _format_clusters([m.shape[1] for m in mats], clusters)
-    restrict = [None] * len(mats) if restrict is None else [_as_index(r, m.shape[1]) for r, m in zip(restrict, mats)]
-    sub = _subset_index(subset_row, G)
+    G = check_same_dim(mats, byrow=False)
+    ncells = [m.shape[1] for m in mats]
+    check_restrict_length(restrict, len(mats))
+    clusters = _format_clusters(ncells, clusters)
+    restrict = restrict_list(restrict, ncells) or [None] * len(mats)
+    sub = subset_index(subset_row, G)
     if sub is not None and sub.size == 0:
         raise ValueError("'subset_row' selects no genes")
     lev = [_levels(c, r, b + 1) for b, (c, r) in enumerate(zip(clusters, restrict))]
@@ -276,8 +223,7 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, mer
     """clusterMNN(..., batch=, restrict=, clusters=, cos.norm=, merge.order=, auto.merge=, min.batch.skip=, subset.row=,
     correct.all=) (R/clusterMNN.R:101-169).  Each batch is genes x cells; `clusters` is a list with one vector of labels
     (integers or strings) per batch, or of length 1 for a single object that `batch=` splits."""
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
+    batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least two batches must be specified")
     mats: List[np.ndarray] = [np.asarray(b) for b in batches]
@@ -288,8 +234,7 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, mer
     x = mats[0]
     if batch is None:
         raise ValueError("'batch' must be specified if '...' has only one object")  # R/checkInputs.R:128
-    batch = np.asarray(batch)
-    if x.ndim != 2 or batch.shape[0] != x.shape[1]:
+    if x.ndim != 2 or np.asarray(batch).shape[0] != x.shape[1]:
         raise ValueError("'length(batch)' and 'ncol(x)' are not the same")
     if restrict is not None and len(restrict) != 1:
         raise ValueError("'restrictions' must of length equal to the number of batches")
@@ -301,28 +246,10 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, mer
             raise ValueError("corresponding entries of '...' and 'clusters' should have the same number of cells")
     else:
         raise ValueError("'clusters' must be either a list or a BlusterParam object")
-    levels = sorted(set(batch.tolist()))
-    mask = None
-    if restrict is not None and restrict[0] is not None:
-        mask = np.zeros(x.shape[1], dtype=bool)
-        mask[_as_index(restrict[0], x.shape[1]) - 1] = True
-    parts, cparts, rparts = [], [], (None if mask is None else [])
-    reorder = np.zeros(x.shape[1], dtype=np.int64)
-    last = 0
-    for lv in levels:
-        keep = batch == lv
-        parts.append(x[:, keep])
-        cparts.append(call[keep])
-        if mask is not None:
-            cr = np.flatnonzero(mask[keep]) + 1
-            if cr.size == 0:
-                raise ValueError("no cells remaining in a batch after restriction")
-            rparts.append(cr.astype(np.int32))
-        cnt = int(keep.sum())
-        reorder[keep] = last + np.arange(1, cnt + 1)
-        last += cnt
-    out = _cluster_mnn(parts, rparts, cparts, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
-                       [str(lv) for lv in levels], device)
+    div = divide_into_batches(x, batch, None if restrict is None else restrict[0], also=(call,))
+    out = _cluster_mnn(div.parts, div.restricted, div.also[0], cos_norm, merge_order, auto_merge, min_batch_skip, subset_row,
+                       correct_all, [str(lv) for lv in div.levels], device)
+    reorder = div.reorder
     out.corrected = out.corrected[reorder - 1]  # output[, divided$reorder] (:166-168)
     out.batch = out.batch[reorder - 1]
     out.cluster = out.cluster[reorder - 1]

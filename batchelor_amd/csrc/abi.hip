@@ -97,25 +97,38 @@ double* upload_rm(bmx::DevBuf<double>& tmp, bmx::DevBuf<double>& out, const doub
     return p;
 }
 
-// The caller's bmx_params_t may come from an older (shorter) or a newer (longer) header: struct_size says how much of
-// it is there.  Fields the caller does not have keep their defaults; bytes this library does not know must be zero.
-bmx_params_t read_params(const bmx_params_t* params) {
+// A parameter struct (bmx_params_t, bmx_mnn_params_t: `name`) may come from an older (shorter) or a newer (longer)
+// header: struct_size says how much of it is there, at least `need` bytes.  Fields the caller does not have keep the
+// values of `defaults`; bytes this library does not know must be zero.
+template <class P>
+P read_versioned(const P* params, size_t need, const char* name, P defaults) {
     if (!params) throw bmx::Error(BMX_ERR_ARG, "null params");
-    bmx_params_t p;
-    std::memset(&p, 0, sizeof(p));
-    p.sigma = 0.1;
+    P p = defaults;
     const int32_t sz = params->struct_size;
-    const size_t need = offsetof(bmx_params_t, auto_merge) + sizeof(int32_t);
     if (sz < (int32_t)need)
-        throw bmx::Error(BMX_ERR_ARG, "bmx_params_t.struct_size is not set (expected sizeof(bmx_params_t))");
+        throw bmx::Error(BMX_ERR_ARG, std::string(name) + ".struct_size is not set (expected sizeof(" + name + "))");
     if ((size_t)sz > sizeof(p)) {
         const unsigned char* extra = reinterpret_cast<const unsigned char*>(params) + sizeof(p);
         for (size_t i = 0; i < (size_t)sz - sizeof(p); ++i)
-            if (extra[i]) throw bmx::Error(BMX_ERR_ARG, "bmx_params_t carries fields this library version does not know");
+            if (extra[i]) throw bmx::Error(BMX_ERR_ARG, std::string(name) + " carries fields this library version does not know");
     }
     std::memcpy(&p, params, std::min((size_t)sz, sizeof(p)));
     p.struct_size = (int32_t)sizeof(p);
     return p;
+}
+
+bmx_params_t read_params(const bmx_params_t* params) {
+    bmx_params_t defaults;
+    std::memset(&defaults, 0, sizeof(defaults));
+    defaults.sigma = 0.1;
+    return read_versioned(params, offsetof(bmx_params_t, auto_merge) + sizeof(int32_t), "bmx_params_t", defaults);
+}
+
+// the implementation behind a handle of the C ABI
+template <class H>
+auto impl_of(H* h) -> decltype(h->impl) {
+    if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
+    return h->impl;
 }
 
 template <class T>
@@ -438,18 +451,10 @@ int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* 
     return guarded([&] {
         if (!out) throw bmx::Error(BMX_ERR_ARG, "null result pointer");
         *out = nullptr;
-        if (!params) throw bmx::Error(BMX_ERR_ARG, "null params");
-        bmx_mnn_params_t p;
-        std::memset(&p, 0, sizeof(p));
-        const int32_t sz = params->struct_size;
-        if (sz < (int32_t)(offsetof(bmx_mnn_params_t, tree_len) + sizeof(int32_t)))
-            throw bmx::Error(BMX_ERR_ARG, "bmx_mnn_params_t.struct_size is not set (expected sizeof(bmx_mnn_params_t))");
-        if ((size_t)sz > sizeof(p)) {
-            const unsigned char* extra = reinterpret_cast<const unsigned char*>(params) + sizeof(p);
-            for (size_t i = 0; i < (size_t)sz - sizeof(p); ++i)
-                if (extra[i]) throw bmx::Error(BMX_ERR_ARG, "bmx_mnn_params_t carries fields this library version does not know");
-        }
-        std::memcpy(&p, params, std::min((size_t)sz, sizeof(p)));
+        bmx_mnn_params_t zeros;
+        std::memset(&zeros, 0, sizeof(zeros));
+        const bmx_mnn_params_t p = read_versioned(params, offsetof(bmx_mnn_params_t, tree_len) + sizeof(int32_t),
+                                                  "bmx_mnn_params_t", zeros);
         if (nbatches < 2) throw bmx::Error(BMX_ERR_ARG, "at least two batches must be specified");
         if (!data || !ncells) throw bmx::Error(BMX_ERR_ARG, "null batch arrays");
         bmx::MnnCorrectArgs a;
@@ -777,19 +782,19 @@ int32_t bmx_pca_create(int32_t device, int32_t G, bmx_pca_t** out) {
 void bmx_pca_destroy(bmx_pca_t* p) { delete p; }
 
 int32_t bmx_pca_add_batch(bmx_pca_t* p, const double* x, int64_t n, double weight, int32_t cos_norm) {
-    return guarded([&] { bmx::pca_add_batch(p->impl, x, n, weight, cos_norm); });
+    return guarded([&] { bmx::pca_add_batch(impl_of(p), x, n, weight, cos_norm); });
 }
 
 int32_t bmx_pca_begin_batch(bmx_pca_t* p, int64_t n, double weight, int32_t cos_norm) {
-    return guarded([&] { bmx::pca_begin_batch(p->impl, n, weight, cos_norm); });
+    return guarded([&] { bmx::pca_begin_batch(impl_of(p), n, weight, cos_norm); });
 }
 
 int32_t bmx_pca_add_block(bmx_pca_t* p, const double* x_block, int64_t n_block) {
-    return guarded([&] { bmx::pca_add_block(p->impl, x_block, n_block); });
+    return guarded([&] { bmx::pca_add_block(impl_of(p), x_block, n_block); });
 }
 
 int32_t bmx_pca_fit(bmx_pca_t* p, int32_t d, int32_t iters, double* centers, double* rotation, double* sdev) {
-    return guarded([&] { bmx::pca_fit(p->impl, d, 0.0, iters, centers, rotation, sdev, nullptr, nullptr); });
+    return guarded([&] { bmx::pca_fit(impl_of(p), d, 0.0, iters, centers, rotation, sdev, nullptr, nullptr); });
 }
 
 int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, double* centers, double* rotation,
@@ -799,7 +804,7 @@ int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, 
         int used = 0;
         double res = 0.0;
         try {
-            bmx::pca_fit(p->impl, d, tol, max_iters, centers, rotation, sdev, &used, &res);
+            bmx::pca_fit(impl_of(p), d, tol, max_iters, centers, rotation, sdev, &used, &res);
         } catch (...) {
             if (iters_used) *iters_used = used;
             if (residual) *residual = res;
@@ -811,7 +816,7 @@ int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, 
 }
 
 int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out) {
-    return guarded([&] { bmx::pca_project(p->impl, batch, out); });
+    return guarded([&] { bmx::pca_project(impl_of(p), batch, out); });
 }
 
 /* ---------------------------------------------------------------- clusterMNN ------------------------------------ */
@@ -838,40 +843,35 @@ void bmx_cluster_destroy(bmx_cluster_t* h) { delete h; }
 int32_t bmx_cluster_begin_batch(bmx_cluster_t* h, int64_t n, const int32_t* clusters0, int32_t n_clusters,
                                 const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::cluster_begin_batch(h->impl, n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
+        bmx::cluster_begin_batch(impl_of(h), n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
     });
 }
 
 int32_t bmx_cluster_add_block(bmx_cluster_t* h, const double* x_block, int64_t n_block) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::cluster_add_block(h->impl, x_block, n_block);
+        bmx::cluster_add_block(impl_of(h), x_block, n_block);
     });
 }
 
 int32_t bmx_cluster_add_batch(bmx_cluster_t* h, const double* x, int64_t n, const int32_t* clusters0, int32_t n_clusters,
                               const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
         if (!x) throw bmx::Error(BMX_ERR_ARG, "the batch is missing");
-        bmx::cluster_begin_batch(h->impl, n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
-        bmx::cluster_add_block(h->impl, x, n);
+        bmx::cluster_begin_batch(impl_of(h), n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
+        bmx::cluster_add_block(impl_of(h), x, n);
     });
 }
 
 int32_t bmx_cluster_centroids(bmx_cluster_t* h, int32_t batch, double* out) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::cluster_centroids(h->impl, batch, out);
+        bmx::cluster_centroids(impl_of(h), batch, out);
     });
 }
 
 int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rotation, int32_t d, const double* centers,
                               const double* centroid_pcs, const double* corrected_pcs, double* out, double* sigma_out) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::cluster_propagate(h->impl, batch, rotation, d, centers, centroid_pcs, corrected_pcs, out, sigma_out);
+        bmx::cluster_propagate(impl_of(h), batch, rotation, d, centers, centroid_pcs, corrected_pcs, out, sigma_out);
     });
 }
 
@@ -902,45 +902,39 @@ void bmx_linear_destroy(bmx_linear_t* h) { delete h; }
 
 int32_t bmx_linear_expect(bmx_linear_t* h, int32_t kind, double log_base, double pseudo_count, int32_t keep_unlogged) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_expect(h->impl, kind, log_base, pseudo_count, keep_unlogged);
+        bmx::linear_expect(impl_of(h), kind, log_base, pseudo_count, keep_unlogged);
     });
 }
 
 int32_t bmx_linear_begin_batch(bmx_linear_t* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_begin_batch(h->impl, n, restrict_idx, n_restrict);
+        bmx::linear_begin_batch(impl_of(h), n, restrict_idx, n_restrict);
     });
 }
 
 int32_t bmx_linear_add_block(bmx_linear_t* h, const double* x_block, int64_t n_block) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_add_block(h->impl, x_block, n_block);
+        bmx::linear_add_block(impl_of(h), x_block, n_block);
     });
 }
 
 int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count, double* const* outs, double* avg_out,
                            double* ref_out) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_rescale(h->impl, log_base, pseudo_count, outs, avg_out, ref_out);
+        bmx::linear_rescale(impl_of(h), log_base, pseudo_count, outs, avg_out, ref_out);
     });
 }
 
 int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
                            int32_t n_keep, double* const* outs, double* coef_out) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_regress(h->impl, design, p, w, keep, n_keep, outs, coef_out);
+        bmx::linear_regress(impl_of(h), design, p, w, keep, n_keep, outs, coef_out);
     });
 }
 
 int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs) {
     return guarded([&] {
-        if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-        bmx::linear_fetch(h->impl, outs);
+        bmx::linear_fetch(impl_of(h), outs);
     });
 }
 

@@ -16,7 +16,6 @@
 //      in ascending j, the deltas staged through LDS sixteen columns at a time.
 // All FP64 vector arithmetic: the work is n C d multiply-adds, small next to the two streaming reads of x.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -25,6 +24,7 @@
 #include "bmx_ops.hpp"
 #include "cluster_mnn.hpp"
 #include "host_xfer.hpp"
+#include "resident_batches.hpp"
 
 namespace bmx {
 namespace {
@@ -290,27 +290,19 @@ __global__ __launch_bounds__(256) void smooth_kernel(double* __restrict__ cur, i
     }
 }
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 void cluster_check_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t n_restrict) {
-    if (n < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
-    if (n > 0x7fffffffll) throw Error(BMX_ERR_ARG, "a batch holds at most 2^31 - 1 cells");
+    check_cell_count(n);
     if (C < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cluster");
     if (C > 65535) throw Error(BMX_ERR_ARG, "a batch holds at most 65 535 clusters");
     if (!clusters0) throw Error(BMX_ERR_ARG, "'clusters' is missing");
     for (int64_t i = 0; i < n; ++i)
         if (clusters0[i] < 0 || clusters0[i] >= C) throw Error(BMX_ERR_ARG, "cluster ids out of range");
+    check_restriction(n, restrict_idx, n_restrict);
     std::vector<char> seen((size_t)C, 0);
-    if (restrict_idx && n_restrict >= 0) {
-        if (n_restrict == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
-        for (int64_t i = 0; i < n_restrict; ++i) {
-            if (restrict_idx[i] < 1 || restrict_idx[i] > n) throw Error(BMX_ERR_ARG, "'restrict' indices out of range");
-            seen[(size_t)clusters0[restrict_idx[i] - 1]] = 1;
-        }
+    if (is_restricted(restrict_idx, n_restrict)) {
+        for (int64_t i = 0; i < n_restrict; ++i) seen[(size_t)clusters0[restrict_idx[i] - 1]] = 1;
     } else {
         for (int64_t i = 0; i < n; ++i) seen[(size_t)clusters0[i]] = 1;
     }
@@ -318,25 +310,21 @@ void cluster_check_batch(int64_t n, const int32_t* clusters0, int C, const int32
         if (!seen[(size_t)cl]) throw Error(BMX_ERR_ARG, "a cluster has no cells remaining after restriction");
 }
 
-struct ClusterBatch {
-    DevBuf<double> x;         // [n][G] (= genes x cells column-major)
+struct ClusterBatch : ResidentBatch {
     DevBuf<double> l2;        // [n] column norms over the handle's genes, empty without cosine normalisation
     DevBuf<int32_t> order;    // restricted cells (0-based) sorted by cluster, ascending within a cluster
     DevBuf<int32_t> chunk_begin, cluster_chunk0, count;
     DevBuf<int32_t> rows;     // restricted cells (0-based) in the caller's order, empty without restriction
-    int64_t n = 0, filled = 0, n_rows = 0;
+    int64_t n_rows = 0;
     int C = 0, nchunks = 0;
     bool cos_norm = false;
 };
 
-class Cluster {
+class Cluster : ResidentBatches<ClusterBatch> {
   public:
-    Cluster(int device, int G, const int32_t* subset, int ns) : device_(device), G_(G) {
+    Cluster(int device, int G, const int32_t* subset, int ns) : ResidentBatches(device, G, "bmx_cluster_begin_batch") {
         if (subset && ns > 0) sub0_host_.assign(subset, subset + ns);
         for (int32_t& s : sub0_host_) s -= 1;
-        BMX_HIP(hipSetDevice(device_));
-        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-        for (hipEvent_t& e : ev_) BMX_HIP(hipEventCreate(&e));
         if (!sub0_host_.empty()) {
             CacheScope scope(&cache_);
             BMX_HIP(hipMemcpyAsync(sub0_.reserve(sub0_host_.size()), sub0_host_.data(), sub0_host_.size() * sizeof(int32_t),
@@ -344,24 +332,11 @@ class Cluster {
             BMX_HIP(hipStreamSynchronize(stream_));
         }
     }
-    ~Cluster() {
-        (void)hipSetDevice(device_);
-        if (stream_) {
-            (void)hipStreamSynchronize(stream_);
-            (void)hipStreamDestroy(stream_);
-        }
-        for (hipEvent_t e : ev_)
-            if (e) (void)hipEventDestroy(e);
-        DevBlockCache::current() = &cache_;  // the members' blocks go back to this handle's cache, which frees them
-    }
+    ~Cluster() { retire(); }
 
     void begin_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t nr, bool cos_norm) {
         cluster_check_batch(n, clusters0, C, restrict_idx, nr);
-        if (!batches_.empty() && batches_.back()->filled != batches_.back()->n)
-            throw Error(BMX_ERR_ARG, "the previous batch has not received all its cells");
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        const bool restricted = restrict_idx && nr >= 0;
+        const bool restricted = is_restricted(restrict_idx, nr);
         // counting sort of the restricted cells by cluster (a cell named twice counts twice, as R's subsetting would)
         std::vector<int32_t> cells;
         if (restricted) {
@@ -387,50 +362,41 @@ class Cluster {
         cluster_chunk0[C] = (int32_t)chunk_begin.size();
         chunk_begin.push_back(start[C]);
 
-        auto nb = std::make_unique<ClusterBatch>();
-        ClusterBatch& b = *nb;
-        b.n = n;
-        b.C = C;
-        b.cos_norm = cos_norm;
-        b.nchunks = cluster_chunk0[C];
-        b.n_rows = restricted ? nr : 0;
-        b.x.reserve((size_t)n * G_);
-        if (cos_norm) b.l2.reserve((size_t)n);
-        auto put = [&](DevBuf<int32_t>& dst, const std::vector<int32_t>& src) {
-            if (src.empty()) return;
-            BMX_HIP(hipMemcpyAsync(dst.reserve(src.size()), src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                   stream_));
-        };
-        put(b.order, order);
-        put(b.chunk_begin, chunk_begin);
-        put(b.cluster_chunk0, cluster_chunk0);
-        put(b.count, count);
-        put(b.rows, cells);
-        BMX_HIP(hipStreamSynchronize(stream_));  // the host vectors go out of scope
-        batches_.push_back(std::move(nb));
+        begin(n, [&](ClusterBatch& b) {
+            b.C = C;
+            b.cos_norm = cos_norm;
+            b.nchunks = cluster_chunk0[C];
+            b.n_rows = restricted ? nr : 0;
+            if (cos_norm) b.l2.reserve((size_t)n);
+            auto put = [&](DevBuf<int32_t>& dst, const std::vector<int32_t>& src) {
+                if (src.empty()) return;
+                BMX_HIP(hipMemcpyAsync(dst.reserve(src.size()), src.data(), src.size() * sizeof(int32_t),
+                                       hipMemcpyHostToDevice, stream_));
+            };
+            put(b.order, order);
+            put(b.chunk_begin, chunk_begin);
+            put(b.cluster_chunk0, cluster_chunk0);
+            put(b.count, count);
+            put(b.rows, cells);
+            BMX_HIP(hipStreamSynchronize(stream_));  // the host vectors go out of scope
+        });
     }
 
     void add_block(const double* x_block, int64_t m) {
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        if (batches_.empty()) throw Error(BMX_ERR_ARG, "bmx_cluster_begin_batch has not been called");
-        ClusterBatch& b = *batches_.back();
-        if (m < 1 || b.filled + m > b.n) throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
-        if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
         const double t0 = now_ms();
-        double* p = b.x.p + b.filled * G_;
-        upload_pageable(p, x_block, (size_t)m * G_ * sizeof(double), stream_);
-        if (b.cos_norm) {
-            if (sub0_host_.empty()) {
-                cosine_l2_device(stream_, p, G_, (int)m, b.l2.p + b.filled);
-            } else {
-                hipLaunchKernelGGL(colnorm_subset_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, (const double*)p,
-                                   G_, (int)m, (const int32_t*)sub0_.p, (int)sub0_host_.size(), b.l2.p + b.filled);
-                BMX_LAUNCH_CHECK();
+        add(x_block, m, [&](ClusterBatch& b, double* p) {
+            if (b.cos_norm) {
+                double* l2 = b.l2.p + (b.filled - m);
+                if (sub0_host_.empty()) {
+                    cosine_l2_device(stream_, p, G_, (int)m, l2);
+                } else {
+                    hipLaunchKernelGGL(colnorm_subset_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_,
+                                       (const double*)p, G_, (int)m, (const int32_t*)sub0_.p, (int)sub0_host_.size(), l2);
+                    BMX_LAUNCH_CHECK();
+                }
             }
-        }
-        b.filled += m;
-        if (b.filled == b.n) BMX_HIP(hipStreamSynchronize(stream_));
+            if (b.complete()) BMX_HIP(hipStreamSynchronize(stream_));
+        });
         ms_[0] += now_ms() - t0;
     }
 
@@ -450,7 +416,7 @@ class Cluster {
         const int G = G_;
         double* part = part_.reserve((size_t)b.nchunks * G);
         double* cen = cen_.reserve((size_t)b.C * G);
-        BMX_HIP(hipEventRecord(ev_[0], stream_));
+        const int e0 = timer_.mark(stream_);
         hipLaunchKernelGGL(centroid_partial_kernel, dim3((unsigned)b.nchunks, (unsigned)cdiv(G, 256)), dim3(256), 0, stream_,
                            (const double*)b.x.p, G, (const double*)(b.cos_norm ? b.l2.p : nullptr),
                            (const int32_t*)b.order.p, (const int32_t*)b.chunk_begin.p, part);
@@ -458,10 +424,11 @@ class Cluster {
         hipLaunchKernelGGL(centroid_reduce_kernel, dim3((unsigned)cdiv(G, 256), (unsigned)b.C), dim3(256), 0, stream_,
                            (const double*)part, G, b.C, (const int32_t*)b.cluster_chunk0.p, (const int32_t*)b.count.p, cen);
         BMX_LAUNCH_CHECK();
-        BMX_HIP(hipEventRecord(ev_[1], stream_));
+        const int e1 = timer_.mark(stream_);
         BMX_HIP(hipMemcpyAsync(out, cen, (size_t)b.C * G * sizeof(double), hipMemcpyDeviceToHost, stream_));
         BMX_HIP(hipStreamSynchronize(stream_));
-        add_span(1, 0, 1);
+        timer_.span(1, e0, e1);
+        timer_.collect(ms_);
     }
 
     void propagate(int bi, const double* rotation, int d, const double* centers, const double* cpcs, const double* corr,
@@ -502,51 +469,43 @@ class Cluster {
         double* W = w_.reserve((size_t)n * C);
         double* dist = dist_.reserve((size_t)n);
 
-        BMX_HIP(hipEventRecord(ev_[0], stream_));
+        const int e0 = timer_.mark(stream_);
         cosnorm_project_device(stream_, b.x.p, G, n, U, d, zero, 0, cur, nullptr, cu_scratch);
         const int64_t total = (int64_t)n * d;
         hipLaunchKernelGGL(finish_projection_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, cur, n, d,
                            (const double*)(b.cos_norm ? b.l2.p : nullptr), (const double*)cu_dev);
         BMX_LAUNCH_CHECK();
-        BMX_HIP(hipEventRecord(ev_[1], stream_));
+        const int e1 = timer_.mark(stream_);
         hipLaunchKernelGGL(nearest_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream_, (const double*)cur, n, d,
                            (const double*)cp_dev, C, W, dist);
         BMX_LAUNCH_CHECK();
         hipLaunchKernelGGL(median_select_kernel, dim3(1), dim3(MSEL_T), 0, stream_, (const double*)dist,
                            (const int32_t*)(b.n_rows ? b.rows.p : nullptr), b.n_rows ? b.n_rows : b.n, sigma_dev);
         BMX_LAUNCH_CHECK();
-        BMX_HIP(hipEventRecord(ev_[2], stream_));
+        const int e2 = timer_.mark(stream_);
         const size_t lds = (size_t)C * JT * sizeof(double);
         ensure_dynamic_lds(reinterpret_cast<const void*>(&smooth_kernel), lds);
         hipLaunchKernelGGL(smooth_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), lds, stream_, cur, n, d, W, C,
                            (const double*)cp_dev, (const double*)corr_dev, (const double*)sigma_dev);
         BMX_LAUNCH_CHECK();
-        BMX_HIP(hipEventRecord(ev_[3], stream_));
+        const int e3 = timer_.mark(stream_);
         double sigma = 0.0;
         BMX_HIP(hipMemcpyAsync(&sigma, sigma_dev, sizeof(double), hipMemcpyDeviceToHost, stream_));
         download_pageable(out, cur, (size_t)n * d * sizeof(double), stream_);
         BMX_HIP(hipStreamSynchronize(stream_));
         if (sigma_out) *sigma_out = sigma;
-        add_span(2, 0, 1);
-        add_span(3, 1, 2);
-        add_span(4, 2, 3);
+        timer_.span(2, e0, e1);
+        timer_.span(3, e1, e2);
+        timer_.span(4, e2, e3);
+        timer_.collect(ms_);
     }
 
     void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
 
   private:
-    void add_span(int stage, int a, int b) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, ev_[a], ev_[b]) == hipSuccess) ms_[stage] += (double)ms;
-        (void)hipGetLastError();
-    }
-    DevBlockCache cache_;  // first: outlives the buffers below
-    int device_, G_;
-    hipStream_t stream_ = nullptr;
-    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+    SpanTimer timer_;
     std::vector<int32_t> sub0_host_;
     DevBuf<int32_t> sub0_;
-    std::vector<std::unique_ptr<ClusterBatch>> batches_;
     DevBuf<double> part_, cen_, u_, small_, cur_, w_, dist_;
     double ms_[5] = {0, 0, 0, 0, 0};
 };

@@ -19,7 +19,6 @@
 //             residual_kernel x - coef[, drop] %*% t(D[, drop]), the dropped columns added in ascending order
 // All FP64 vector arithmetic, contraction off.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -28,6 +27,7 @@
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
 #include "linear_correct.hpp"
+#include "resident_batches.hpp"
 
 namespace bmx {
 namespace {
@@ -219,23 +219,13 @@ __global__ __launch_bounds__(256) void residual_kernel(const double* __restrict_
     }
 }
 
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 int mode_of(double log_base) { return log_base == 2.0 ? 1 : (log_base == 10.0 ? 2 : 3); }
 
 }  // namespace
 
 void linear_check_batch(int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
-    if (n < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
-    if (n > 0x7fffffffll) throw Error(BMX_ERR_ARG, "a batch holds at most 2^31 - 1 cells");
-    if (restrict_idx && n_restrict >= 0) {
-        if (n_restrict == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
-        if (n_restrict > 0x7fffffffll) throw Error(BMX_ERR_ARG, "'restrict' names at most 2^31 - 1 cells");
-        for (int64_t i = 0; i < n_restrict; ++i)
-            if (restrict_idx[i] < 1 || restrict_idx[i] > n) throw Error(BMX_ERR_ARG, "'restrict' indices out of range");
-    }
+    check_cell_count(n);
+    check_restriction(n, restrict_idx, n_restrict);
 }
 
 void linear_check_rescale(double log_base, double pseudo_count) {
@@ -256,37 +246,27 @@ void linear_check_regress(const double* design, int p, const double* w, const in
         if (keep[i] < 1 || keep[i] > p) throw Error(BMX_ERR_ARG, "'keep' indices out of range");
 }
 
-struct LinearBatch {
-    DevBuf<double> x;        // [n][G] (= genes x cells column-major)
+struct LinearBatch : ResidentBatch {
     DevBuf<double> u;        // [n][G] unlogged values, when they are kept
     DevBuf<double> part;     // [nchunks][G]
     DevBuf<int32_t> order;   // restricted cells (0-based) ascending, empty without restriction
     std::vector<int32_t> order_host;
-    int64_t n = 0, filled = 0, m = 0;  // m: restricted cells
+    int64_t m = 0;  // restricted cells
     int nchunks = 0, sum_done = 0;
     int sum_kind = 0;  // what part / the mean slot hold: 0 nothing, 1 plain, 2 unlogged
     double sum_base = 0.0, sum_pseudo = 0.0;
     bool has_u = false;
 };
 
-class Linear {
+class Linear : ResidentBatches<LinearBatch> {
   public:
-    Linear(int device, int G) : device_(device), G_(G) {
-        BMX_HIP(hipSetDevice(device_));
-        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    Linear(int device, int G) : ResidentBatches(device, G, "bmx_linear_begin_batch") {
         BMX_HIP(hipStreamCreateWithFlags(&kstream_, hipStreamNonBlocking));
         BMX_HIP(hipEventCreateWithFlags(&landed_, hipEventDisableTiming));
     }
     ~Linear() {
-        (void)hipSetDevice(device_);
-        for (hipStream_t s : {stream_, kstream_})
-            if (s) {
-                (void)hipStreamSynchronize(s);
-                (void)hipStreamDestroy(s);
-            }
+        retire({kstream_});
         if (landed_) (void)hipEventDestroy(landed_);
-        for (hipEvent_t e : events_) (void)hipEventDestroy(e);
-        DevBlockCache::current() = &cache_;  // the members' blocks go back to this handle's cache, which frees them
     }
 
     void expect(int kind, double log_base, double pseudo, int keep_unlogged) {
@@ -301,55 +281,42 @@ class Linear {
 
     void begin_batch(int64_t n, const int32_t* restrict_idx, int64_t nr) {
         linear_check_batch(n, restrict_idx, nr);
-        if (!batches_.empty() && batches_.back()->filled != batches_.back()->n)
-            throw Error(BMX_ERR_ARG, "the previous batch has not received all its cells");
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        auto nb = std::make_unique<LinearBatch>();
-        LinearBatch& b = *nb;
-        b.n = n;
-        const bool restricted = restrict_idx && nr >= 0;
-        if (restricted) {  // (a cell named twice counts twice, as R's subsetting would)
-            b.order_host.assign(restrict_idx, restrict_idx + nr);
-            for (int32_t& v : b.order_host) v -= 1;
-            std::sort(b.order_host.begin(), b.order_host.end());
-        }
-        b.m = restricted ? nr : n;
-        b.nchunks = cdiv(b.m, LCH);
-        b.x.reserve((size_t)n * G_);
-        b.part.reserve((size_t)b.nchunks * G_);
-        if (keep_u_ && !restricted) {
-            b.u.reserve((size_t)n * G_);
-            b.has_u = true;
-        }
-        if (restricted) {
-            BMX_HIP(hipMemcpyAsync(b.order.reserve(b.order_host.size()), b.order_host.data(),
-                                   b.order_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            BMX_HIP(hipStreamSynchronize(stream_));
-        }
-        batches_.push_back(std::move(nb));
+        begin(n, [&](LinearBatch& b) {
+            const bool restricted = is_restricted(restrict_idx, nr);
+            if (restricted) {  // (a cell named twice counts twice, as R's subsetting would)
+                b.order_host.assign(restrict_idx, restrict_idx + nr);
+                for (int32_t& v : b.order_host) v -= 1;
+                std::sort(b.order_host.begin(), b.order_host.end());
+            }
+            b.m = restricted ? nr : n;
+            b.nchunks = cdiv(b.m, LCH);
+            b.part.reserve((size_t)b.nchunks * G_);
+            if (keep_u_ && !restricted) {
+                b.u.reserve((size_t)n * G_);
+                b.has_u = true;
+            }
+            if (restricted) {
+                BMX_HIP(hipMemcpyAsync(b.order.reserve(b.order_host.size()), b.order_host.data(),
+                                       b.order_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+                BMX_HIP(hipStreamSynchronize(stream_));
+            }
+        });
     }
 
     void add_block(const double* x_block, int64_t m) {
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        if (batches_.empty()) throw Error(BMX_ERR_ARG, "bmx_linear_begin_batch has not been called");
-        LinearBatch& b = *batches_.back();
-        if (m < 1 || b.filled + m > b.n) throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
-        if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
         const double t0 = now_ms();
-        upload_pageable(b.x.p + b.filled * G_, x_block, (size_t)m * G_ * sizeof(double), stream_);
-        b.filled += m;
-        if (expect_kind_ != 0) {
-            BMX_HIP(hipEventRecord(landed_, stream_));
-            BMX_HIP(hipStreamWaitEvent(kstream_, landed_, 0));
-            launch_sums(b, expect_kind_, expect_base_, expect_pseudo_);
-        }
-        if (b.filled == b.n) {
-            BMX_HIP(hipStreamSynchronize(stream_));
-            BMX_HIP(hipStreamSynchronize(kstream_));
-            collect_spans();
-        }
+        add(x_block, m, [&](LinearBatch& b, double*) {
+            if (expect_kind_ != 0) {
+                BMX_HIP(hipEventRecord(landed_, stream_));
+                BMX_HIP(hipStreamWaitEvent(kstream_, landed_, 0));
+                launch_sums(b, expect_kind_, expect_base_, expect_pseudo_);
+            }
+            if (b.complete()) {
+                BMX_HIP(hipStreamSynchronize(stream_));
+                BMX_HIP(hipStreamSynchronize(kstream_));
+                timer_.collect(ms_);
+            }
+        });
         ms_[0] += now_ms() - t0;
     }
 
@@ -368,7 +335,7 @@ class Linear {
         hipLaunchKernelGGL(rescale_stats_kernel, dim3((unsigned)cdiv(G, 256)), dim3(256), 0, kstream_, (const double*)stats,
                            G, B, ref, scale);
         BMX_LAUNCH_CHECK();
-        spans_.push_back({2, ea, mark()});
+        timer_.span(2, ea, mark());
         const int mode = mode_of(log_base);
         const double lob = std::log(log_base);
         second_pass(outs, [&](int bi, const LinearBatch& b, int64_t c0, int mb, double* out) {
@@ -390,7 +357,7 @@ class Linear {
         });
         fetch_small(avg_out, stats, (size_t)B * G);
         fetch_small(ref_out, ref, (size_t)G);
-        collect_spans();
+        timer_.collect(ms_);
     }
 
     void regress(const double* design, int p, const double* w, const int32_t* keep, int n_keep, double* const* outs,
@@ -409,7 +376,7 @@ class Linear {
                                    out);
             });
             fetch_small(coef_out, mean, (size_t)B * G);
-            collect_spans();
+            timer_.collect(ms_);
             return;
         }
         // the weights and the dropped columns of the design, row-major and padded to whole tiles, on the host
@@ -465,7 +432,7 @@ class Linear {
         hipLaunchKernelGGL(coef_reduce_kernel, dim3((unsigned)cdiv(G, 256), (unsigned)p16), dim3(256), 0, kstream_,
                            (const double*)part, G, p16, (int)nch, coef);
         BMX_LAUNCH_CHECK();
-        spans_.push_back({1, ea, mark()});
+        timer_.span(1, ea, mark());
         std::vector<int64_t> cell0((size_t)B + 1, 0);
         for (int bi = 0; bi < B; ++bi) cell0[(size_t)bi + 1] = cell0[(size_t)bi] + batches_[(size_t)bi]->n;
         second_pass(outs, [&](int bi, const LinearBatch& b, int64_t c0, int mb, double* out) {
@@ -474,7 +441,7 @@ class Linear {
                                (const double*)(D + (size_t)(cell0[(size_t)bi] + c0) * pd16), pd16, out);
         });
         fetch_small(coef_out, coef, (size_t)p * G);
-        collect_spans();
+        timer_.collect(ms_);
     }
 
     void fetch(double* const* outs) {
@@ -493,29 +460,7 @@ class Linear {
     void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
 
   private:
-    struct Span {
-        int stage, a, b;
-    };
-    // a timing event recorded on the kernel stream now
-    int mark() {
-        if (next_event_ == (int)events_.size()) {
-            hipEvent_t e = nullptr;
-            BMX_HIP(hipEventCreate(&e));
-            events_.push_back(e);
-        }
-        BMX_HIP(hipEventRecord(events_[(size_t)next_event_], kstream_));
-        return next_event_++;
-    }
-    // (both streams are idle)
-    void collect_spans() {
-        for (const Span& s : spans_) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, events_[(size_t)s.a], events_[(size_t)s.b]) == hipSuccess) ms_[s.stage] += (double)ms;
-            (void)hipGetLastError();
-        }
-        spans_.clear();
-        next_event_ = 0;
-    }
+    int mark() { return timer_.mark(kstream_); }  // a timing event recorded on the kernel stream now
     void check_ready(double* const* outs) {
         if (batches_.empty()) throw Error(BMX_ERR_ARG, "no batch has been added");
         if (!outs) throw Error(BMX_ERR_ARG, "'outs' is missing");
@@ -563,7 +508,7 @@ class Linear {
         }
 #undef BMX_SUMS
         BMX_LAUNCH_CHECK();
-        spans_.push_back({1, ea, mark()});
+        timer_.span(1, ea, mark());
         b.sum_done = complete;
     }
 
@@ -577,7 +522,7 @@ class Linear {
             hipLaunchKernelGGL(mean_kernel, dim3((unsigned)cdiv(G, 256)), dim3(256), 0, kstream_, (const double*)b.part.p, G,
                                b.nchunks, (double)b.m, mean + bi * (size_t)G);
             BMX_LAUNCH_CHECK();
-            spans_.push_back({2, ea, mark()});
+            timer_.span(2, ea, mark());
         }
     }
 
@@ -608,13 +553,13 @@ class Linear {
             launch(k.bi, *batches_[(size_t)k.bi], k.c0, k.mb, buf[i & 1]);
             BMX_LAUNCH_CHECK();
             done[i] = mark();
-            spans_.push_back({3, ea, done[i]});
+            timer_.span(3, ea, done[i]);
         };
         queue(0);
         for (size_t i = 0; i < blocks.size(); ++i) {
             if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
             const Blk& k = blocks[i];
-            BMX_HIP(hipStreamWaitEvent(stream_, events_[(size_t)done[i]], 0));
+            BMX_HIP(hipStreamWaitEvent(stream_, timer_.event(done[i]), 0));
             download_pageable(outs[k.bi] + k.c0 * G, buf[i & 1], (size_t)k.mb * G * sizeof(double), stream_);
         }
         BMX_HIP(hipStreamSynchronize(kstream_));
@@ -622,21 +567,15 @@ class Linear {
         ms_[4] += now_ms() - t0;
     }
 
-    DevBlockCache cache_;  // first: outlives the buffers below
-    int device_, G_;
-    hipStream_t stream_ = nullptr, kstream_ = nullptr;  // copies; kernels
+    hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
     hipEvent_t landed_ = nullptr;
-    std::vector<hipEvent_t> events_;
-    int next_event_ = 0;
-    std::vector<Span> spans_;
-    std::vector<std::unique_ptr<LinearBatch>> batches_;
+    SpanTimer timer_;
     DevBuf<double> stats_, w_, d_, gpart_, out_[2];
     DevBuf<int32_t> drop_;
     int expect_kind_ = 0;
     double expect_base_ = 0.0, expect_pseudo_ = 0.0;
     bool keep_u_ = false;
     double ms_[5] = {0, 0, 0, 0, 0};
-
 };
 
 Linear* linear_create(int device, int G) { return new Linear(device, G); }

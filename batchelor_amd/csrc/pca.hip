@@ -26,6 +26,7 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
+#include "resident_batches.hpp"
 
 namespace bmx {
 namespace {
@@ -385,62 +386,34 @@ void jacobi_eigen(std::vector<double>& A, std::vector<double>& V, int n) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-struct PcaBatch {
-    DevBuf<double> x;    // [n][G]  (= genes x cells column-major)
+struct PcaBatch : ResidentBatch {
     DevBuf<double> inv;  // [n] 1 / max(1e-8, l2), empty without cosine normalisation
-    int64_t n = 0;       // cells announced by begin_batch
-    int64_t filled = 0;  // cells received so far
     double weight = 1.0;
     bool cos_norm = false;
 };
 
-class Pca {
+class Pca : ResidentBatches<PcaBatch> {
   public:
-    Pca(int device, int G) : device_(device), G_(G) {
-        BMX_HIP(hipSetDevice(device_));
-        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    }
-    ~Pca() {
-        (void)hipSetDevice(device_);
-        if (stream_) {
-            (void)hipStreamSynchronize(stream_);
-            (void)hipStreamDestroy(stream_);
-        }
-        DevBlockCache::current() = &cache_;
-    }
-    DevBlockCache* cache() { return &cache_; }
+    Pca(int device, int G) : ResidentBatches(device, G, "bmx_pca_begin_batch") {}
+    ~Pca() { retire(); }
 
     // a batch of n cells whose columns arrive in one or more blocks (add_block), in order
     void begin_batch(int64_t n, double weight, bool cos_norm) {
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        if (n < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
-        if (!batches_.empty() && batches_.back()->filled != batches_.back()->n)
-            throw Error(BMX_ERR_ARG, "the previous batch has not received all its cells");
-        batches_.emplace_back(new PcaBatch());
-        PcaBatch& b = *batches_.back();
-        b.n = n;
-        b.weight = weight;
-        b.cos_norm = cos_norm;
-        b.x.reserve((size_t)n * G_);
-        if (cos_norm) b.inv.reserve((size_t)n);
+        check_cell_count(n, false);
+        begin(n, [&](PcaBatch& b) {
+            b.weight = weight;
+            b.cos_norm = cos_norm;
+            if (cos_norm) b.inv.reserve((size_t)n);
+        });
         fitted_ = false;
     }
-    // the next m cells (columns) of the batch begun last: x_block is G x m column-major host memory (pageable is fine:
-    // it goes through the pinned staging ring, which has taken the block by the time this returns)
     void add_block(const double* x_block, int64_t m) {
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        if (batches_.empty()) throw Error(BMX_ERR_ARG, "bmx_pca_begin_batch has not been called");
-        PcaBatch& b = *batches_.back();
-        if (m < 1 || b.filled + m > b.n) throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
-        double* p = b.x.p + b.filled * G_;
-        upload_pageable(p, x_block, (size_t)m * G_ * sizeof(double), stream_);
-        if (b.cos_norm) {
-            hipLaunchKernelGGL(inv_l2_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, p, m, G_, b.inv.p + b.filled);
+        add(x_block, m, [&](PcaBatch& b, double* p) {
+            if (!b.cos_norm) return;
+            hipLaunchKernelGGL(inv_l2_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, p, m, G_,
+                               b.inv.p + (b.filled - m));
             BMX_LAUNCH_CHECK();
-        }
-        b.filled += m;
+        });
     }
     void add_batch(const double* x, int64_t n, double weight, bool cos_norm) {
         begin_batch(n, weight, cos_norm);
@@ -780,10 +753,7 @@ class Pca {
         }
     }
 
-    DevBlockCache cache_;
-    int device_ = 0, G_ = 0, d_ = 0, L_ = PL;
-    hipStream_t stream_ = nullptr;
-    std::vector<std::unique_ptr<PcaBatch>> batches_;
+    int d_ = 0, L_ = PL;
     DevBuf<double> mu_, q_, y_, xr_, yr_, w_, qt_, ut_, z_, zt_, part_, small_;
     bool fitted_ = false;
 };

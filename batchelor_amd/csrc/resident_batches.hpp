@@ -1,0 +1,166 @@
+// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear) have in common: the argument checks of a
+// batch, the bookkeeping of a batch that arrives in column blocks, the store that owns the cache, the copy stream and
+// the batches, and the event-pair stage timer.  The checks and the bookkeeping make no HIP call.
+#pragma once
+#include <chrono>
+#include <cstring>
+#include <initializer_list>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "bmx_common.hpp"
+#include "host_xfer.hpp"
+
+namespace bmx {
+
+inline double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// ---- argument checks, without a device (throw Error(BMX_ERR_ARG))
+// int32_cells: the handle indexes a batch's cells with 32-bit integers
+inline void check_cell_count(int64_t n, bool int32_cells = true) {
+    if (n < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
+    if (int32_cells && n > 0x7fffffffll) throw Error(BMX_ERR_ARG, "a batch holds at most 2^31 - 1 cells");
+}
+// a batch's restriction: 1-based cells of its n, in any order; a null list or n_restrict < 0 means all cells
+inline bool is_restricted(const int32_t* restrict_idx, int64_t n_restrict) { return restrict_idx && n_restrict >= 0; }
+inline void check_restriction(int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
+    if (!is_restricted(restrict_idx, n_restrict)) return;
+    if (n_restrict == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
+    if (n_restrict > 0x7fffffffll) throw Error(BMX_ERR_ARG, "'restrict' names at most 2^31 - 1 cells");
+    for (int64_t i = 0; i < n_restrict; ++i)
+        if (restrict_idx[i] < 1 || restrict_idx[i] > n) throw Error(BMX_ERR_ARG, "'restrict' indices out of range");
+}
+
+// ---- a batch announced with n cells whose columns arrive in blocks, in order
+struct BlockLedger {
+    int64_t n = 0;       // cells announced
+    int64_t filled = 0;  // cells received so far
+    bool complete() const { return filled == n; }
+};
+// `last`: the batch begun before, if any
+inline void check_begin(const BlockLedger* last) {
+    if (last && !last->complete()) throw Error(BMX_ERR_ARG, "the previous batch has not received all its cells");
+}
+// `open`: the batch begun last, if any; `begin_entry`: the entry point that begins one ("bmx_pca_begin_batch")
+inline void check_block(const BlockLedger* open, const void* x_block, int64_t m, const char* begin_entry) {
+    if (!open) throw Error(BMX_ERR_ARG, std::string(begin_entry) + " has not been called");
+    if (m < 1 || open->filled + m > open->n) throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
+    if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
+}
+
+// ---- the store.  Batch: a struct derived from ResidentBatch with the handle's own per-batch buffers.
+struct ResidentBatch : BlockLedger {
+    DevBuf<double> x;  // [n][G] (= genes x cells column-major)
+};
+
+template <class Batch>
+class ResidentBatches {
+  public:
+    ResidentBatches(int device, int G, const char* begin_entry) : device_(device), G_(G), begin_entry_(begin_entry) {
+        BMX_HIP(hipSetDevice(device_));
+        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    }
+    ResidentBatches(const ResidentBatches&) = delete;
+    ResidentBatches& operator=(const ResidentBatches&) = delete;
+
+  protected:
+    // Destruction.  A DevBuf hands its block to the cache DevBlockCache::current() names at that moment, so two things
+    // must hold for every DevBuf of the store, of its batches and of the derived handle: (1) current() names cache_
+    // before the first of them is released, and (2) cache_ is destroyed after the last.  (2): cache_ is the first member
+    // of this base, and a base's members go after everything the derived class declares.  (1): the derived class's
+    // destructor BODY -- which runs before any member is released -- calls retire(); this destructor alone would be
+    // too late for the derived members.  retire() also drains and destroys the copy stream, then `more` in order.
+    void retire(std::initializer_list<hipStream_t> more = {}) {
+        (void)hipSetDevice(device_);
+        if (stream_) {
+            (void)hipStreamSynchronize(stream_);
+            (void)hipStreamDestroy(stream_);
+            stream_ = nullptr;
+        }
+        for (hipStream_t s : more)
+            if (s) {
+                (void)hipStreamSynchronize(s);
+                (void)hipStreamDestroy(s);
+            }
+        DevBlockCache::current() = &cache_;  // the blocks go back to this handle's cache, which frees them
+    }
+    ~ResidentBatches() = default;
+
+    // A new batch of n cells (the caller has checked n: check_cell_count): x is reserved, then fill(batch) reserves and
+    // uploads what else the handle keeps for it; the batch joins the list when fill returns.
+    template <class F>
+    void begin(int64_t n, F&& fill) {
+        check_begin(batches_.empty() ? nullptr : batches_.back().get());
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        auto nb = std::make_unique<Batch>();
+        nb->n = n;
+        nb->x.reserve((size_t)n * G_);
+        fill(*nb);
+        batches_.push_back(std::move(nb));
+    }
+    // The next m cells (columns) of the batch begun last: x_block is G x m column-major host memory (pageable is fine: it
+    // goes through the pinned staging ring, which has taken the block by the time the copy is queued).  The copy is
+    // queued on the copy stream, then queued(batch, p) does the handle's work behind it: p is where the block lands,
+    // batch.filled already counts it.
+    template <class F>
+    void add(const double* x_block, int64_t m, F&& queued) {
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        Batch* b = batches_.empty() ? nullptr : batches_.back().get();
+        check_block(b, x_block, m, begin_entry_);
+        double* p = b->x.p + b->filled * G_;
+        upload_pageable(p, x_block, (size_t)m * G_ * sizeof(double), stream_);
+        b->filled += m;
+        queued(*b, p);
+    }
+
+    DevBlockCache cache_;  // first: see retire()
+    int device_, G_;
+    const char* begin_entry_;
+    hipStream_t stream_ = nullptr;  // copies (and, in Pca and Cluster, the kernels)
+    std::vector<std::unique_ptr<Batch>> batches_;
+};
+
+// ---- device time by stage, from pairs of events
+class SpanTimer {
+  public:
+    ~SpanTimer() {
+        for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+    }
+    // a timing event recorded on `stream` now
+    int mark(hipStream_t stream) {
+        if (next_ == (int)events_.size()) {
+            hipEvent_t e = nullptr;
+            BMX_HIP(hipEventCreate(&e));
+            events_.push_back(e);
+        }
+        BMX_HIP(hipEventRecord(events_[(size_t)next_], stream));
+        return next_++;
+    }
+    hipEvent_t event(int i) const { return events_[(size_t)i]; }
+    void span(int stage, int a, int b) { spans_.push_back({stage, a, b}); }
+    // the spans since the last call go into ms[stage] and the events are free again (the streams marked are idle)
+    void collect(double* ms) {
+        for (const Span& s : spans_) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, events_[(size_t)s.a], events_[(size_t)s.b]) == hipSuccess) ms[s.stage] += (double)t;
+            (void)hipGetLastError();
+        }
+        spans_.clear();
+        next_ = 0;
+    }
+
+  private:
+    struct Span {
+        int stage, a, b;
+    };
+    std::vector<hipEvent_t> events_;
+    int next_ = 0;
+    std::vector<Span> spans_;
+};
+
+}  // namespace bmx

@@ -7,8 +7,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .inputs import check_same_dim, divide_into_batches, reindex_pairings, unpack_batches
 from .multi_batch_pca import cosineNorm, multiBatchPCA, multiBatchPCA_host, project
-from .reduced_mnn import MnnResult, _fast_mnn, _reindex_pairings, divideIntoBatches
+from .reduced_mnn import MnnResult, fast_mnn_core
 
 
 @dataclass
@@ -40,19 +41,16 @@ def fastMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, cos_norm=Tru
     """fastMNN(..., batch=, k=, prop.k=, restrict=, cos.norm=, ndist=, d=, weights=, merge.order=, auto.merge=,
     min.batch.skip=) (R/fastMNN.R:283-331): several batches (`.fast_mnn_list`, :339-358) or ONE genes x cells object with
     `batch=` naming each cell's batch (`.fast_mnn_single`, :364-388)."""
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
+    batches = unpack_batches(batches)
     if len(batches) == 1:
         return _fast_mnn_single(np.asarray(batches[0], dtype=np.float64), batch, k, prop_k, restrict, cos_norm, ndist, d,
                                 weights, merge_order, auto_merge, min_batch_skip, device, pca, pca_tol, pca_maxit)
     if len(batches) < 2:
         raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
     mats = [np.asarray(b, dtype=np.float64) for b in batches]
-    G = mats[0].shape[0]
-    if any(m.ndim != 2 or m.shape[0] != G for m in mats):
-        raise ValueError("number of rows is not the same across batches")  # R/checkInputs.R:64-71
+    check_same_dim(mats, byrow=False)
     rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit)
-    out: MnnResult = _fast_mnn(pcs, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device)
+    out: MnnResult = fast_mnn_core(pcs, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device)
     return FastMnnResult(corrected=out.corrected, batch=out.batch, rotation=rec["rotation"], centers=rec["centers"],
                          merge_info=out.merge_info, stats=out.stats)
 
@@ -78,10 +76,10 @@ def _fast_mnn_single(x, batch, k, prop_k, restrict, cos_norm, ndist, d, weights,
     allpcs = np.empty((x.shape[1], pcs[0].shape[1]))
     for lev, pc in zip(levels, pcs):
         allpcs[batch == lev] = pc
-    div = divideIntoBatches(allpcs, batch, r)
-    out = _fast_mnn(div["batches"], k, prop_k, div["restricted"], ndist, merge_order, auto_merge, min_batch_skip,
-                    [str(lev) for lev in div["levels"]], device)
-    reo = div["reorder"]                                         # R/fastMNN.R:383-385
-    out.merge_info.pairs = _reindex_pairings(out.merge_info.pairs, reo)
+    div = divide_into_batches(allpcs, batch, r, byrow=True)
+    out = fast_mnn_core(div.parts, k, prop_k, div.restricted, ndist, merge_order, auto_merge, min_batch_skip,
+                    [str(lev) for lev in div.levels], device)
+    reo = div.reorder                                            # R/fastMNN.R:383-385
+    out.merge_info.pairs = reindex_pairings(out.merge_info.pairs, reo)
     return FastMnnResult(corrected=out.corrected[reo - 1], batch=out.batch[reo - 1], rotation=rec["rotation"],
                          centers=rec["centers"], merge_info=out.merge_info, stats=out.stats)

@@ -22,8 +22,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from .cluster_mnn import _as_index
-from .mnn_correct import _subset_index
+from ._handle import ResidentHandle
+from .inputs import check_same_dim, check_unique_names, divide_into_batches, restrict_list, subset_index, unpack_batches
 
 MAX_DESIGN_COLUMNS = 64   # BMX_LINEAR_MAX_DESIGN_COLUMNS
 BLOCK_BYTES = 1 << 28     # a batch above this size goes to the device in column blocks of about this many bytes
@@ -46,10 +46,8 @@ class LinearCorrectResult:
 
 
 def _as_matrices(batches, what):
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
     mats: List[np.ndarray] = []
-    for b in batches:
+    for b in unpack_batches(batches):
         mod = type(b).__module__ or ""
         if mod.startswith("scipy.sparse") or hasattr(b, "tocsr"):
             raise TypeError(f"{what} takes dense matrices: sparse inputs are not supported")
@@ -62,60 +60,28 @@ def _as_matrices(batches, what):
     return mats
 
 
-def _check_rows(mats):
-    G = mats[0].shape[0] if mats[0].ndim == 2 else -1
-    for m in mats:
-        if m.ndim != 2 or m.shape[0] != G:
-            raise ValueError("number of rows is not the same across batches")  # R/checkInputs.R:64
-    return G
-
-
 def _check_names(names, n):
     if names is None:
         return None
     names = [str(v) for v in names]
     if len(names) != n:
         raise ValueError("'names' must have one entry per batch")
-    if len(set(names)) != len(names):
-        raise ValueError("names of batches should be unique")  # R/rescaleBatches.R:140, R/regressBatches.R:117
+    check_unique_names(names)  # R/rescaleBatches.R:140, R/regressBatches.R:117
     return names
 
 
-def _restrictions(restrict, mats):
-    if restrict is None:
-        return [None] * len(mats)
-    if len(restrict) != len(mats):
-        raise ValueError("'restrictions' must of length equal to the number of batches")  # R/checkInputs.R:101
-    return [_as_index(r, m.shape[1]) for r, m in zip(restrict, mats)]
-
-
-def _divide_by_column(x, batch, restrict):
-    """divideIntoBatches(byrow=FALSE) (R/divideIntoBatches.R:36-84): levels are the sorted unique values of `batch`."""
+def _check_batch(batch, ncells):
     batch = np.asarray(batch)
-    if batch.ndim != 1 or batch.shape[0] != x.shape[1]:
+    if batch.ndim != 1 or batch.shape[0] != ncells:
         raise ValueError("'length(batch)' should be equal to number of cells in '...'")  # R/divideIntoBatches.R:97
-    levels = sorted(set(batch.tolist()))
-    mask = None
-    if restrict is not None:
-        mask = np.zeros(x.shape[1], dtype=bool)
-        mask[restrict - 1] = True
-    parts, rparts = [], []
-    reorder = np.zeros(x.shape[1], dtype=np.int64)
-    last = 0
-    for lv in levels:
-        keep = batch == lv
-        parts.append(x[:, keep])
-        if mask is None:
-            rparts.append(None)
-        else:
-            cr = np.flatnonzero(mask[keep]) + 1
-            if cr.size == 0:
-                raise ValueError("no cells remaining in a batch after restriction")  # R/divideIntoBatches.R:72
-            rparts.append(cr.astype(np.int32))
-        cnt = int(keep.sum())
-        reorder[keep] = last + np.arange(1, cnt + 1)
-        last += cnt
-    return parts, rparts, levels, reorder
+    return batch
+
+
+def _divide(x, batch, restrict):
+    """One object split by column: the parts, their restrictions, each divided cell's level, the way back."""
+    div = divide_into_batches(x, batch, restrict)
+    labels = np.repeat(np.asarray(div.levels), [m.shape[1] for m in div.parts])
+    return div.parts, div.restricted or [None] * len(div.parts), labels, div.reorder
 
 
 def _labels(names, ncells):
@@ -123,28 +89,10 @@ def _labels(names, ncells):
     return np.repeat(lab, ncells)
 
 
-class _LinearHandle:
+class _LinearHandle(ResidentHandle):
     """bmx_linear_t: the batches stay in HBM between the statistics and the pass that writes the result."""
-
-    def __init__(self, n_genes, device):
-        L = _lib.lib()
-        L.bmx_linear_destroy.argtypes = [ctypes.c_void_p]
-        L.bmx_linear_destroy.restype = None
-        self._h = ctypes.c_void_p()
-        self.G = int(n_genes)
-        self.ncells: List[int] = []
-        _lib.check(L.bmx_linear_create(ctypes.c_int32(int(device)), ctypes.c_int32(self.G), ctypes.byref(self._h)))
-
-    def close(self):
-        if self._h:
-            _lib.lib().bmx_linear_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX = "bmx_linear"
+    STAGES = STAGES
 
     def expect(self, kind, log_base=2.0, pseudo_count=1.0, keep_unlogged=False):
         _lib.check(_lib.lib().bmx_linear_expect(self._h, ctypes.c_int32(int(kind)), ctypes.c_double(float(log_base)),
@@ -152,18 +100,10 @@ class _LinearHandle:
                                                 ctypes.c_int32(int(bool(keep_unlogged)))))
 
     def add_batch(self, x, restrict, block_bytes=None):
-        """x: genes x cells.  Above block_bytes the batch goes over in column blocks, converted to column-major one
-        block at a time (the whole matrix never exists twice on the host)."""
-        L = _lib.lib()
-        n = int(x.shape[1])
-        rp = None if restrict is None else _lib.i32p(restrict)
-        rn = ctypes.c_int64(-1 if restrict is None else int(restrict.size))
-        block = max(1, int(BLOCK_BYTES if block_bytes is None else block_bytes) // (8 * self.G))
-        _lib.check(L.bmx_linear_begin_batch(self._h, ctypes.c_int64(n), rp, rn))
-        for a in range(0, n, block):
-            xb = _lib.as_f(x[:, a:a + block])
-            _lib.check(L.bmx_linear_add_block(self._h, _lib.f64p(xb), ctypes.c_int64(xb.shape[1])))
-        self.ncells.append(n)
+        """x: genes x cells; see ResidentHandle._upload for block_bytes (None: the module's BLOCK_BYTES)."""
+        self._upload(x, BLOCK_BYTES if block_bytes is None else block_bytes,
+                     None if restrict is None else _lib.i32p(restrict),
+                     ctypes.c_int64(-1 if restrict is None else int(restrict.size)))
 
     def _outs(self):
         out = np.empty((self.G, sum(self.ncells)), dtype=np.float64, order="F")
@@ -205,11 +145,6 @@ class _LinearHandle:
         _lib.check(_lib.lib().bmx_linear_fetch(self._h, ptrs))
         return out
 
-    def stage_ms(self):
-        st = np.zeros(5, dtype=np.float64)
-        _lib.check(_lib.lib().bmx_linear_stage_ms(self._h, _lib.f64p(st)))
-        return dict(zip(STAGES, st.tolist()))
-
 
 def _rows(mats, sub):
     return mats if sub is None else [m[sub - 1] for m in mats]
@@ -225,14 +160,13 @@ def rescaleBatches(*batches, batch=None, restrict=None, log_base=2, pseudo_count
     mats = _as_matrices(batches, "rescaleBatches")
     if len(mats) == 0:
         raise ValueError("at least two batches must be specified")  # R/rescaleBatches.R:107
-    G = _check_rows(mats)
-    res = _restrictions(restrict, mats)
+    G = check_same_dim(mats, byrow=False)
+    res = restrict_list(restrict, [m.shape[1] for m in mats]) or [None] * len(mats)
     reorder = None
     if len(mats) == 1:
         if batch is None:
             raise ValueError("'batch' must be specified if '...' has only one object")  # R/divideIntoBatches.R:88
-        mats, res, levels, reorder = _divide_by_column(mats[0], batch, res[0])
-        labels = np.repeat(np.asarray(levels), [m.shape[1] for m in mats])
+        mats, res, labels, reorder = _divide(mats[0], _check_batch(batch, mats[0].shape[1]), res[0])
     else:
         names = _check_names(names, len(mats))
         labels = _labels(names, [m.shape[1] for m in mats])
@@ -243,7 +177,7 @@ def rescaleBatches(*batches, batch=None, restrict=None, log_base=2, pseudo_count
         raise ValueError("'log_base' must be positive, finite and not 1")
     if not np.isfinite(pseudo_count):
         raise ValueError("'pseudo_count' must be finite")
-    sub = None if correct_all else _subset_index(subset_row, G)  # R/rescaleBatches.R:82-84
+    sub = None if correct_all else subset_index(subset_row, G)  # R/rescaleBatches.R:82-84
     if sub is not None and sub.size == 0:
         raise ValueError("'subset_row' selects no genes")
     mats = _rows(mats, sub)
@@ -290,9 +224,9 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
     mats = _as_matrices(batches, "regressBatches")
     if len(mats) == 0:
         raise ValueError("at least two batches must be specified")  # R/regressBatches.R:133
-    G = _check_rows(mats)
-    res = _restrictions(restrict, mats)
+    G = check_same_dim(mats, byrow=False)
     ncells = [m.shape[1] for m in mats]
+    res = restrict_list(restrict, ncells) or [None] * len(mats)
     total = sum(ncells)
     reorder = None
     if len(mats) > 1:
@@ -304,9 +238,7 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
                 raise ValueError("'batch' must be specified if '...' has only one object")  # R/divideIntoBatches.R:88
             labels = np.ones(total, dtype=np.int64)  # :124-128
         else:
-            labels = np.asarray(batch)
-            if labels.ndim != 1 or labels.shape[0] != total:
-                raise ValueError("'length(batch)' should be equal to number of cells in '...'")
+            labels = _check_batch(batch, total)
     if design is not None:
         design = np.asarray(design, dtype=np.float64)
         if design.ndim != 2 or design.shape[0] != total:
@@ -328,15 +260,14 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
             if keep.size and (keep.min() < 1 or keep.max() > p):
                 raise ValueError("'keep' indices out of range")
             keep = np.unique(keep).astype(np.int32)
-    sub = None if correct_all else _subset_index(subset_row, G)  # R/regressBatches.R:136-139
+    sub = None if correct_all else subset_index(subset_row, G)  # R/regressBatches.R:136-139
     if sub is not None and sub.size == 0:
         raise ValueError("'subset_row' selects no genes")
     if d is not None and int(d) < 1:
         raise ValueError("'d' must be positive")
 
     if design is None and len(mats) == 1:
-        mats, res, levels, reorder = _divide_by_column(mats[0], labels, res[0])
-        labels_out = np.repeat(np.asarray(levels), [m.shape[1] for m in mats])
+        mats, res, labels_out, reorder = _divide(mats[0], labels, res[0])
     else:
         labels_out = labels
     w = None
@@ -365,7 +296,7 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
         labels_out = labels_out[reorder - 1]
     result = LinearCorrectResult(corrected=out, batch=labels_out, coefficients=coef, stats={"stage_ms": stage_ms})
     if d is not None:
-        result.pcs = _residual_pcs(out, labels_out, int(d), _subset_index(subset_row, G) if correct_all else None, device)
+        result.pcs = _residual_pcs(out, labels_out, int(d), subset_index(subset_row, G) if correct_all else None, device)
     return result
 
 

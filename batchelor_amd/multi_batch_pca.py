@@ -14,6 +14,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._handle import ResidentHandle
+from .inputs import check_same_dim, unpack_batches
 
 
 def cosineNorm(x, mode="matrix"):
@@ -63,44 +65,38 @@ def _weight_vector(ncells, weights):
     return w
 
 
-class DevicePCA:
+class DevicePCA(ResidentHandle):
     """bmx_pca_t: the batches (genes x cells) stay in HBM; fit() = multiBatchPCA (R/multiBatchPCA.R:211-322) by
     Chebyshev-filtered subspace iteration on the FP64 matrix cores, run until the Ritz residual is below `tol`;
     project(b) = crossprod(cosineNorm(x_b) - centers, rotation)."""
+    PREFIX = "bmx_pca"
 
     def __init__(self, n_genes, device=0):
         _lib.require_gpu()
-        self._h = ctypes.c_void_p()
-        lib = _lib.lib()
-        lib.bmx_pca_destroy.argtypes = [ctypes.c_void_p]
-        lib.bmx_pca_destroy.restype = None
-        _lib.check(lib.bmx_pca_create(int(device), int(n_genes), ctypes.byref(self._h)))
-        self.G = int(n_genes)
-        self.ncells = []
+        super().__init__(n_genes, device)
         self.d = 0
         self.iters_used = 0
         self.residual = float("nan")
 
-    def add_batch(self, x, weight=1.0, cos_norm=False):
-        x = _lib.as_f(x)
+    def _check_rows(self, x):
         if x.ndim != 2 or x.shape[0] != self.G:
             raise ValueError("number of rows is not the same across batches")
-        _lib.check(_lib.lib().bmx_pca_add_batch(self._h, _lib.f64p(x), ctypes.c_int64(x.shape[1]),
-                                                ctypes.c_double(float(weight)), 1 if cos_norm else 0))
-        self.ncells.append(int(x.shape[1]))
+
+    def add_batch(self, x, weight=1.0, cos_norm=False):
+        x = _lib.as_f(x)
+        self._check_rows(x)
+        self._upload(x, None, ctypes.c_double(float(weight)), 1 if cos_norm else 0)
 
     def begin_batch(self, n, weight=1.0, cos_norm=False):
         """Announce a batch of n cells whose columns follow in blocks (add_block), so that it never has to exist on the
         host in one piece."""
-        _lib.check(_lib.lib().bmx_pca_begin_batch(self._h, ctypes.c_int64(int(n)), ctypes.c_double(float(weight)),
-                                                  1 if cos_norm else 0))
+        self._call("begin_batch", ctypes.c_int64(int(n)), ctypes.c_double(float(weight)), 1 if cos_norm else 0)
         self.ncells.append(int(n))
 
     def add_block(self, x_block):
         x_block = _lib.as_f(x_block)
-        if x_block.ndim != 2 or x_block.shape[0] != self.G:
-            raise ValueError("number of rows is not the same across batches")
-        _lib.check(_lib.lib().bmx_pca_add_block(self._h, _lib.f64p(x_block), ctypes.c_int64(x_block.shape[1])))
+        self._check_rows(x_block)
+        self._call("add_block", _lib.f64p(x_block), ctypes.c_int64(x_block.shape[1]))
 
     def fit(self, d=50, tol=1e-9, max_iters=500, iters=None):
         """tol: relative Ritz residual at which the iteration stops (raises if max_iters applications of the operator do
@@ -128,17 +124,6 @@ class DevicePCA:
         _lib.check(_lib.lib().bmx_pca_project(self._h, int(b), _lib.f64p(out)))
         return np.ascontiguousarray(out)
 
-    def close(self):
-        if self._h:
-            _lib.lib().bmx_pca_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_iters=500, iters=None, device=0,
                   return_pcs=True, l2=None, block=65536):
@@ -152,13 +137,10 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
     iteration cannot take -- fewer genes or cells than its block of 64 / 128 vectors, d > 120, data of rank below the
     block -- go to multiBatchPCA_host (north_star keeps multiBatchPCA on the host path anyway), as does a call in
     round 1's form with per-cell norms `l2=` (and its `block=`)."""
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
+    batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
-    G = np.asarray(batches[0]).shape[0]
-    if any(np.asarray(m).ndim != 2 or np.asarray(m).shape[0] != G for m in batches):
-        raise ValueError("number of rows is not the same across batches")
+    G = check_same_dim(batches, byrow=False)
     ncells = [np.asarray(m).shape[1] for m in batches]
     w = _weight_vector(ncells, weights)
     width = 64 if d <= 56 else 128
@@ -204,14 +186,11 @@ def multiBatchPCA_host(*batches, d=50, weights=None, l2=None, block=65536):
 
     Returns {"rotation": [G x d], "centers": [G], "d": singular values, "weights": w}.  Project with `project()`.
     """
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
+    batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
     mats = [np.asarray(b, dtype=np.float64) for b in batches]
-    G = mats[0].shape[0]
-    if any(m.ndim != 2 or m.shape[0] != G for m in mats):
-        raise ValueError("number of rows is not the same across batches")
+    G = check_same_dim(mats, byrow=False)
     w = _weight_vector([m.shape[1] for m in mats], weights)
     inv = [None if l2 is None else 1.0 / np.maximum(1e-8, np.asarray(l2[i], dtype=np.float64)) for i in range(len(mats))]
 

@@ -15,6 +15,7 @@ from typing import Any, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import inputs
 from .merge_tree import encode_postorder, resolve_merge_order
 
 
@@ -44,6 +45,19 @@ class MnnResult:
     batch: np.ndarray         # batch id (1-based) or name per row
     merge_info: MergeInfo
     stats: Optional[list] = None   # per merge {nL, nR, U, P, nL_all, nR_all}: sizes behind the flop / byte counts
+
+
+def _pack_batches(batches, restrict):
+    """The batches (cells x d) and their restrictions as bmx_engine_upload / bmx_fast_mnn take them:
+    (keepalive, B, d, void* data [B], int32 nrows [B], void* restrict [B] or None, int32 n_restrict [B])."""
+    mats = [_lib.as_f(b) for b in batches]
+    if len(mats) < 2:
+        raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
+    d = inputs.check_same_dim(mats, byrow=True)
+    B = len(mats)
+    nrows = np.asarray([m.shape[0] for m in mats], dtype=np.int32)
+    rkeep, rptr, rn = inputs.pack_restrictions(inputs.restrict_list(restrict, nrows.tolist()), B)
+    return (mats, rkeep), B, d, (ctypes.c_void_p * B)(*[m.ctypes.data for m in mats]), nrows, rptr, rn
 
 
 class MnnEngine:
@@ -84,35 +98,9 @@ class MnnEngine:
         _lib.check(_lib.lib().bmx_engine_set_shard(self._h, int(rank), int(world), self._cb, None))
 
     def upload(self, batches: Sequence[np.ndarray], restrict=None):
-        mats = [_lib.as_f(b) for b in batches]
-        if len(mats) < 2:
-            raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
-        d = mats[0].shape[1]
-        for m in mats:
-            if m.ndim != 2 or m.shape[1] != d:
-                raise ValueError("number of columns is not the same across batches")  # R/checkInputs.R:64-71
-        B = len(mats)
-        data = (ctypes.c_void_p * B)(*[m.ctypes.data for m in mats])
-        nrows = np.asarray([m.shape[0] for m in mats], dtype=np.int32)
-        rlist, rptr, rn = [], (ctypes.c_void_p * B)(), np.full(B, -1, dtype=np.int32)
-        if restrict is not None:
-            if len(restrict) != B:
-                raise ValueError("'restrictions' must of length equal to the number of batches")
-            for b, r in enumerate(restrict):
-                if r is None:
-                    rlist.append(None)
-                    continue
-                r = np.asarray(r)
-                r = (np.flatnonzero(r) + 1) if r.dtype == bool else r
-                r = np.ascontiguousarray(r, dtype=np.int32)
-                if r.size == 0:
-                    raise ValueError("no cells remaining in a batch after restriction")
-                rlist.append(r)
-                rptr[b] = r.ctypes.data
-                rn[b] = r.size
-        _lib.check(_lib.lib().bmx_engine_upload(self._h, B, d, data, _lib.i32p(nrows),
-                                                rptr if restrict is not None else None, _lib.i32p(rn)))
-        self._keep = (mats, rlist)
+        keep, B, d, data, nrows, rptr, rn = _pack_batches(batches, restrict)
+        _lib.check(_lib.lib().bmx_engine_upload(self._h, B, d, data, _lib.i32p(nrows), rptr, _lib.i32p(rn)))
+        self._keep = keep
         self.nbatches, self.nrows, self.d = B, nrows.tolist(), d
 
     def run(self, k=20, prop_k=None, ndist=3.0, min_batch_skip=0.0, merge_tree=None, auto_merge=False, var_adj=False,
@@ -263,31 +251,7 @@ def fast_mnn_one_shot(batches, restrict=None, k=20, prop_k=None, ndist=3.0, min_
     column-major), host results out; the library pulls the batches through its pinned staging ring while the first
     merges already run.  `merge_tree`: binary tree with 1-based integer leaves (None: 1..B progressive)."""
     _lib.require_gpu()
-    mats = [_lib.as_f(b) for b in batches]
-    if len(mats) < 2:
-        raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
-    d = mats[0].shape[1]
-    for m in mats:
-        if m.ndim != 2 or m.shape[1] != d:
-            raise ValueError("number of columns is not the same across batches")  # R/checkInputs.R:64-71
-    B = len(mats)
-    data = (ctypes.c_void_p * B)(*[m.ctypes.data for m in mats])
-    nrows = np.asarray([m.shape[0] for m in mats], dtype=np.int32)
-    rlist, rptr, rn = [], (ctypes.c_void_p * B)(), np.full(B, -1, dtype=np.int32)
-    if restrict is not None:
-        if len(restrict) != B:
-            raise ValueError("'restrictions' must of length equal to the number of batches")
-        for b, r in enumerate(restrict):
-            if r is None:
-                continue
-            r = np.asarray(r)
-            r = (np.flatnonzero(r) + 1) if r.dtype == bool else r
-            r = np.ascontiguousarray(r, dtype=np.int32)
-            if r.size == 0:
-                raise ValueError("no cells remaining in a batch after restriction")
-            rlist.append(r)
-            rptr[b] = r.ctypes.data
-            rn[b] = r.size
+    keep, B, d, data, nrows, rptr, rn = _pack_batches(batches, restrict)
     p = BmxParams(ctypes.sizeof(BmxParams), int(k), float("nan") if prop_k is None else float(prop_k), float(ndist),
                   float("nan") if min_batch_skip is None else float(min_batch_skip), 1 if auto_merge else 0,
                   1 if var_adj else 0, float(sigma))
@@ -301,9 +265,9 @@ def fast_mnn_one_shot(batches, restrict=None, k=20, prop_k=None, ndist=3.0, min_
     sk = np.zeros(nm, dtype=np.int32)
     lv = np.zeros((nm, B), dtype=np.float64, order="F")
     eng = MnnEngine.__new__(MnnEngine)
-    eng._h, eng._keep, eng._cb = ctypes.c_void_p(), (mats, rlist), None
+    eng._h, eng._keep, eng._cb = ctypes.c_void_p(), keep, None
     eng.nbatches, eng.nrows, eng.d = B, nrows.tolist(), d
-    _lib.check(_lib.lib().bmx_fast_mnn(B, d, data, _lib.i32p(nrows), rptr if restrict is not None else None, _lib.i32p(rn),
+    _lib.check(_lib.lib().bmx_fast_mnn(B, d, data, _lib.i32p(nrows), rptr, _lib.i32p(rn),
                                        ctypes.byref(p), _lib.i32p(code), int(code.size), _lib.f64p(corrected),
                                        _lib.i32p(batch), _lib.i32p(ml), _lib.i32p(mr), _lib.f64p(bs), _lib.i32p(sk),
                                        _lib.f64p(lv), ctypes.byref(eng._h)))
@@ -318,89 +282,48 @@ def fast_mnn_one_shot(batches, restrict=None, k=20, prop_k=None, ndist=3.0, min_
                      stats=stats)
 
 
-def _fast_mnn(batches, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device=0,
+def fast_mnn_core(batches, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device=0,
               var_adj=False, sigma=0.1):
     """.fast_mnn (R/fastMNN.R:398-429)."""
-    if names is not None and len(set(names)) != len(names):
-        raise ValueError("names of batches should be unique")  # R/fastMNN.R:422
+    inputs.check_unique_names(names)  # R/fastMNN.R:422
+    restrict = inputs.restrict_list(restrict, [np.asarray(b).shape[0] for b in batches])  # R/fastMNN.R:405
     # the one call the .Call shim makes (bmx_fast_mnn: upload hidden behind the first merges), on the device asked for
     _lib.require_gpu()
     _lib.check(_lib.lib().bmx_set_device(int(device)))
     tree = None if auto_merge else resolve_merge_order(len(batches), merge_order, names)
     out = fast_mnn_one_shot(batches, restrict, k=k, prop_k=prop_k, ndist=ndist, min_batch_skip=min_batch_skip,
                             merge_tree=tree, auto_merge=auto_merge, var_adj=var_adj, sigma=sigma)
-    if names is not None:  # R/fastMNN.R:419-427
-        nm = np.asarray(list(names), dtype=object)
-        out.batch = nm[out.batch - 1]
-        out.merge_info.left = [[names[i - 1] for i in s] for s in out.merge_info.left]
-        out.merge_info.right = [[names[i - 1] for i in s] for s in out.merge_info.right]
-    return out
+    return inputs.apply_names(out, names)  # R/fastMNN.R:419-427
 
 
 def divideIntoBatches(x, batch, restrict=None):
-    """R/divideIntoBatches.R:36-84 with byrow=TRUE: levels are the sorted unique values of `batch`."""
-    x = np.asarray(x, dtype=np.float64)
-    batch = np.asarray(batch)
-    if batch.shape[0] != x.shape[0]:
-        raise ValueError("'length(batch)' and 'nrow(x)' are not the same")
-    levels = sorted(set(batch.tolist()))
-    mask = None
-    if restrict is not None:
-        r = np.asarray(restrict)
-        mask = np.zeros(x.shape[0], dtype=bool)
-        if r.dtype == bool:
-            mask[:] = r
-        else:
-            mask[r.astype(np.int64) - 1] = True
-    out, restricted = [], ([] if mask is not None else None)
-    reorder = np.zeros(x.shape[0], dtype=np.int64)
-    last = 0
-    for lev in levels:
-        keep = batch == lev
-        cur = x[keep]
-        if mask is not None:
-            cr = np.flatnonzero(mask[keep]) + 1
-            if cr.size == 0:
-                raise ValueError("no cells remaining in a batch after restriction")
-            restricted.append(cr.astype(np.int32))
-        out.append(cur)
-        reorder[keep] = last + np.arange(1, cur.shape[0] + 1)
-        last += cur.shape[0]
-    return {"batches": out, "levels": levels, "reorder": reorder, "restricted": restricted}
+    """R/divideIntoBatches.R:36-84 with byrow=TRUE (inputs.divide_into_batches), as a dict."""
+    div = inputs.divide_into_batches(np.asarray(x, dtype=np.float64), batch, restrict, byrow=True)
+    return {"batches": div.parts, "levels": div.levels, "reorder": div.reorder, "restricted": div.restricted}
 
 
-def _reindex_pairings(pairings, new_order):
-    """R/utils_reorder.R:23-36."""
-    new_order = np.asarray(new_order, dtype=np.int64)
-    rev = np.zeros(new_order.size + 1, dtype=np.int64)
-    rev[new_order] = np.arange(1, new_order.size + 1)
-    return [(rev[l], rev[r]) for l, r in pairings]
+_reindex_pairings = inputs.reindex_pairings
 
 
 def reducedMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, ndist=3, merge_order=None, auto_merge=False,
                min_batch_skip=0.0, names=None, device=0, var_adj=False, sigma=0.1) -> MnnResult:
     """reducedMNN(..., batch=, k=, prop.k=, restrict=, ndist=, merge.order=, auto.merge=, min.batch.skip=)
     (R/reducedMNN.R:61-95).  `names` plays the role of the argument names of `...`."""
-    if len(batches) == 1 and isinstance(batches[0], (list, tuple)):
-        batches = tuple(batches[0])
+    batches = inputs.unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least two batches must be specified")
-    d = np.asarray(batches[0]).shape[1]
-    for b in batches:
-        if np.asarray(b).ndim != 2 or np.asarray(b).shape[1] != d:
-            raise ValueError("number of columns is not the same across batches")
-    if restrict is not None and len(restrict) != len(batches):
-        raise ValueError("'restrictions' must of length equal to the number of batches")
+    inputs.check_same_dim(batches, byrow=True)
+    inputs.check_restrict_length(restrict, len(batches))
     if len(batches) == 1:
         if batch is None:
             raise ValueError("'batch' must be specified if '...' has only one object")  # R/checkInputs.R:128
         div = divideIntoBatches(batches[0], batch, None if restrict is None else restrict[0])
-        out = _fast_mnn(div["batches"], k, prop_k, div["restricted"], ndist, merge_order, auto_merge, min_batch_skip,
+        out = fast_mnn_core(div["batches"], k, prop_k, div["restricted"], ndist, merge_order, auto_merge, min_batch_skip,
                         [str(l) for l in div["levels"]], device, var_adj, sigma)
         reo = div["reorder"]
         out.corrected = out.corrected[reo - 1]
         out.batch = out.batch[reo - 1]
         out.merge_info.pairs = _reindex_pairings(out.merge_info.pairs, reo)
         return out
-    return _fast_mnn([np.asarray(b, dtype=np.float64) for b in batches], k, prop_k, restrict, ndist, merge_order,
+    return fast_mnn_core([np.asarray(b, dtype=np.float64) for b in batches], k, prop_k, restrict, ndist, merge_order,
                      auto_merge, min_batch_skip, names, device, var_adj, sigma)
