@@ -16,6 +16,7 @@
 #include "bmx_common.hpp"
 #include "bmx_ops.hpp"
 #include "cluster_mnn.hpp"
+#include "delta_variance.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
 #include "linear_correct.hpp"
@@ -235,6 +236,8 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
         } else if (n == "asv_ticks_literal" || n == "asv_ticks_chains" || n == "asv_literal_addends" || n == "asv_chain_tiles") {
             bmx::asv_ticks_read(t);
             *value = (int64_t)t[n == "asv_ticks_literal" ? 4 : (n == "asv_ticks_chains" ? 5 : (n == "asv_literal_addends" ? 6 : 7))];
+        } else if (n == "delta_gene_tile" || n == "delta_pair_chunk") {
+            *value = n == "delta_gene_tile" ? bmx::DELTA_GENE_TILE : bmx::DELTA_PAIR_CHUNK;
         } else if (n == "asv_tally_reset") {
             bmx::asv_tally_read(t, true);
             *value = 0;
@@ -942,6 +945,61 @@ int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5) {
     return guarded([&] {
         if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
         bmx::linear_stage_ms(h->impl, out5);
+    });
+}
+
+/* ---------------------------------------------------------------- mnnDeltaVariance ------------------------------ */
+struct bmx_delta {
+    bmx::Delta* impl = nullptr;
+    ~bmx_delta() { bmx::delta_destroy(impl); }
+};
+
+int32_t bmx_delta_create(int32_t device, int32_t G, bmx_delta_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "mnnDeltaVariance needs at least one gene");
+        auto h = std::make_unique<bmx_delta>();
+        h->impl = bmx::delta_create(device, G);
+        *out = h.release();
+    });
+}
+
+void bmx_delta_destroy(bmx_delta_t* h) { delete h; }
+
+int32_t bmx_delta_begin_batch(bmx_delta_t* h, int64_t n) {
+    return guarded([&] {
+        bmx::delta_begin_batch(impl_of(h), n);
+    });
+}
+
+int32_t bmx_delta_add_block(bmx_delta_t* h, const double* x_block, int64_t n_block) {
+    return guarded([&] {
+        bmx::delta_add_block(impl_of(h), x_block, n_block);
+    });
+}
+
+int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_genes0, int32_t n_norm_genes, int32_t nsteps,
+                      const int32_t* const* left, const int32_t* const* right, const int64_t* npairs, double* mean,
+                      double* total) {
+    return guarded([&] {
+        bmx::DeltaRun a;
+        a.cos_norm = cos_norm;
+        a.norm_genes0 = norm_genes0;
+        a.n_norm_genes = n_norm_genes;
+        a.nsteps = nsteps;
+        a.left = left;
+        a.right = right;
+        a.npairs = npairs;
+        a.mean = mean;
+        a.total = total;
+        bmx::delta_run(impl_of(h), a);  // (delta_check_run comes before any device work)
+    });
+}
+
+int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5) {
+    return guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        bmx::delta_stage_ms(h->impl, out5);
     });
 }
 

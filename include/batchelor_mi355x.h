@@ -116,7 +116,9 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * neighbouring quantile), "asv_tally_reset" (zeroes them and the ticks); 100 MHz device ticks of the tiled form added up over its
  * workgroups: "asv_ticks_stream", "asv_ticks_wait", "asv_ticks_cells" (the stream, the testing hook's round barrier, the per-cell
  * phase), "asv_ticks_literal" / "asv_ticks_chains" (the re-run cells' selection + re-evaluation + sort, their chains and walks),
- * "asv_literal_addends" (addends the re-run cells kept), "asv_chain_tiles" (tiles with a re-run cell).  Waits for the device. */
+ * "asv_literal_addends" (addends the re-run cells kept), "asv_chain_tiles" (tiles with a re-run cell).  Waits for the device.
+ * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
+ * owns, pairs of a step it walks). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
  * call went -- 0 the histogram quantile (a well-conditioned cell), 1 re-run in the reference's order of operations, 2
@@ -462,6 +464,36 @@ int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs);
  * time of out[1] the first pass (chunk sums / the product with w), out[2] the statistics kernels, out[3] the second pass's
  * kernels; out[4] = host wall time of the second pass with its downloads. */
 int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * mnnDeltaVariance() (R/mnnDeltaVariance.R:95-201): per gene and merge step, the mean of the MNN-paired cells and the
+ * variance of their deltas.  The batches (genes x cells, column-major) are uploaded once, whole or in column blocks
+ * through the pinned staging ring, and stay in HBM; a batch that does not fit in free HBM fails with a message that
+ * names subset_row (the caller uploads the rows it wants, n_genes of them; streaming by gene block is not offered).
+ * The trend fit and the combination over steps stay with the caller.  Every sum has one fixed order and no
+ * floating-point atomics are used: the same input gives the same bits on every run.  Every argument is checked before
+ * any device work.  The kernels' gene-tile width and pair-chunk length are bmx_dev_get "delta_gene_tile" /
+ * "delta_pair_chunk" (no device needed).
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_delta bmx_delta_t;
+int32_t bmx_delta_create(int32_t device, int32_t n_genes, bmx_delta_t** out);
+void bmx_delta_destroy(bmx_delta_t* h);
+/* A batch of n cells; its cells follow in one or more blocks (x_block: n_genes x n_block column-major, host), in order. */
+int32_t bmx_delta_begin_batch(bmx_delta_t* h, int64_t n);
+int32_t bmx_delta_add_block(bmx_delta_t* h, const double* x_block, int64_t n_block);
+/* One call for all merge steps.  cos_norm != 0 (:121-126): every cell of every batch is divided by
+ * pmax(1e-8, l2 / ml2), l2 its norm over norm_genes0 (0-based genes, n_norm_genes of them; NULL / 0: all genes), ml2 the
+ * mean over the batches of each batch's mean l2.  left[s] / right[s]: the npairs[s] pairs of step s as 1-based columns
+ * of the batches side by side in upload order (what merge_info.pairs holds).  mean and total are [n_genes x nsteps]
+ * column-major: mean = (rowMeans(left) + rowMeans(right)) / 2, total = the sample variance of left - right, taken as
+ * rowVars takes it (the mean first, then the centred squares); NaN where a step has fewer than two pairs (mean: none). */
+int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_genes0, int32_t n_norm_genes, int32_t nsteps,
+                      const int32_t* const* left, const int32_t* const* right, const int64_t* npairs, double* mean,
+                      double* total);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), HIP-event
+ * time of out[1] the cell norms, out[2] the two pair passes (the gather), out[3] the pair preparation and the reductions
+ * over chunks; out[4] = host wall time of bmx_delta_run. */
+int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5);
 
 #ifdef __cplusplus
 }
