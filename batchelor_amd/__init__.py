@@ -13,3 +13,4 @@ from .mnn_correct import mnnCorrect  # noqa: F401
 from .cluster_mnn import ClusterMnnResult, clusterMNN  # noqa: F401
 from .linear_correct import LinearCorrectResult, regressBatches, rescaleBatches  # noqa: F401
 from .delta_variance import MnnDeltaVarianceResult, mnnDeltaVariance  # noqa: F401
+from .multi_batch_norm import MultiBatchNormResult, multiBatchNorm  # noqa: F401

@@ -21,6 +21,7 @@
 #include "host_xfer.hpp"
 #include "linear_correct.hpp"
 #include "mnn_correct.hpp"
+#include "multi_batch_norm.hpp"
 #include "rccl_dyn.hpp"
 
 struct bmx_engine {
@@ -945,6 +946,67 @@ int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5) {
     return guarded([&] {
         if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
         bmx::linear_stage_ms(h->impl, out5);
+    });
+}
+
+/* ---------------------------------------------------------------- multiBatchNorm -------------------------------- */
+struct bmx_norm {
+    bmx::Norm* impl = nullptr;
+    ~bmx_norm() { bmx::norm_destroy(impl); }
+};
+
+int32_t bmx_norm_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat, bmx_norm_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        auto h = std::make_unique<bmx_norm>();
+        h->impl = bmx::norm_create(device, G, stat_rows, n_stat);
+        *out = h.release();
+    });
+}
+
+void bmx_norm_destroy(bmx_norm_t* h) { delete h; }
+
+int32_t bmx_norm_check_create(int32_t G, const int32_t* stat_rows, int64_t n_stat) {
+    return guarded([&] {
+        bmx::norm_check_create(G, stat_rows, n_stat);
+    });
+}
+
+int32_t bmx_norm_check_batch(int64_t n, const double* size_factors) {
+    return guarded([&] {
+        bmx::norm_check_batch(n, size_factors);
+    });
+}
+
+int32_t bmx_norm_check_run(double min_mean, int32_t log, double pseudo_count) {
+    return guarded([&] {
+        bmx::norm_check_run(min_mean, log, pseudo_count);
+    });
+}
+
+int32_t bmx_norm_begin_batch(bmx_norm_t* h, int64_t n, const double* size_factors) {
+    return guarded([&] {
+        bmx::norm_begin_batch(impl_of(h), n, size_factors);
+    });
+}
+
+int32_t bmx_norm_add_block(bmx_norm_t* h, const double* x_block, int64_t n_block) {
+    return guarded([&] {
+        bmx::norm_add_block(impl_of(h), x_block, n_block);
+    });
+}
+
+int32_t bmx_norm_run(bmx_norm_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs, double* sf_out,
+                     double* ave_out, double* ratios_out, int32_t* smallest_out) {
+    return guarded([&] {
+        bmx::norm_run(impl_of(h), min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out);
+    });
+}
+
+int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5) {
+    return guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        bmx::norm_stage_ms(h->impl, out5);
     });
 }
 

@@ -536,34 +536,7 @@ class Linear : ResidentBatches<LinearBatch> {
         // (the second grid dimension holds at most 65 535 workgroups of CPW cells)
         const int64_t per = std::min<int64_t>(
             65535 * (int64_t)CPW, std::max<int64_t>(1, (int64_t)(OUT_BLOCK_BYTES / (sizeof(double) * (size_t)G))));
-        struct Blk {
-            int bi;
-            int64_t c0;
-            int mb;
-        };
-        std::vector<Blk> blocks;
-        for (size_t bi = 0; bi < batches_.size(); ++bi)
-            for (int64_t c0 = 0; c0 < batches_[bi]->n; c0 += per)
-                blocks.push_back({(int)bi, c0, (int)std::min(per, batches_[bi]->n - c0)});
-        double* buf[2] = {out_[0].reserve((size_t)per * G), out_[1].reserve((size_t)per * G)};
-        std::vector<int> done(blocks.size(), -1);
-        auto queue = [&](size_t i) {
-            const Blk& k = blocks[i];
-            const int ea = mark();
-            launch(k.bi, *batches_[(size_t)k.bi], k.c0, k.mb, buf[i & 1]);
-            BMX_LAUNCH_CHECK();
-            done[i] = mark();
-            timer_.span(3, ea, done[i]);
-        };
-        queue(0);
-        for (size_t i = 0; i < blocks.size(); ++i) {
-            if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
-            const Blk& k = blocks[i];
-            BMX_HIP(hipStreamWaitEvent(stream_, timer_.event(done[i]), 0));
-            download_pageable(outs[k.bi] + k.c0 * G, buf[i & 1], (size_t)k.mb * G * sizeof(double), stream_);
-        }
-        BMX_HIP(hipStreamSynchronize(kstream_));
-        BMX_HIP(hipStreamSynchronize(stream_));
+        blocked_output(batches_, G, per, kstream_, stream_, timer_, 3, out_, outs, launch);
         ms_[4] += now_ms() - t0;
     }
 

@@ -1,7 +1,9 @@
-// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear) have in common: the argument checks of a
-// batch, the bookkeeping of a batch that arrives in column blocks, the store that owns the cache, the copy stream and
-// the batches, and the event-pair stage timer.  The checks and the bookkeeping make no HIP call.
+// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear, Norm) have in common: the argument checks
+// of a batch, the bookkeeping of a batch that arrives in column blocks, the store that owns the cache, the copy stream and
+// the batches, the event-pair stage timer and the blocked pass that writes every cell.  The checks and the bookkeeping
+// make no HIP call.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <initializer_list>
@@ -162,5 +164,43 @@ class SpanTimer {
     int next_ = 0;
     std::vector<Span> spans_;
 };
+
+// ---- a pass that writes every cell of every batch (Linear, Norm), in blocks of at most `per` cells through the two
+// device buffers of `buf`: launch(bi, batch, first cell, cells, device out) queues the kernel of a block on `kstream`;
+// the block then goes to outs[bi] through the download ring on `copy` while the next block's kernel runs into the other
+// buffer.  The kernels' event time goes to the timer's `stage`.  Both streams are idle when this returns.
+template <class Batch, class F>
+void blocked_output(const std::vector<std::unique_ptr<Batch>>& batches, int G, int64_t per, hipStream_t kstream,
+                    hipStream_t copy, SpanTimer& timer, int stage, DevBuf<double> (&buf)[2], double* const* outs,
+                    F&& launch) {
+    struct Blk {
+        int bi;
+        int64_t c0;
+        int mb;
+    };
+    std::vector<Blk> blocks;
+    for (size_t bi = 0; bi < batches.size(); ++bi)
+        for (int64_t c0 = 0; c0 < batches[bi]->n; c0 += per)
+            blocks.push_back({(int)bi, c0, (int)std::min(per, batches[bi]->n - c0)});
+    double* dev[2] = {buf[0].reserve((size_t)per * G), buf[1].reserve((size_t)per * G)};
+    std::vector<int> done(blocks.size(), -1);
+    auto queue = [&](size_t i) {
+        const Blk& k = blocks[i];
+        const int ea = timer.mark(kstream);
+        launch(k.bi, *batches[(size_t)k.bi], k.c0, k.mb, dev[i & 1]);
+        BMX_LAUNCH_CHECK();
+        done[i] = timer.mark(kstream);
+        timer.span(stage, ea, done[i]);
+    };
+    queue(0);
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
+        const Blk& k = blocks[i];
+        BMX_HIP(hipStreamWaitEvent(copy, timer.event(done[i]), 0));
+        download_pageable(outs[k.bi] + k.c0 * G, dev[i & 1], (size_t)k.mb * G * sizeof(double), copy);
+    }
+    BMX_HIP(hipStreamSynchronize(kstream));
+    BMX_HIP(hipStreamSynchronize(copy));
+}
 
 }  // namespace bmx

@@ -466,6 +466,51 @@ int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs);
 int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * multiBatchNorm() (R/multiBatchNorm.R:100-280): size factors rescaled between batches, then log-normalized values.
+ * The batches (genes x cells counts, FP64, column-major, finite and >= 0) are uploaded once, whole or in column blocks
+ * through the pinned staging ring, and stay in HBM.  With S the statistic rows:
+ *   size factors  sf = given / mean(given), or lib / mean(lib) with lib[c] = sum over S of x[g, c]; every one must be
+ *                 finite and > 0 ("size factors should be positive")
+ *   averages      ave[g] = (1 / n) * sum over c of x[g, c] / sf[c], g in S
+ *   ratios        for every pair first < second, over the genes with
+ *                 (ave_f / sum(ave_f) + ave_s / sum(ave_s)) / 2 * (sum(ave_f) + sum(ave_s)) / 2 >= min_mean:
+ *                 ratios[first][second] = median(ave_s / ave_f), ratios[second][first] = median(ave_f / ave_s) (the middle
+ *                 order statistic, or the mean of the two middle ones; 0 / x = 0 and x / 0 = inf are ordered with the
+ *                 rest); no kept gene, a NaN ratio or a median that is 0 or not finite is an error ("median ratio of
+ *                 averages between batches is not finite").  The diagonal is 1; the reference batch is the first column
+ *                 whose minimum is the smallest; rescaling[b] = ratios[b][reference].
+ *   values        log2(x / (sf / rescaling[b]) + pseudo_count), or x / (sf / rescaling[b]), for every uploaded row.
+ * Library sizes and per-gene sums are taken in a fixed order over fixed chunks of cells without floating-point atomics:
+ * the same input gives the same bits on every run and for every blocking of the upload.  Arguments are checked before
+ * any device work; what only the data can show (a bad count, a cell without counts, a pair without a median) is raised
+ * as device flags and reported by bmx_norm_run when its kernels have finished.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_norm bmx_norm_t;
+/* stat_rows: 1-based rows of S in the order the averages are reported (a row named twice counts twice), n_stat of them;
+ * NULL / n_stat < 0: all rows.  (A caller that wants values for the rows of S only uploads just those rows.) */
+int32_t bmx_norm_create(int32_t device, int32_t n_genes, const int32_t* stat_rows, int64_t n_stat, bmx_norm_t** out);
+void bmx_norm_destroy(bmx_norm_t* h);
+/* The argument checks of bmx_norm_create / _begin_batch / _run on their own: they need no device. */
+int32_t bmx_norm_check_create(int32_t n_genes, const int32_t* stat_rows, int64_t n_stat);
+int32_t bmx_norm_check_batch(int64_t n, const double* size_factors);
+int32_t bmx_norm_check_run(double min_mean, int32_t log, double pseudo_count);
+/* A batch of n cells.  size_factors [n] (any scale, finite and > 0) or NULL for library sizes.  Its cells follow in one
+ * or more blocks (x_block: n_genes x n_block column-major, host), in order; the library sizes and per-gene sums of a
+ * block run behind the upload of the next. */
+int32_t bmx_norm_begin_batch(bmx_norm_t* h, int64_t n, const double* size_factors);
+int32_t bmx_norm_add_block(bmx_norm_t* h, const double* x_block, int64_t n_block);
+/* outs[b]: n_genes x n_b column-major (caller-allocated).  Nullable: sf_out [cells of all batches, upload order] the
+ * size factors the values were divided by (never re-centred); ave_out [n_stat x n_batches] column-major; ratios_out
+ * [n_batches x n_batches] ROW-major (ratios_out[i * n_batches + j] = ratios[i][j]); smallest_out the 1-based reference
+ * batch.  log: 1 for log2(. + pseudo_count), 0 for the normalized counts. */
+int32_t bmx_norm_run(bmx_norm_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs, double* sf_out,
+                     double* ave_out, double* ratios_out, int32_t* smallest_out);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), HIP-event
+ * time of out[1] the statistics passes (column sums, per-gene sums, size factors, averages), out[2] the ratio stage,
+ * out[3] the output kernels; out[4] = host wall time of the output pass with its downloads. */
+int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * mnnDeltaVariance() (R/mnnDeltaVariance.R:95-201): per gene and merge step, the mean of the MNN-paired cells and the
  * variance of their deltas.  The batches (genes x cells, column-major) are uploaded once, whole or in column blocks
  * through the pinned staging ring, and stay in HBM; a batch that does not fit in free HBM fails with a message that
