@@ -1010,6 +1010,58 @@ int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5) {
     });
 }
 
+struct bmx_norm_sparse {
+    bmx::NormSparse* impl = nullptr;
+    ~bmx_norm_sparse() { bmx::norm_sparse_destroy(impl); }
+};
+
+int32_t bmx_norm_sparse_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat,
+                               bmx_norm_sparse_t** out) {
+    return guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        auto h = std::make_unique<bmx_norm_sparse>();
+        h->impl = bmx::norm_sparse_create(device, G, stat_rows, n_stat);
+        *out = h.release();
+    });
+}
+
+void bmx_norm_sparse_destroy(bmx_norm_sparse_t* h) { delete h; }
+
+int32_t bmx_norm_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
+                                    const int32_t* indices, const double* data, int64_t nnz) {
+    return guarded([&] {
+        bmx::norm_check_sparse_block(n, filled, n_block, indptr, indices, data, nnz);
+    });
+}
+
+int32_t bmx_norm_sparse_begin_batch(bmx_norm_sparse_t* h, int64_t n, const double* size_factors, int64_t nnz) {
+    return guarded([&] {
+        bmx::norm_sparse_begin_batch(impl_of(h), n, size_factors, nnz);
+    });
+}
+
+int32_t bmx_norm_sparse_add_block(bmx_norm_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                  const double* data, int64_t nnz) {
+    return guarded([&] {
+        bmx::norm_sparse_add_block(impl_of(h), n_block, indptr, indices, data, nnz);
+    });
+}
+
+int32_t bmx_norm_sparse_run(bmx_norm_sparse_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs,
+                            double* sf_out, double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out) {
+    return guarded([&] {
+        bmx::norm_sparse_run(impl_of(h), min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out,
+                             zero_out);
+    });
+}
+
+int32_t bmx_norm_sparse_stage_ms(const bmx_norm_sparse_t* h, double* out5) {
+    return guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        bmx::norm_sparse_stage_ms(h->impl, out5);
+    });
+}
+
 /* ---------------------------------------------------------------- mnnDeltaVariance ------------------------------ */
 struct bmx_delta {
     bmx::Delta* impl = nullptr;

@@ -16,6 +16,20 @@
 //   output  norm_out_kernel  log2(x / sf_out + pseudo) (or x / sf_out), in blocks through two device buffers that
 //                            download behind the kernels (blocked_output)
 // No floating-point atomics, FP64 vector arithmetic, contraction off: the same input gives the same bits on every run.
+//
+// Sparse counts (NormSparse, bmx_norm_sparse_*): a batch stays in HBM as CSC -- indptr [n + 1] int64 absolute, indices
+// int32, data FP64 -- filled in column blocks through the same staging ring.  The reductions and the output pass have
+// sparse forms, everything between them is shared with the dense handle:
+//   sp_colsum_kernel        one wave a cell over its stored entries; also the flags for a bad count, a row outside
+//                           [0, G) and rows that do not ascend strictly within a column
+//   sp_gene_partial_kernel  one workgroup per (chunk, tile of GT genes), the tile's sums in the LDS: the chunk's columns
+//                           in ascending order, one addition per stored entry, a barrier between columns.  A gene's sum
+//                           has one accumulator and takes its terms in cell order, as gene_partial_kernel's does; the
+//                           terms left out are x / w = +0, which change no bit of a sum of non-negative terms.
+//   sp_out_kernel           one wave a column over the stored entries only; zero_image_kernel: what a zero becomes
+// Every entry position comes from an indptr the host has checked (norm_check_sparse_block); a row index is compared
+// with its bounds before it addresses anything, and an entry that fails is skipped.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -38,6 +52,9 @@ constexpr double DBL_LARGEST = 1.7976931348623157e308;
 // flags (device): a count that is negative or not finite, a size factor that is not positive, a pair without a finite
 // median ratio; [3]: the reference batch (0-based)
 enum { F_COUNT = 0, F_SF = 1, F_RATIO = 2, F_SMALLEST = 3, F_WORDS = 4 };
+// the sparse handle's further words: a row index outside [0, G), rows of a column that do not ascend strictly
+enum { F_ROW = 4, F_ORDER = 5, F_SPARSE_WORDS = 6 };
+constexpr int GT = 4096;  // genes per tile of the sparse per-gene sums (32 KiB of accumulators in the LDS)
 
 __device__ __forceinline__ int invalid_count(double v) { return !(v >= 0.0 && v <= DBL_LARGEST); }
 
@@ -347,6 +364,127 @@ __global__ __launch_bounds__(256) void norm_out_kernel(const double* __restrict_
     }
 }
 
+// ---- sparse counts: a batch as CSC, indptr [n + 1] absolute positions into idx / val.  indptr has been checked on the
+// host (non-decreasing, within the arrays), idx and val have not.
+
+// The library sizes of the cells [c0, c0 + m), one wave a cell: lane l adds the column's entries l, l + 64, ..., then
+// the lanes are added in a fixed order.  mult (nullable): every value times mult[row].  w null: the entries are checked
+// only.  An entry whose row is outside [0, G) raises F_ROW and is left out; a row that is not above the one stored
+// before it raises F_ORDER.
+__global__ __launch_bounds__(256) void sp_colsum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                        const double* __restrict__ val, int G, int64_t c0, int64_t m,
+                                                        const double* __restrict__ mult, double* __restrict__ w,
+                                                        int32_t* __restrict__ flags) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = c0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= c0 + m) return;  // (a whole wave leaves)
+    const int64_t kb = indptr[c], ke = indptr[c + 1];
+    double s = 0.0;
+    int bad = 0, bad_row = 0, bad_order = 0;
+    for (int64_t k = kb + lane; k < ke; k += 64) {
+        const int32_t r = idx[k];
+        double v = val[k];
+        bad |= invalid_count(v);
+        if (k > kb && idx[k - 1] >= r) bad_order = 1;
+        if (r < 0 || r >= G) {
+            bad_row = 1;
+            continue;
+        }
+        if (mult) v *= mult[r];
+        s += v;
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+    if (bad) flags[F_COUNT] = 1;
+    if (bad_row) flags[F_ROW] = 1;
+    if (bad_order) flags[F_ORDER] = 1;
+    if (lane == 0 && w) w[c] = s;
+}
+
+// the first position in [lo, hi) whose row is not below g (rows ascending; on rows in any order it still ends, somewhere
+// in [lo, hi])
+__device__ __forceinline__ int64_t first_row_at_least(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int g) {
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (idx[mid] < g) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// part[ch][g] = sum over the cells [ch * NCH, min(n, (ch + 1) * NCH)), in order, of x[g, cell] / w[cell] for the genes g
+// of tile blockIdx.y, all G rows (part is [nchunks][G]).  Thread t first finds the tile's entries in the chunk's column t;
+// then the columns are taken one after the other, the threads striding over a column's entries in the tile, with a
+// barrier before the next column.  Rows are unique within a canonical column, so no two threads meet at an accumulator
+// (on a column that is not canonical they may, F_ORDER has been raised for it, and the addresses stay inside the tile).
+__global__ __launch_bounds__(256) void sp_gene_partial_kernel(const int64_t* __restrict__ indptr,
+                                                              const int32_t* __restrict__ idx,
+                                                              const double* __restrict__ val, int G,
+                                                              const double* __restrict__ w, int64_t n, int ch0,
+                                                              double* __restrict__ part) {
+    __shared__ double acc[GT];
+    __shared__ int64_t lo[NCH], hi[NCH];
+    const int ch = ch0 + blockIdx.x;
+    const int g0 = blockIdx.y * GT, g1 = min(G, g0 + GT);
+    const int64_t b = (int64_t)ch * NCH;
+    const int ncol = (int)((b + NCH < n ? b + NCH : n) - b);
+    for (int i = threadIdx.x; i < g1 - g0; i += 256) acc[i] = 0.0;
+    if ((int)threadIdx.x < ncol) {
+        const int64_t kb = indptr[b + threadIdx.x], ke = indptr[b + threadIdx.x + 1];
+        const int64_t first = first_row_at_least(idx, kb, ke, g0);
+        lo[threadIdx.x] = first;
+        hi[threadIdx.x] = first_row_at_least(idx, first, ke, g1);
+    }
+    __syncthreads();
+    for (int j = 0; j < ncol; ++j) {
+        const double wj = w[b + j];
+        const int64_t ke = hi[j];
+        for (int64_t k = lo[j] + threadIdx.x; k < ke; k += 256) {
+            const int r = idx[k];
+            if (r >= g0 && r < g1) acc[r - g0] += val[k] / wj;
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < g1 - g0; i += 256) part[(int64_t)ch * G + g0 + i] = acc[i];
+}
+
+// ave[g] = (sum over the chunks, ascending, of part[chunk][rows[g]]) * scale[0], part [nchunks][G]: ave_kernel for sums
+// kept by row
+__global__ __launch_bounds__(256) void ave_rows_kernel(const double* __restrict__ part, int G,
+                                                       const int32_t* __restrict__ rows, int nS, int nchunks,
+                                                       const double* __restrict__ scale, double* __restrict__ ave) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= nS) return;
+    const int r = rows[g];
+    double s = part[r];
+    for (int ch = 1; ch < nchunks; ++ch) s += part[(int64_t)ch * G + r];
+    ave[g] = s * scale[0];
+}
+
+// out[k - k0] = log2(val[k] / sfo[c] + pseudo) (LOG) or val[k] / sfo[c] for the stored entries k of the cells c in
+// [c0, c0 + mb), k0 = indptr[c0]; one wave a cell
+template <bool LOG>
+__global__ __launch_bounds__(256) void sp_out_kernel(const int64_t* __restrict__ indptr, const double* __restrict__ val,
+                                                     int64_t c0, int mb, const double* __restrict__ sfo, double pseudo,
+                                                     double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = c0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= c0 + mb) return;
+    const int64_t k0 = indptr[c0], ke = indptr[c + 1];
+    const double so = sfo[c];
+    for (int64_t k = indptr[c] + lane; k < ke; k += 64) {
+        const double a = val[k] / so;
+        out[k - k0] = LOG ? log2(a + pseudo) : a;
+    }
+}
+
+// what norm_out_kernel makes of a count of zero (its quotient by any size factor is +0), by the same log2
+template <bool LOG>
+__global__ void zero_image_kernel(double pseudo, double* __restrict__ zero) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double a = 0.0 / 1.0;
+    zero[0] = LOG ? log2(a + pseudo) : a;
+}
+
 }  // namespace
 
 void norm_check_create(int G, const int32_t* stat_rows, int64_t n_stat) {
@@ -373,14 +511,122 @@ void norm_check_run(double min_mean, int log, double pseudo_count) {
     if (!std::isfinite(pseudo_count)) throw Error(BMX_ERR_ARG, "'pseudo_count' must be finite");
 }
 
-struct NormBatch : ResidentBatch {
+void norm_check_sparse_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
+                             const double* data, int64_t nnz) {
+    if (!indptr) throw Error(BMX_ERR_ARG, "the block's 'indptr' is missing");
+    if (nnz < 0) throw Error(BMX_ERR_ARG, "the block's number of stored entries is negative");
+    if (nnz > 0 && (!indices || !data)) throw Error(BMX_ERR_ARG, "the block's 'indices' or 'data' is missing");
+    if (n < 1 || filled < 0 || m < 1 || m > n || filled > n - m)
+        throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
+    if (indptr[0] != 0) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not start at 0");
+    for (int64_t i = 0; i < m; ++i)
+        if (indptr[i + 1] < indptr[i]) throw Error(BMX_ERR_ARG, "the block's 'indptr' decreases");
+    if (indptr[m] != nnz) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not end at its number of stored entries");
+}
+
+// what both handles keep for a batch beside its counts
+struct NormStats {
     DevBuf<double> w;     // [n] library sizes, or the size factors given
     DevBuf<double> sf;    // [n] w / mean(w)
     DevBuf<double> sfo;   // [n] sf / rescaling
-    DevBuf<double> part;  // [nchunks][nS]
+    DevBuf<double> part;  // [nchunks][nS] (sparse counts: [nchunks][G])
     bool given = false;
     int nchunks = 0, sum_done = 0;
 };
+struct NormBatch : ResidentBatch, NormStats {};
+
+namespace {
+
+struct StatPointers {
+    double *ave, *ratios, *rescaling;
+};
+
+// The stages between the reductions and the output pass, on kstream, for either handle: size factors and averages
+// (launch_ave(batch, scale, ave) queues a batch's averaging kernel), the ratios and the reference, the size factors the
+// values are divided by.  flags: the words from F_SF on are cleared first.
+template <class Batch, class F>
+StatPointers launch_stat_stages(const std::vector<std::unique_ptr<Batch>>& batches, int nS, double min_mean,
+                                DevBuf<double>& stats, int32_t* flags, hipStream_t kstream, SpanTimer& timer,
+                                F&& launch_ave) {
+    const int B = (int)batches.size();
+    const int64_t npairs = (int64_t)B * (B - 1) / 2;
+    if (npairs > 0x7fffffffll) throw Error(BMX_ERR_ARG, "too many batches");
+    double* ave = stats.reserve((size_t)B * nS + (size_t)B * B + 2 * (size_t)B);  // ave [B][nS], ratios [B][B],
+    double* ratios = ave + (size_t)B * nS;                                        // rescaling [B], scale [B]
+    double* rescaling = ratios + (size_t)B * B;
+    double* scale = rescaling + B;
+    BMX_HIP(hipMemsetAsync(flags + F_SF, 0, (F_WORDS - F_SF) * sizeof(int32_t), kstream));
+    BMX_HIP(hipMemsetAsync(ratios, 0, (size_t)B * B * sizeof(double), kstream));
+    int ea = timer.mark(kstream);
+    for (int bi = 0; bi < B; ++bi) {
+        Batch& b = *batches[(size_t)bi];
+        hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, kstream, (const double*)b.w.p, b.n, b.sf.p, scale + bi,
+                           flags);
+        BMX_LAUNCH_CHECK();
+        launch_ave(b, (const double*)(scale + bi), ave + (size_t)bi * nS);
+        BMX_LAUNCH_CHECK();
+    }
+    timer.span(1, ea, timer.mark(kstream));
+    ea = timer.mark(kstream);
+    if (npairs > 0) {
+        hipLaunchKernelGGL(ratio_kernel, dim3((unsigned)npairs), dim3(RT), 0, kstream, (const double*)ave, nS, B, min_mean,
+                           ratios, flags);
+        BMX_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(smallest_kernel, dim3(1), dim3(64), 0, kstream, ratios, B, rescaling, flags);
+    BMX_LAUNCH_CHECK();
+    for (int bi = 0; bi < B; ++bi) {
+        Batch& b = *batches[(size_t)bi];
+        hipLaunchKernelGGL(sfout_kernel, dim3((unsigned)cdiv(b.n, 256)), dim3(256), 0, kstream, (const double*)b.sf.p, b.n,
+                           (const double*)(rescaling + bi), b.sfo.p);
+        BMX_LAUNCH_CHECK();
+    }
+    timer.span(2, ea, timer.mark(kstream));
+    return {ave, ratios, rescaling};
+}
+
+// The small results and the first nflags flag words, behind everything else on kstream; waits for the stream.
+template <class Batch>
+void fetch_small_results(const std::vector<std::unique_ptr<Batch>>& batches, int nS, const StatPointers& st,
+                         const int32_t* flags_dev, int nflags, int32_t* flags, hipStream_t kstream, double* sf_out,
+                         double* ave_out, double* ratios_out) {
+    const size_t B = batches.size();
+    BMX_HIP(hipMemcpyAsync(flags, flags_dev, (size_t)nflags * sizeof(int32_t), hipMemcpyDeviceToHost, kstream));
+    if (ave_out) BMX_HIP(hipMemcpyAsync(ave_out, st.ave, B * nS * sizeof(double), hipMemcpyDeviceToHost, kstream));
+    if (ratios_out) BMX_HIP(hipMemcpyAsync(ratios_out, st.ratios, B * B * sizeof(double), hipMemcpyDeviceToHost, kstream));
+    if (sf_out) {
+        int64_t at = 0;
+        for (auto& b : batches) {
+            BMX_HIP(hipMemcpyAsync(sf_out + at, b->sfo.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, kstream));
+            at += b->n;
+        }
+    }
+    BMX_HIP(hipStreamSynchronize(kstream));
+}
+
+void throw_if_flagged(const int32_t* flags) {
+    if (flags[F_COUNT]) throw Error(BMX_ERR_ARG, "counts should be finite and non-negative");
+    if (flags[F_SF]) throw Error(BMX_ERR_ARG, "size factors should be positive");
+    if (flags[F_RATIO]) throw Error(BMX_ERR_ARG, "median ratio of averages between batches is not finite");
+}
+
+// The statistic rows of a handle on the device: 0-based rows, and how often every one of the G rows is named.
+void upload_stat_rows(const int32_t* stat_rows, int64_t n_stat, int G, DevBuf<int32_t>& rows_dev, DevBuf<double>& mult_dev,
+                      hipStream_t stream) {
+    std::vector<int32_t> rows(stat_rows, stat_rows + n_stat);
+    std::vector<double> mult((size_t)G, 0.0);
+    for (int32_t& r : rows) {
+        r -= 1;
+        mult[(size_t)r] += 1.0;
+    }
+    BMX_HIP(hipMemcpyAsync(rows_dev.reserve(rows.size()), rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                           stream));
+    BMX_HIP(hipMemcpyAsync(mult_dev.reserve(mult.size()), mult.data(), mult.size() * sizeof(double), hipMemcpyHostToDevice,
+                           stream));
+    BMX_HIP(hipStreamSynchronize(stream));
+}
+
+}  // namespace
 
 class Norm : ResidentBatches<NormBatch> {
   public:
@@ -391,17 +637,7 @@ class Norm : ResidentBatches<NormBatch> {
         nS_ = G;
         if (stat_rows && n_stat >= 0) {
             nS_ = (int)n_stat;
-            std::vector<int32_t> rows(stat_rows, stat_rows + n_stat);
-            std::vector<double> mult((size_t)G, 0.0);
-            for (int32_t& r : rows) {
-                r -= 1;
-                mult[(size_t)r] += 1.0;
-            }
-            BMX_HIP(hipMemcpyAsync(rows_.reserve(rows.size()), rows.data(), rows.size() * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, stream_));
-            BMX_HIP(hipMemcpyAsync(mult_.reserve(mult.size()), mult.data(), mult.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, stream_));
-            BMX_HIP(hipStreamSynchronize(stream_));
+            upload_stat_rows(stat_rows, n_stat, G, rows_, mult_, stream_);
             subset_ = true;
         }
         BMX_HIP(hipMemsetAsync(flags_.reserve(F_WORDS), 0, F_WORDS * sizeof(int32_t), stream_));
@@ -454,41 +690,12 @@ class Norm : ResidentBatches<NormBatch> {
         }
         CacheScope scope(&cache_);
         BMX_HIP(hipSetDevice(device_));
-        const int G = G_, nS = nS_, B = (int)batches_.size();
-        const int64_t npairs = (int64_t)B * (B - 1) / 2;
-        if (npairs > 0x7fffffffll) throw Error(BMX_ERR_ARG, "too many batches");
-        double* ave = stats_.reserve((size_t)B * nS + (size_t)B * B + 2 * (size_t)B);  // ave [B][nS], ratios [B][B],
-        double* ratios = ave + (size_t)B * nS;                                         // rescaling [B], scale [B]
-        double* rescaling = ratios + (size_t)B * B;
-        double* scale = rescaling + B;
-        BMX_HIP(hipMemsetAsync(flags_.p + F_SF, 0, (F_WORDS - F_SF) * sizeof(int32_t), kstream_));
-        BMX_HIP(hipMemsetAsync(ratios, 0, (size_t)B * B * sizeof(double), kstream_));
-        int ea = mark();
-        for (int bi = 0; bi < B; ++bi) {
-            NormBatch& b = *batches_[(size_t)bi];
-            hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, kstream_, (const double*)b.w.p, b.n, b.sf.p, scale + bi,
-                               flags_.p);
-            BMX_LAUNCH_CHECK();
-            hipLaunchKernelGGL(ave_kernel, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, kstream_, (const double*)b.part.p, nS,
-                               b.nchunks, (const double*)(scale + bi), ave + (size_t)bi * nS);
-            BMX_LAUNCH_CHECK();
-        }
-        timer_.span(1, ea, mark());
-        ea = mark();
-        if (npairs > 0) {
-            hipLaunchKernelGGL(ratio_kernel, dim3((unsigned)npairs), dim3(RT), 0, kstream_, (const double*)ave, nS, B, min_mean,
-                               ratios, flags_.p);
-            BMX_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(smallest_kernel, dim3(1), dim3(64), 0, kstream_, ratios, B, rescaling, flags_.p);
-        BMX_LAUNCH_CHECK();
-        for (int bi = 0; bi < B; ++bi) {
-            NormBatch& b = *batches_[(size_t)bi];
-            hipLaunchKernelGGL(sfout_kernel, dim3((unsigned)cdiv(b.n, 256)), dim3(256), 0, kstream_, (const double*)b.sf.p, b.n,
-                               (const double*)(rescaling + bi), b.sfo.p);
-            BMX_LAUNCH_CHECK();
-        }
-        timer_.span(2, ea, mark());
+        const int G = G_, nS = nS_;
+        const StatPointers st = launch_stat_stages(
+            batches_, nS, min_mean, stats_, flags_.p, kstream_, timer_, [&](NormBatch& b, const double* scale, double* ave) {
+                hipLaunchKernelGGL(ave_kernel, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, kstream_, (const double*)b.part.p,
+                                   nS, b.nchunks, scale, ave);
+            });
 
         const double t0 = now_ms();
         // (the second grid dimension holds at most 65 535 workgroups of CPW cells)
@@ -512,25 +719,11 @@ class Norm : ResidentBatches<NormBatch> {
                        });
         ms_[4] += now_ms() - t0;
 
-        // the small results and the flags, behind everything else
         int32_t flags[F_WORDS] = {0, 0, 0, 0};
-        BMX_HIP(hipMemcpyAsync(flags, flags_.p, sizeof(flags), hipMemcpyDeviceToHost, kstream_));
-        if (ave_out) BMX_HIP(hipMemcpyAsync(ave_out, ave, (size_t)B * nS * sizeof(double), hipMemcpyDeviceToHost, kstream_));
-        if (ratios_out)
-            BMX_HIP(hipMemcpyAsync(ratios_out, ratios, (size_t)B * B * sizeof(double), hipMemcpyDeviceToHost, kstream_));
-        if (sf_out) {
-            int64_t at = 0;
-            for (auto& b : batches_) {
-                BMX_HIP(hipMemcpyAsync(sf_out + at, b->sfo.p, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, kstream_));
-                at += b->n;
-            }
-        }
-        BMX_HIP(hipStreamSynchronize(kstream_));
+        fetch_small_results(batches_, nS, st, flags_.p, F_WORDS, flags, kstream_, sf_out, ave_out, ratios_out);
         timer_.collect(ms_);
         if (smallest_out) *smallest_out = flags[F_SMALLEST] + 1;
-        if (flags[F_COUNT]) throw Error(BMX_ERR_ARG, "counts should be finite and non-negative");
-        if (flags[F_SF]) throw Error(BMX_ERR_ARG, "size factors should be positive");
-        if (flags[F_RATIO]) throw Error(BMX_ERR_ARG, "median ratio of averages between batches is not finite");
+        throw_if_flagged(flags);
     }
 
     void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
@@ -582,6 +775,228 @@ class Norm : ResidentBatches<NormBatch> {
     double ms_[5] = {0, 0, 0, 0, 0};
 };
 
+// ---- sparse counts
+struct SparseNormBatch : BlockLedger, NormStats {
+    static constexpr bool dense_x = false;
+    DevBuf<int64_t> indptr;        // [n + 1] absolute positions
+    DevBuf<int32_t> indices;       // [nnz] 0-based rows
+    DevBuf<double> data;           // [nnz]
+    std::vector<int64_t> hindptr;  // indptr on the host: the output pass cuts its blocks by it
+    int64_t nnz = 0, nnz_filled = 0;
+};
+
+class NormSparse : ResidentBatches<SparseNormBatch> {
+  public:
+    NormSparse(int device, int G, const int32_t* stat_rows, int64_t n_stat)
+        : ResidentBatches(device, G, "bmx_norm_sparse_begin_batch") {
+        CacheScope scope(&cache_);
+        BMX_HIP(hipStreamCreateWithFlags(&kstream_, hipStreamNonBlocking));
+        BMX_HIP(hipEventCreateWithFlags(&landed_, hipEventDisableTiming));
+        nS_ = G;
+        if (stat_rows && n_stat >= 0) {
+            nS_ = (int)n_stat;
+            upload_stat_rows(stat_rows, n_stat, G, rows_, mult_, stream_);
+            subset_ = true;
+        }
+        BMX_HIP(hipMemsetAsync(flags_.reserve(F_SPARSE_WORDS), 0, F_SPARSE_WORDS * sizeof(int32_t), stream_));
+        zero_.reserve(1);
+        BMX_HIP(hipStreamSynchronize(stream_));
+    }
+    ~NormSparse() {
+        retire({kstream_});
+        if (landed_) (void)hipEventDestroy(landed_);
+    }
+
+    void begin_batch(int64_t n, const double* size_factors, int64_t nnz) {
+        norm_check_batch(n, size_factors);
+        if (nnz < 0) throw Error(BMX_ERR_ARG, "the batch's number of stored entries is negative");
+        begin(n, [&](SparseNormBatch& b) {
+            b.nnz = nnz;
+            b.indptr.reserve((size_t)n + 1);
+            b.indices.reserve((size_t)std::max<int64_t>(nnz, 1));
+            b.data.reserve((size_t)std::max<int64_t>(nnz, 1));
+            b.hindptr.assign((size_t)n + 1, 0);
+            b.nchunks = cdiv(n, NCH);
+            b.part.reserve((size_t)b.nchunks * G_);
+            b.w.reserve((size_t)n);
+            b.sf.reserve((size_t)n);
+            b.sfo.reserve((size_t)n);
+            b.given = size_factors != nullptr;
+            if (b.given) {
+                BMX_HIP(hipMemcpyAsync(b.w.p, size_factors, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream_));
+                BMX_HIP(hipStreamSynchronize(stream_));
+            }
+        });
+    }
+
+    // the next m cells of the batch begun last: indptr [m + 1] relative to the block, its nnz entries
+    void add_block(int64_t m, const int64_t* indptr, const int32_t* indices, const double* data, int64_t nnz) {
+        const double t0 = now_ms();
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        SparseNormBatch* bp = batches_.empty() ? nullptr : batches_.back().get();
+        check_block(bp, indptr, m, begin_entry_);
+        SparseNormBatch& b = *bp;
+        norm_check_sparse_block(b.n, b.filled, m, indptr, indices, data, nnz);
+        if (nnz > b.nnz - b.nnz_filled) throw Error(BMX_ERR_ARG, "the block holds more entries than the batch announced");
+        if (b.filled + m == b.n && b.nnz_filled + nnz != b.nnz)
+            throw Error(BMX_ERR_ARG, "the batch has received fewer entries than it announced");
+        int64_t* habs = b.hindptr.data() + b.filled;
+        for (int64_t i = 0; i <= m; ++i) habs[i] = b.nnz_filled + indptr[i];
+        upload_pageable(b.indptr.p + b.filled, habs, (size_t)(m + 1) * sizeof(int64_t), stream_);
+        upload_pageable(b.indices.p + b.nnz_filled, indices, (size_t)nnz * sizeof(int32_t), stream_);
+        upload_pageable(b.data.p + b.nnz_filled, data, (size_t)nnz * sizeof(double), stream_);
+        b.filled += m;
+        b.nnz_filled += nnz;
+        BMX_HIP(hipEventRecord(landed_, stream_));
+        BMX_HIP(hipStreamWaitEvent(kstream_, landed_, 0));
+        launch_sums(b, b.filled - m, m);
+        if (b.complete()) {
+            BMX_HIP(hipStreamSynchronize(stream_));
+            BMX_HIP(hipStreamSynchronize(kstream_));
+            timer_.collect(ms_);
+        }
+        ms_[0] += now_ms() - t0;
+    }
+
+    void run(double min_mean, int log, double pseudo, double* const* outs, double* sf_out, double* ave_out,
+             double* ratios_out, int32_t* smallest_out, double* zero_out) {
+        norm_check_run(min_mean, log, pseudo);
+        if (batches_.empty()) throw Error(BMX_ERR_ARG, "no batch has been added");
+        if (!outs) throw Error(BMX_ERR_ARG, "'outs' is missing");
+        for (size_t i = 0; i < batches_.size(); ++i) {
+            if (!batches_[i]->complete()) throw Error(BMX_ERR_ARG, "a batch has not received all its cells");
+            if (!outs[i] && batches_[i]->nnz > 0) throw Error(BMX_ERR_ARG, "an output array is missing");
+        }
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        const int G = G_, nS = nS_;
+        const StatPointers st = launch_stat_stages(
+            batches_, nS, min_mean, stats_, flags_.p, kstream_, timer_,
+            [&](SparseNormBatch& b, const double* scale, double* ave) {
+                if (subset_)
+                    hipLaunchKernelGGL(ave_rows_kernel, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, kstream_,
+                                       (const double*)b.part.p, G, (const int32_t*)rows_.p, nS, b.nchunks, scale, ave);
+                else
+                    hipLaunchKernelGGL(ave_kernel, dim3((unsigned)cdiv(nS, 256)), dim3(256), 0, kstream_,
+                                       (const double*)b.part.p, nS, b.nchunks, scale, ave);
+            });
+
+        const double t0 = now_ms();
+        if (log)
+            hipLaunchKernelGGL(zero_image_kernel<true>, dim3(1), dim3(64), 0, kstream_, pseudo, zero_.p);
+        else
+            hipLaunchKernelGGL(zero_image_kernel<false>, dim3(1), dim3(64), 0, kstream_, pseudo, zero_.p);
+        BMX_LAUNCH_CHECK();
+        blocked_output_sparse(log, pseudo, outs);
+        ms_[4] += now_ms() - t0;
+
+        int32_t flags[F_SPARSE_WORDS] = {0, 0, 0, 0, 0, 0};
+        double zero = 0.0;
+        BMX_HIP(hipMemcpyAsync(&zero, zero_.p, sizeof(double), hipMemcpyDeviceToHost, kstream_));
+        fetch_small_results(batches_, nS, st, flags_.p, F_SPARSE_WORDS, flags, kstream_, sf_out, ave_out, ratios_out);
+        timer_.collect(ms_);
+        if (smallest_out) *smallest_out = flags[F_SMALLEST] + 1;
+        if (zero_out) *zero_out = zero;
+        if (flags[F_ROW]) throw Error(BMX_ERR_ARG, "sparse counts: a row index is outside [0, number of genes)");
+        if (flags[F_ORDER])
+            throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
+        throw_if_flagged(flags);
+    }
+
+    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+
+  private:
+    int mark() { return timer_.mark(kstream_); }
+
+    // on the kernel stream: the library sizes of the cells [c0, c0 + m) of b, which have just been queued for upload, then
+    // the chunks of b that are complete with the cells resident so far and not summed yet (Norm::launch_sums)
+    void launch_sums(SparseNormBatch& b, int64_t c0, int64_t m) {
+        const int ea = mark();
+        hipLaunchKernelGGL(sp_colsum_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
+                           (const int32_t*)b.indices.p, (const double*)b.data.p, G_, c0, m,
+                           (const double*)(subset_ ? mult_.p : nullptr), b.given ? nullptr : b.w.p, flags_.p);
+        BMX_LAUNCH_CHECK();
+        const int complete = b.complete() ? b.nchunks : (int)(b.filled / NCH);
+        for (int ch = b.sum_done; ch < complete; ch += 65535) {  // (a grid dimension holds at most 65 535 workgroups)
+            const unsigned nch = (unsigned)std::min(65535, complete - ch);
+            hipLaunchKernelGGL(sp_gene_partial_kernel, dim3(nch, (unsigned)cdiv(G_, GT)), dim3(256), 0, kstream_,
+                               (const int64_t*)b.indptr.p, (const int32_t*)b.indices.p, (const double*)b.data.p, G_,
+                               (const double*)b.w.p, b.n, ch, b.part.p);
+            BMX_LAUNCH_CHECK();
+        }
+        b.sum_done = std::max(b.sum_done, complete);
+        timer_.span(1, ea, mark());
+    }
+
+    // blocked_output over the stored entries: a block is a run of whole cells of a batch with at most OUT_BLOCK_BYTES of
+    // entries (one cell if that cell alone has more); its values go to outs[batch] at the position of its first entry
+    // through the download ring while the next block's kernel writes the other buffer.
+    void blocked_output_sparse(int log, double pseudo, double* const* outs) {
+        struct Blk {
+            int bi;
+            int64_t c0;
+            int mb;
+        };
+        const int64_t cap = (int64_t)(OUT_BLOCK_BYTES / sizeof(double));
+        std::vector<Blk> blocks;
+        int64_t largest = 1;
+        for (size_t bi = 0; bi < batches_.size(); ++bi) {
+            const std::vector<int64_t>& hp = batches_[bi]->hindptr;
+            const int64_t n = batches_[bi]->n;
+            for (int64_t c0 = 0; c0 < n;) {
+                // the last c1 <= c0 + 2^30 with hp[c1] - hp[c0] <= cap, but one cell at the least
+                const int64_t end = std::min(n, c0 + ((int64_t)1 << 30));
+                int64_t c1 = std::upper_bound(hp.begin() + c0, hp.begin() + end + 1, hp[(size_t)c0] + cap) - hp.begin() - 1;
+                c1 = std::max(c1, c0 + 1);
+                if (hp[(size_t)c1] > hp[(size_t)c0]) {  // (a block of empty cells has nothing to write)
+                    blocks.push_back({(int)bi, c0, (int)(c1 - c0)});
+                    largest = std::max(largest, hp[(size_t)c1] - hp[(size_t)c0]);
+                }
+                c0 = c1;
+            }
+        }
+        if (blocks.empty()) return;
+        double* dev[2] = {out_[0].reserve((size_t)largest), out_[1].reserve((size_t)largest)};
+        std::vector<int> done(blocks.size(), -1);
+        auto queue = [&](size_t i) {
+            const Blk& k = blocks[i];
+            const SparseNormBatch& b = *batches_[(size_t)k.bi];
+            const int ea = mark();
+            const dim3 grid((unsigned)cdiv(k.mb, 4));
+            if (log)
+                hipLaunchKernelGGL(sp_out_kernel<true>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
+                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, dev[i & 1]);
+            else
+                hipLaunchKernelGGL(sp_out_kernel<false>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
+                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, dev[i & 1]);
+            BMX_LAUNCH_CHECK();
+            done[i] = mark();
+            timer_.span(3, ea, done[i]);
+        };
+        queue(0);
+        for (size_t i = 0; i < blocks.size(); ++i) {
+            if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
+            const Blk& k = blocks[i];
+            const std::vector<int64_t>& hp = batches_[(size_t)k.bi]->hindptr;
+            const int64_t k0 = hp[(size_t)k.c0], k1 = hp[(size_t)(k.c0 + k.mb)];
+            BMX_HIP(hipStreamWaitEvent(stream_, timer_.event(done[i]), 0));
+            download_pageable(outs[k.bi] + k0, dev[i & 1], (size_t)(k1 - k0) * sizeof(double), stream_);
+        }
+        BMX_HIP(hipStreamSynchronize(kstream_));
+        BMX_HIP(hipStreamSynchronize(stream_));
+    }
+
+    hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
+    hipEvent_t landed_ = nullptr;
+    SpanTimer timer_;
+    DevBuf<double> stats_, mult_, zero_, out_[2];
+    DevBuf<int32_t> rows_, flags_;
+    int nS_ = 0;
+    bool subset_ = false;
+    double ms_[5] = {0, 0, 0, 0, 0};
+};
+
 Norm* norm_create(int device, int G, const int32_t* stat_rows, int64_t n_stat) {
     norm_check_create(G, stat_rows, n_stat);
     return new Norm(device, G, stat_rows, n_stat);
@@ -594,5 +1009,23 @@ void norm_run(Norm* h, double min_mean, int log, double pseudo_count, double* co
     h->run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out);
 }
 void norm_stage_ms(const Norm* h, double* out5) { h->stage_ms(out5); }
+
+NormSparse* norm_sparse_create(int device, int G, const int32_t* stat_rows, int64_t n_stat) {
+    norm_check_create(G, stat_rows, n_stat);
+    return new NormSparse(device, G, stat_rows, n_stat);
+}
+void norm_sparse_destroy(NormSparse* h) { delete h; }
+void norm_sparse_begin_batch(NormSparse* h, int64_t n, const double* size_factors, int64_t nnz) {
+    h->begin_batch(n, size_factors, nnz);
+}
+void norm_sparse_add_block(NormSparse* h, int64_t m, const int64_t* indptr, const int32_t* indices, const double* data,
+                           int64_t nnz) {
+    h->add_block(m, indptr, indices, data, nnz);
+}
+void norm_sparse_run(NormSparse* h, double min_mean, int log, double pseudo_count, double* const* outs, double* sf_out,
+                     double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out) {
+    h->run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out, zero_out);
+}
+void norm_sparse_stage_ms(const NormSparse* h, double* out5) { h->stage_ms(out5); }
 
 }  // namespace bmx

@@ -30,4 +30,23 @@ void norm_run(Norm* h, double min_mean, int log, double pseudo_count, double* co
 // pass with its downloads
 void norm_stage_ms(const Norm* h, double* out5);
 
+// ---- the same for sparse counts: a batch is kept as CSC (indptr int64, 0-based int32 rows, FP64 values), its cells
+// arrive in column blocks, and the values are written for the stored entries only.
+class NormSparse;
+NormSparse* norm_sparse_create(int device, int G, const int32_t* stat_rows, int64_t n_stat);
+void norm_sparse_destroy(NormSparse* h);
+// a block of m cells for a batch of n cells that holds `filled` so far, without a device (throws Error(BMX_ERR_ARG)):
+// indptr [m + 1] relative to the block (starts at 0, never decreases, ends at nnz); indices / data [nnz]
+void norm_check_sparse_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
+                             const double* data, int64_t nnz);
+// a batch of n cells with nnz stored entries in all; size_factors as for norm_begin_batch
+void norm_sparse_begin_batch(NormSparse* h, int64_t n, const double* size_factors, int64_t nnz);
+void norm_sparse_add_block(NormSparse* h, int64_t m, const int64_t* indptr, const int32_t* indices, const double* data,
+                           int64_t nnz);
+// outs[b]: [nnz_b] the values of batch b's stored entries, in their order.  zero_out (nullable): what the same pass
+// makes of a count of zero, log2(pseudo_count) by the device's log2 or 0.  The rest as for norm_run.
+void norm_sparse_run(NormSparse* h, double min_mean, int log, double pseudo_count, double* const* outs, double* sf_out,
+                     double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out);
+void norm_sparse_stage_ms(const NormSparse* h, double* out5);
+
 }  // namespace bmx

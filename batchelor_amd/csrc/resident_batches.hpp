@@ -53,8 +53,11 @@ inline void check_block(const BlockLedger* open, const void* x_block, int64_t m,
     if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
 }
 
-// ---- the store.  Batch: a struct derived from ResidentBatch with the handle's own per-batch buffers.
+// ---- the store.  Batch: a struct derived from ResidentBatch with the handle's own per-batch buffers -- or, for a handle
+// that keeps its cells in another form (the sparse counts of multiBatchNorm), one derived from BlockLedger alone that
+// says `dense_x = false`: begin() then reserves nothing itself and add() is not for it.
 struct ResidentBatch : BlockLedger {
+    static constexpr bool dense_x = true;
     DevBuf<double> x;  // [n][G] (= genes x cells column-major)
 };
 
@@ -91,8 +94,8 @@ class ResidentBatches {
     }
     ~ResidentBatches() = default;
 
-    // A new batch of n cells (the caller has checked n: check_cell_count): x is reserved, then fill(batch) reserves and
-    // uploads what else the handle keeps for it; the batch joins the list when fill returns.
+    // A new batch of n cells (the caller has checked n: check_cell_count): x is reserved (a dense batch), then fill(batch)
+    // reserves and uploads what else the handle keeps for it; the batch joins the list when fill returns.
     template <class F>
     void begin(int64_t n, F&& fill) {
         check_begin(batches_.empty() ? nullptr : batches_.back().get());
@@ -100,7 +103,7 @@ class ResidentBatches {
         BMX_HIP(hipSetDevice(device_));
         auto nb = std::make_unique<Batch>();
         nb->n = n;
-        nb->x.reserve((size_t)n * G_);
+        if constexpr (Batch::dense_x) nb->x.reserve((size_t)n * G_);
         fill(*nb);
         batches_.push_back(std::move(nb));
     }

@@ -1,7 +1,7 @@
 """multiBatchNorm() (R/multiBatchNorm.R:88-280): per-batch size factors rescaled so that the batches' average counts agree,
 then log-normalized values.  The function the other corrections' inputs come from.
 
-The counts (genes x cells, dense) are uploaded once, whole or in column blocks, and stay in HBM.  Library sizes and the
+The counts (genes x cells) are uploaded once, whole or in column blocks, and stay in HBM.  Library sizes and the
 per-gene sums run behind the upload; the pairwise median ratios, the choice of the reference batch and the rescaling
 are taken on the device; one elementwise pass writes the values, which come back block by block behind the kernels
 (csrc/multi_batch_norm.hip, bmx_norm_*).  scuttle's helpers are used as include/batchelor_mi355x.h states them:
@@ -9,8 +9,16 @@ are taken on the device; one elementwise pass writes the values, which come back
     averages      rowMeans(t(t(x) / sf)) over subset_row
     values        log2(x / sf + pseudo_count), the size factors never re-centred (center.size.factors=FALSE)
 
-Out of scope (a clear error where it can be reached): sparse counts and SingleCellExperiment inputs (TypeError), hence
-altExp handling; integer or float32 storage on the device (inputs are converted to FP64 as elsewhere); logNormCounts
+Sparse counts: batches that are scipy.sparse matrices or arrays (all of a call, or none) are brought to canonical CSC on the
+host -- duplicates summed, rows ascending, float64 values, int32 rows -- and stay CSC in HBM (bmx_norm_sparse_*).  The
+per-gene sums take their terms in the dense path's order with the zeros left out, so with the same size factors every
+statistic equals the dense path's bit for bit.  Values are computed for the stored entries only (a stored zero is a value
+like any other): where a zero maps to 0.0 -- log=False, or log2(pseudo_count) == 0 on the device -- `logcounts` is CSC with
+the pattern of the canonical input, otherwise it is dense as R's is, filled with the device's image of a zero.
+
+Out of scope (a clear error where it can be reached): SingleCellExperiment inputs (TypeError), hence altExp handling;
+sparse and dense batches in one call (TypeError); integer or float32 storage on the device (inputs are converted to FP64
+as elsewhere); logNormCounts
 arguments other than `log` and `pseudo_count` in norm_args (`downsample`, `transform`, `size.factors`, ...: ValueError);
 handing the result to fastMNN without a copy to the host; batches that do not fit in HBM together (the allocation fails
 with BatchelorMI355XError).
@@ -22,6 +30,7 @@ from dataclasses import dataclass
 from typing import Optional, Union
 
 import numpy as np
+import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
@@ -37,7 +46,8 @@ NORM_ARGS = ("log", "pseudo_count")
 @dataclass
 class MultiBatchNormResult:
     """What multiBatchNorm() returns."""
-    logcounts: Union[list, np.ndarray]     # per batch genes x cells, or one matrix in the caller's cell order (column-major)
+    logcounts: Union[list, np.ndarray]     # per batch genes x cells, or one matrix in the caller's cell order (column-major);
+                                           # sparse counts: CSC where a zero stays 0.0, dense otherwise
     size_factors: Union[list, np.ndarray]  # the size factors the values were divided by, same shape
     batch: np.ndarray                      # per batch its id (1-based), name or level; one object kept whole: per cell
     averages: np.ndarray                   # |subset_row| x batches
@@ -84,6 +94,94 @@ class _NormHandle(ResidentHandle):
         return out, sf, ave, ratios, int(smallest.value)
 
 
+def canonical_csc(m):
+    """A scipy.sparse matrix or array of any format as canonical CSC: duplicates summed, rows ascending within a column,
+    float64 data, int32 indices; stored zeros stay.  Returns (csc, owned): the caller's object is never modified, and
+    `owned` is False when the result still shares its index arrays with it."""
+    c = m.tocsc()
+    owned = c is not m
+    if not c.has_canonical_format:
+        if not owned:
+            c, owned = c.copy(), True
+        c.sum_duplicates()  # (sorts the indices first)
+    if c.data.dtype != np.float64:
+        c = sp.csc_matrix((c.data.astype(np.float64), c.indices, c.indptr), shape=c.shape)
+    if c.indices.dtype != np.int32:
+        c = sp.csc_matrix((c.data, c.indices.astype(np.int32), c.indptr), shape=c.shape)
+        owned = True
+    return c, owned
+
+
+def csc_blocks(c, width):
+    """The column blocks of canonical CSC `c`, `width` cells each (the last one fewer), as the library takes them:
+    (cells, indptr relative to the block as int64, indices, data)."""
+    n = c.shape[1]
+    for a in range(0, n, width):
+        b = min(n, a + width)
+        k0, k1 = int(c.indptr[a]), int(c.indptr[b])
+        yield b - a, c.indptr[a:b + 1].astype(np.int64) - k0, c.indices[k0:k1], c.data[k0:k1]
+
+
+class _SparseNormHandle(ResidentHandle):
+    """bmx_norm_sparse_t: _NormHandle for counts kept as CSC in HBM."""
+    PREFIX = "bmx_norm_sparse"
+    STAGES = STAGES
+
+    def __init__(self, n_genes, device, stat_rows=None):
+        rows = None if stat_rows is None else np.ascontiguousarray(stat_rows, dtype=np.int32)
+        super().__init__(n_genes, device, None if rows is None else _lib.i32p(rows),
+                         ctypes.c_int64(-1 if rows is None else int(rows.size)))
+        self.n_stat = self.G if rows is None else int(rows.size)
+        self.nnz = []
+
+    def add_batch(self, c, size_factors=None, block_bytes=None):
+        """c: canonical CSC, genes x cells.  The blocks are whole chunks of cells, as many as hold about block_bytes of
+        stored entries (12 bytes each) at the batch's mean density."""
+        bb = BLOCK_BYTES if block_bytes is None else block_bytes
+        n, nnz = int(c.shape[1]), int(c.nnz)
+        per = max(1, int(bb) * n // max(1, 12 * nnz))
+        per = max(CHUNK, per // CHUNK * CHUNK)
+        sf = None if size_factors is None else np.ascontiguousarray(size_factors, dtype=np.float64)
+        self._call("begin_batch", ctypes.c_int64(n), None if sf is None else _lib.f64p(sf), ctypes.c_int64(nnz))
+        for m, indptr, indices, data in csc_blocks(c, per):
+            self._call("add_block", ctypes.c_int64(m), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
+                       _lib.f64p(data), ctypes.c_int64(data.size))
+        self.ncells.append(n)
+        self.nnz.append(nnz)
+
+    def run(self, min_mean, log, pseudo_count):
+        N, B = sum(self.ncells), len(self.ncells)
+        outs = [np.empty(k, dtype=np.float64) for k in self.nnz]
+        ptrs = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+        sf = np.empty(N, dtype=np.float64)
+        ave = np.empty((self.n_stat, B), dtype=np.float64, order="F")
+        ratios = np.empty((B, B), dtype=np.float64)
+        smallest, zero = ctypes.c_int32(0), ctypes.c_double(0.0)
+        self._call("run", ctypes.c_double(float(min_mean)), ctypes.c_int32(int(bool(log))),
+                   ctypes.c_double(float(pseudo_count)), ptrs, _lib.f64p(sf), _lib.f64p(ave), _lib.f64p(ratios),
+                   ctypes.byref(smallest), ctypes.byref(zero))
+        return outs, float(zero.value), sf, ave, ratios, int(smallest.value)
+
+
+def _sparse_batches(batches):
+    """The batches as CSC if they are scipy.sparse objects (None if none is); a call that mixes them with anything else
+    is refused."""
+    raw = unpack_batches(batches)
+    flags = [sp.issparse(b) for b in raw]
+    if not any(flags):
+        return None
+    if not all(flags):
+        raise TypeError("multiBatchNorm takes batches that are all sparse or all dense, not a mixture")
+    return [b.tocsc() for b in raw]
+
+
+def _same_rows(mats):
+    for m in mats:
+        if m.shape[0] != mats[0].shape[0]:
+            raise ValueError("number of rows is not the same across batches")
+    return mats[0].shape[0]
+
+
 def _check_size_factors(sf, n):
     sf = np.asarray(sf, dtype=np.float64)
     if sf.ndim != 1 or sf.shape[0] != n:
@@ -96,15 +194,19 @@ def _check_size_factors(sf, n):
 def multiBatchNorm(*batches, batch=None, size_factors=None, norm_args=None, min_mean=1, subset_row=None,
                    normalize_all=False, preserve_single=True, names=None, device=0) -> MultiBatchNormResult:
     """multiBatchNorm(..., batch=, norm.args=, min.mean=, subset.row=, normalize.all=, preserve.single=)
-    (R/multiBatchNorm.R:88-171).  Each batch is a dense genes x cells matrix of counts; one object plus `batch=` is split
-    by column (levels sorted).  `size_factors`: one vector per batch (one vector over all cells for a single object), in
+    (R/multiBatchNorm.R:88-171).  Each batch is a genes x cells matrix of counts, all dense or all scipy.sparse (see the
+    module's text for what a sparse call returns); one object plus `batch=` is split by column (levels sorted).
+    `size_factors`: one vector per batch (one vector over all cells for a single object), in
     place of sizeFactors(); None: library sizes over `subset_row`.  `norm_args`: `log` (default True) and `pseudo_count`
     (default 1).  `names` plays the role of the argument names of `...`.  With one object and preserve_single the result
     is one matrix and one vector in the caller's cell order, otherwise lists with one entry per batch."""
-    mats = _as_matrices(batches, "multiBatchNorm")
+    mats = _sparse_batches(batches)
+    sparse = mats is not None
+    if not sparse:
+        mats = _as_matrices(batches, "multiBatchNorm")
     if len(mats) == 0:
         raise ValueError("at least one matrix of counts must be supplied")  # R/multiBatchNorm.R:118
-    G = check_same_dim(mats, byrow=False)
+    G = _same_rows(mats) if sparse else check_same_dim(mats, byrow=False)
     norm_args = dict(norm_args or {})
     for key in norm_args:
         if key not in NORM_ARGS:
@@ -148,17 +250,42 @@ def multiBatchNorm(*batches, batch=None, size_factors=None, norm_args=None, min_
             stat_rows = sub                      # values for every row, statistics over subset_row
         else:
             mats = [m[sub - 1] for m in mats]    # R/multiBatchNorm.R:146-148, :162-164
+    if sparse:  # (a batch that is still the caller's object lends its index arrays: the result gets copies of them)
+        given = {id(b) for b in unpack_batches(batches)}
+        mats, owned = zip(*[(c, own or id(m) not in given) for m in mats for c, own in [canonical_csc(m)]])
     _lib.require_gpu()
-    h = _NormHandle(mats[0].shape[0], device, stat_rows)
+    h = (_SparseNormHandle if sparse else _NormHandle)(mats[0].shape[0], device, stat_rows)
     try:
         for m, s in zip(mats, sfs):
             h.add_batch(m, s)
-        out, sf, ave, ratios, smallest = h.run(min_mean, log, pseudo_count)
+        if sparse:
+            values, zero, sf, ave, ratios, smallest = h.run(min_mean, log, pseudo_count)
+        else:
+            out, sf, ave, ratios, smallest = h.run(min_mean, log, pseudo_count)
         stage_ms = h.stage_ms()
     finally:
         h.close()
 
-    if reorder is not None and preserve_single:
+    if sparse and zero == 0.0:  # a zero stays a zero: the result keeps the pattern
+        parts = [sp.csc_matrix((v, m.indices if o else m.indices.copy(), m.indptr if o else m.indptr.copy()), shape=m.shape)
+                 for v, m, o in zip(values, mats, owned)]
+        out = None
+    elif sparse:                # dense, as R's: the image of a zero everywhere, the stored entries scattered in
+        out = np.full((mats[0].shape[0], sum(m.shape[1] for m in mats)), zero, dtype=np.float64, order="F")
+        at = 0
+        for v, m in zip(values, mats):
+            out[m.indices, at + np.repeat(np.arange(m.shape[1]), np.diff(m.indptr))] = v
+            at += m.shape[1]
+
+    if out is None:
+        edges = np.concatenate([[0], np.cumsum([m.shape[1] for m in mats])])
+        if reorder is not None and preserve_single:
+            logcounts = sp.hstack(parts, format="csc")[:, reorder - 1]
+            size_out, labels_out = sf[reorder - 1], batch
+        else:
+            logcounts, labels_out = parts, np.asarray(labels)
+            size_out = [sf[a:b] for a, b in zip(edges[:-1], edges[1:])]
+    elif reorder is not None and preserve_single:
         logcounts = np.asfortranarray(out[:, reorder - 1])  # sizeFactors(sce) <- all.sf[reorder] (:150-152)
         size_out = sf[reorder - 1]
         labels_out = batch

@@ -510,6 +510,38 @@ int32_t bmx_norm_run(bmx_norm_t* h, double min_mean, int32_t log, double pseudo_
  * out[3] the output kernels; out[4] = host wall time of the output pass with its downloads. */
 int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5);
 
+/* Sparse counts: the same function over batches kept in HBM as CSC -- per batch indptr [n + 1] (int64), 0-based int32 row
+ * indices and FP64 values, the rows of a column strictly ascending (no duplicates; explicit zeros are values like any
+ * other).  A batch is announced with its cells and its stored entries and filled in column blocks.  Statistics, ratios
+ * and flags are those of bmx_norm_t, and the per-gene sums take their terms in the same order with the zeros left out,
+ * which changes no bit of a sum of non-negative terms: with the same size factors the results equal the dense handle's
+ * bit for bit.  Values are written for the stored entries only; zero_out tells what every other entry would be.  What
+ * only the device sees of the pattern is flagged like a bad count and reported by bmx_norm_sparse_run: "a row index is
+ * outside [0, number of genes)", "the row indices of a column should be strictly ascending".  Such entries are skipped
+ * by every kernel, never used as an address. */
+typedef struct bmx_norm_sparse bmx_norm_sparse_t;
+/* stat_rows / n_stat: as for bmx_norm_create. */
+int32_t bmx_norm_sparse_create(int32_t device, int32_t n_genes, const int32_t* stat_rows, int64_t n_stat,
+                               bmx_norm_sparse_t** out);
+void bmx_norm_sparse_destroy(bmx_norm_sparse_t* h);
+/* The checks of a block on their own (no device): a block of n_block cells for a batch of n cells of which `filled` have
+ * arrived.  indptr [n_block + 1] is relative to the block: it starts at 0, never decreases and ends at nnz; indices and
+ * data [nnz] may be NULL only when nnz is 0. */
+int32_t bmx_norm_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
+                                    const int32_t* indices, const double* data, int64_t nnz);
+/* A batch of n cells with nnz stored entries in all (reserved once).  size_factors: as for bmx_norm_begin_batch.  Its cells
+ * follow in one or more blocks, in order; a block's reductions run behind the upload of the next. */
+int32_t bmx_norm_sparse_begin_batch(bmx_norm_sparse_t* h, int64_t n, const double* size_factors, int64_t nnz);
+int32_t bmx_norm_sparse_add_block(bmx_norm_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                  const double* data, int64_t nnz);
+/* outs[b]: [nnz_b] the values of batch b's stored entries in their order (may be NULL for a batch without entries).
+ * zero_out (nullable): log2(pseudo_count) by the device's log2 -- what the dense handle writes for a zero -- or 0 without
+ * the log.  The other arguments as for bmx_norm_run. */
+int32_t bmx_norm_sparse_run(bmx_norm_sparse_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs,
+                            double* sf_out, double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out);
+/* As bmx_norm_stage_ms. */
+int32_t bmx_norm_sparse_stage_ms(const bmx_norm_sparse_t* h, double* out5);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * mnnDeltaVariance() (R/mnnDeltaVariance.R:95-201): per gene and merge step, the mean of the MNN-paired cells and the
  * variance of their deltas.  The batches (genes x cells, column-major) are uploaded once, whole or in column blocks
