@@ -1,5 +1,7 @@
-// extern "C" boundary of libbatchelor_mi355x.so (declared in include/batchelor_mi355x.h).
-// Nothing throws across it: exceptions become return codes + a thread-local message.
+// extern "C" boundary of libbatchelor_mi355x.so (declared in include/batchelor_mi355x.h): the engine, the one-shot
+// primitives, the legacy natives and mnnCorrect.  The entry points of the handles that keep batches resident (bmx_pca_*,
+// bmx_cluster_*, bmx_linear_*, bmx_norm_*, bmx_norm_sparse_*, bmx_delta_*) stand at the end of their classes' files.
+// Nothing throws across the boundary: exceptions become return codes + a thread-local message (guarded, defined here).
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -15,14 +17,11 @@
 
 #include "bmx_common.hpp"
 #include "bmx_ops.hpp"
-#include "cluster_mnn.hpp"
-#include "delta_variance.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
-#include "linear_correct.hpp"
 #include "mnn_correct.hpp"
-#include "multi_batch_norm.hpp"
 #include "rccl_dyn.hpp"
+#include "resident_batches.hpp"
 
 struct bmx_engine {
     std::unique_ptr<bmx::Engine> impl;
@@ -38,22 +37,6 @@ thread_local std::string g_last_error;
 thread_local int64_t g_last_fallbacks = 0;
 thread_local int g_force_exact = 0;
 thread_local std::unique_ptr<bmx::Engine> g_prim;  // scratch engine behind the single-primitive entry points
-
-int guarded(const std::function<void()>& fn) {
-    try {
-        fn();
-        return BMX_OK;
-    } catch (const bmx::Error& e) {
-        g_last_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        g_last_error = "out of host memory";
-        return BMX_ERR_HIP;
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        return BMX_ERR_ARG;
-    }
-}
 
 bmx::Engine& prim(int d) {
     if (!g_prim) {
@@ -126,13 +109,6 @@ bmx_params_t read_params(const bmx_params_t* params) {
     return read_versioned(params, offsetof(bmx_params_t, auto_merge) + sizeof(int32_t), "bmx_params_t", defaults);
 }
 
-// the implementation behind a handle of the C ABI
-template <class H>
-auto impl_of(H* h) -> decltype(h->impl) {
-    if (!h) throw bmx::Error(BMX_ERR_ARG, "null handle");
-    return h->impl;
-}
-
 template <class T>
 T* malloc_arr(size_t n) {
     T* p = (T*)std::malloc(std::max<size_t>(n, 1) * sizeof(T));
@@ -162,6 +138,25 @@ void make_node(bmx::Engine& e, bmx::Node& node, bmx::DevBuf<double>& tmp, const 
 }
 
 }  // namespace
+
+// (declared in resident_batches.hpp: the entry points of the resident-batch handles, which stand beside their classes,
+// go through it too)
+int bmx::guarded(const std::function<void()>& fn) {
+    try {
+        fn();
+        return BMX_OK;
+    } catch (const bmx::Error& e) {
+        g_last_error = e.what();
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        g_last_error = "out of host memory";
+        return BMX_ERR_HIP;
+    } catch (const std::exception& e) {
+        g_last_error = e.what();
+        return BMX_ERR_ARG;
+    }
+}
+using bmx::guarded;
 
 extern "C" {
 
@@ -764,356 +759,6 @@ int32_t bmx_cosnorm_project(const double* x, int32_t G, int32_t n, const double*
         bmx::cosnorm_project_device(s, px, G, n, pu, d, pc, cos_norm, po, nullptr, dcu.reserve(d));
         BMX_HIP(hipMemcpyAsync(out, po, (size_t)n * d * sizeof(double), hipMemcpyDeviceToHost, s));
         BMX_HIP(hipStreamSynchronize(s));
-    });
-}
-
-/* ---------------------------------------------------------------- device PCA ------------------------------------ */
-struct bmx_pca {
-    bmx::Pca* impl = nullptr;
-    ~bmx_pca() { bmx::pca_destroy(impl); }
-};
-
-int32_t bmx_pca_create(int32_t device, int32_t G, bmx_pca_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "the PCA needs at least one gene");
-        auto h = std::make_unique<bmx_pca>();
-        h->impl = bmx::pca_create(device, G);
-        *out = h.release();
-    });
-}
-
-void bmx_pca_destroy(bmx_pca_t* p) { delete p; }
-
-int32_t bmx_pca_add_batch(bmx_pca_t* p, const double* x, int64_t n, double weight, int32_t cos_norm) {
-    return guarded([&] { bmx::pca_add_batch(impl_of(p), x, n, weight, cos_norm); });
-}
-
-int32_t bmx_pca_begin_batch(bmx_pca_t* p, int64_t n, double weight, int32_t cos_norm) {
-    return guarded([&] { bmx::pca_begin_batch(impl_of(p), n, weight, cos_norm); });
-}
-
-int32_t bmx_pca_add_block(bmx_pca_t* p, const double* x_block, int64_t n_block) {
-    return guarded([&] { bmx::pca_add_block(impl_of(p), x_block, n_block); });
-}
-
-int32_t bmx_pca_fit(bmx_pca_t* p, int32_t d, int32_t iters, double* centers, double* rotation, double* sdev) {
-    return guarded([&] { bmx::pca_fit(impl_of(p), d, 0.0, iters, centers, rotation, sdev, nullptr, nullptr); });
-}
-
-int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, double* centers, double* rotation,
-                        double* sdev, int32_t* iters_used, double* residual) {
-    return guarded([&] {
-        if (!(tol > 0.0)) throw bmx::Error(BMX_ERR_ARG, "the PCA tolerance must be positive");
-        int used = 0;
-        double res = 0.0;
-        try {
-            bmx::pca_fit(impl_of(p), d, tol, max_iters, centers, rotation, sdev, &used, &res);
-        } catch (...) {
-            if (iters_used) *iters_used = used;
-            if (residual) *residual = res;
-            throw;
-        }
-        if (iters_used) *iters_used = used;
-        if (residual) *residual = res;
-    });
-}
-
-int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out) {
-    return guarded([&] { bmx::pca_project(impl_of(p), batch, out); });
-}
-
-/* ---------------------------------------------------------------- clusterMNN ------------------------------------ */
-struct bmx_cluster {
-    bmx::Cluster* impl = nullptr;
-    ~bmx_cluster() { bmx::cluster_destroy(impl); }
-};
-
-int32_t bmx_cluster_create(int32_t device, int32_t G, const int32_t* subset_row, int32_t n_subset_row, bmx_cluster_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "clusterMNN needs at least one gene");
-        if (n_subset_row < 0 || (n_subset_row > 0 && !subset_row)) throw bmx::Error(BMX_ERR_ARG, "invalid 'subset_row'");
-        for (int32_t i = 0; i < n_subset_row; ++i)
-            if (subset_row[i] < 1 || subset_row[i] > G) throw bmx::Error(BMX_ERR_SUBSET, "subset indices out of range");
-        auto h = std::make_unique<bmx_cluster>();
-        h->impl = bmx::cluster_create(device, G, subset_row, n_subset_row);
-        *out = h.release();
-    });
-}
-
-void bmx_cluster_destroy(bmx_cluster_t* h) { delete h; }
-
-int32_t bmx_cluster_begin_batch(bmx_cluster_t* h, int64_t n, const int32_t* clusters0, int32_t n_clusters,
-                                const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
-    return guarded([&] {
-        bmx::cluster_begin_batch(impl_of(h), n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
-    });
-}
-
-int32_t bmx_cluster_add_block(bmx_cluster_t* h, const double* x_block, int64_t n_block) {
-    return guarded([&] {
-        bmx::cluster_add_block(impl_of(h), x_block, n_block);
-    });
-}
-
-int32_t bmx_cluster_add_batch(bmx_cluster_t* h, const double* x, int64_t n, const int32_t* clusters0, int32_t n_clusters,
-                              const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
-    return guarded([&] {
-        if (!x) throw bmx::Error(BMX_ERR_ARG, "the batch is missing");
-        bmx::cluster_begin_batch(impl_of(h), n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm);
-        bmx::cluster_add_block(impl_of(h), x, n);
-    });
-}
-
-int32_t bmx_cluster_centroids(bmx_cluster_t* h, int32_t batch, double* out) {
-    return guarded([&] {
-        bmx::cluster_centroids(impl_of(h), batch, out);
-    });
-}
-
-int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rotation, int32_t d, const double* centers,
-                              const double* centroid_pcs, const double* corrected_pcs, double* out, double* sigma_out) {
-    return guarded([&] {
-        bmx::cluster_propagate(impl_of(h), batch, rotation, d, centers, centroid_pcs, corrected_pcs, out, sigma_out);
-    });
-}
-
-int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5) {
-    return guarded([&] {
-        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
-        bmx::cluster_stage_ms(h->impl, out5);
-    });
-}
-
-/* ---------------------------------------------------------------- rescaleBatches / regressBatches -------------- */
-struct bmx_linear {
-    bmx::Linear* impl = nullptr;
-    ~bmx_linear() { bmx::linear_destroy(impl); }
-};
-
-int32_t bmx_linear_create(int32_t device, int32_t G, bmx_linear_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "the linear corrections need at least one gene");
-        auto h = std::make_unique<bmx_linear>();
-        h->impl = bmx::linear_create(device, G);
-        *out = h.release();
-    });
-}
-
-void bmx_linear_destroy(bmx_linear_t* h) { delete h; }
-
-int32_t bmx_linear_expect(bmx_linear_t* h, int32_t kind, double log_base, double pseudo_count, int32_t keep_unlogged) {
-    return guarded([&] {
-        bmx::linear_expect(impl_of(h), kind, log_base, pseudo_count, keep_unlogged);
-    });
-}
-
-int32_t bmx_linear_begin_batch(bmx_linear_t* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
-    return guarded([&] {
-        bmx::linear_begin_batch(impl_of(h), n, restrict_idx, n_restrict);
-    });
-}
-
-int32_t bmx_linear_add_block(bmx_linear_t* h, const double* x_block, int64_t n_block) {
-    return guarded([&] {
-        bmx::linear_add_block(impl_of(h), x_block, n_block);
-    });
-}
-
-int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count, double* const* outs, double* avg_out,
-                           double* ref_out) {
-    return guarded([&] {
-        bmx::linear_rescale(impl_of(h), log_base, pseudo_count, outs, avg_out, ref_out);
-    });
-}
-
-int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
-                           int32_t n_keep, double* const* outs, double* coef_out) {
-    return guarded([&] {
-        bmx::linear_regress(impl_of(h), design, p, w, keep, n_keep, outs, coef_out);
-    });
-}
-
-int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs) {
-    return guarded([&] {
-        bmx::linear_fetch(impl_of(h), outs);
-    });
-}
-
-int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5) {
-    return guarded([&] {
-        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
-        bmx::linear_stage_ms(h->impl, out5);
-    });
-}
-
-/* ---------------------------------------------------------------- multiBatchNorm -------------------------------- */
-struct bmx_norm {
-    bmx::Norm* impl = nullptr;
-    ~bmx_norm() { bmx::norm_destroy(impl); }
-};
-
-int32_t bmx_norm_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat, bmx_norm_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        auto h = std::make_unique<bmx_norm>();
-        h->impl = bmx::norm_create(device, G, stat_rows, n_stat);
-        *out = h.release();
-    });
-}
-
-void bmx_norm_destroy(bmx_norm_t* h) { delete h; }
-
-int32_t bmx_norm_check_create(int32_t G, const int32_t* stat_rows, int64_t n_stat) {
-    return guarded([&] {
-        bmx::norm_check_create(G, stat_rows, n_stat);
-    });
-}
-
-int32_t bmx_norm_check_batch(int64_t n, const double* size_factors) {
-    return guarded([&] {
-        bmx::norm_check_batch(n, size_factors);
-    });
-}
-
-int32_t bmx_norm_check_run(double min_mean, int32_t log, double pseudo_count) {
-    return guarded([&] {
-        bmx::norm_check_run(min_mean, log, pseudo_count);
-    });
-}
-
-int32_t bmx_norm_begin_batch(bmx_norm_t* h, int64_t n, const double* size_factors) {
-    return guarded([&] {
-        bmx::norm_begin_batch(impl_of(h), n, size_factors);
-    });
-}
-
-int32_t bmx_norm_add_block(bmx_norm_t* h, const double* x_block, int64_t n_block) {
-    return guarded([&] {
-        bmx::norm_add_block(impl_of(h), x_block, n_block);
-    });
-}
-
-int32_t bmx_norm_run(bmx_norm_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs, double* sf_out,
-                     double* ave_out, double* ratios_out, int32_t* smallest_out) {
-    return guarded([&] {
-        bmx::norm_run(impl_of(h), min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out);
-    });
-}
-
-int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5) {
-    return guarded([&] {
-        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
-        bmx::norm_stage_ms(h->impl, out5);
-    });
-}
-
-struct bmx_norm_sparse {
-    bmx::NormSparse* impl = nullptr;
-    ~bmx_norm_sparse() { bmx::norm_sparse_destroy(impl); }
-};
-
-int32_t bmx_norm_sparse_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat,
-                               bmx_norm_sparse_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        auto h = std::make_unique<bmx_norm_sparse>();
-        h->impl = bmx::norm_sparse_create(device, G, stat_rows, n_stat);
-        *out = h.release();
-    });
-}
-
-void bmx_norm_sparse_destroy(bmx_norm_sparse_t* h) { delete h; }
-
-int32_t bmx_norm_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
-                                    const int32_t* indices, const double* data, int64_t nnz) {
-    return guarded([&] {
-        bmx::norm_check_sparse_block(n, filled, n_block, indptr, indices, data, nnz);
-    });
-}
-
-int32_t bmx_norm_sparse_begin_batch(bmx_norm_sparse_t* h, int64_t n, const double* size_factors, int64_t nnz) {
-    return guarded([&] {
-        bmx::norm_sparse_begin_batch(impl_of(h), n, size_factors, nnz);
-    });
-}
-
-int32_t bmx_norm_sparse_add_block(bmx_norm_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
-                                  const double* data, int64_t nnz) {
-    return guarded([&] {
-        bmx::norm_sparse_add_block(impl_of(h), n_block, indptr, indices, data, nnz);
-    });
-}
-
-int32_t bmx_norm_sparse_run(bmx_norm_sparse_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs,
-                            double* sf_out, double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out) {
-    return guarded([&] {
-        bmx::norm_sparse_run(impl_of(h), min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out,
-                             zero_out);
-    });
-}
-
-int32_t bmx_norm_sparse_stage_ms(const bmx_norm_sparse_t* h, double* out5) {
-    return guarded([&] {
-        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
-        bmx::norm_sparse_stage_ms(h->impl, out5);
-    });
-}
-
-/* ---------------------------------------------------------------- mnnDeltaVariance ------------------------------ */
-struct bmx_delta {
-    bmx::Delta* impl = nullptr;
-    ~bmx_delta() { bmx::delta_destroy(impl); }
-};
-
-int32_t bmx_delta_create(int32_t device, int32_t G, bmx_delta_t** out) {
-    return guarded([&] {
-        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
-        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "mnnDeltaVariance needs at least one gene");
-        auto h = std::make_unique<bmx_delta>();
-        h->impl = bmx::delta_create(device, G);
-        *out = h.release();
-    });
-}
-
-void bmx_delta_destroy(bmx_delta_t* h) { delete h; }
-
-int32_t bmx_delta_begin_batch(bmx_delta_t* h, int64_t n) {
-    return guarded([&] {
-        bmx::delta_begin_batch(impl_of(h), n);
-    });
-}
-
-int32_t bmx_delta_add_block(bmx_delta_t* h, const double* x_block, int64_t n_block) {
-    return guarded([&] {
-        bmx::delta_add_block(impl_of(h), x_block, n_block);
-    });
-}
-
-int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_genes0, int32_t n_norm_genes, int32_t nsteps,
-                      const int32_t* const* left, const int32_t* const* right, const int64_t* npairs, double* mean,
-                      double* total) {
-    return guarded([&] {
-        bmx::DeltaRun a;
-        a.cos_norm = cos_norm;
-        a.norm_genes0 = norm_genes0;
-        a.n_norm_genes = n_norm_genes;
-        a.nsteps = nsteps;
-        a.left = left;
-        a.right = right;
-        a.npairs = npairs;
-        a.mean = mean;
-        a.total = total;
-        bmx::delta_run(impl_of(h), a);  // (delta_check_run comes before any device work)
-    });
-}
-
-int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5) {
-    return guarded([&] {
-        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
-        bmx::delta_stage_ms(h->impl, out5);
     });
 }
 

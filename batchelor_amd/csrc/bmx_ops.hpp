@@ -1,5 +1,8 @@
-// Device-level building blocks of the merge loop (implemented in pairs.hip / correct.hip / legacy.hip).
-// All pointers are device pointers, all matrices row-major [cells x d] FP64, all launches go to `stream`.
+// Device-level building blocks that more than one file uses: the merge loop's (pairs.hip / correct.hip), the steps
+// upstream of the engine (prepca.hip) and the legacy natives (legacy.hip).  Unless a section says otherwise all pointers
+// are device pointers, all matrices row-major [cells x d] FP64, and all launches go to `stream`.  The handles that keep
+// batches resident (pca.hip, cluster_mnn.hip, linear_correct.hip, multi_batch_norm.hip, delta_variance.hip) hold their
+// own classes and C entry points and declare nothing here.
 #pragma once
 #include <functional>
 #include "bmx_common.hpp"
@@ -159,18 +162,9 @@ void apply_cosine_norm_device(hipStream_t stream, const double* x, int G, int n,
 void cosnorm_project_device(hipStream_t stream, const double* x, int G, int n, const double* u, int d,
                             const double* centers, int cos_norm, double* out, double* l2_out, double* cu_scratch);
 
-// ---- multiBatchPCA on the device (pca.hip) -----------------------------------------------------------------------
-class Pca;
-Pca* pca_create(int device, int G);
-void pca_destroy(Pca* p);
-void pca_add_batch(Pca* p, const double* x_host, int64_t n, double weight, int cos_norm);
-void pca_begin_batch(Pca* p, int64_t n, double weight, int cos_norm);
-void pca_add_block(Pca* p, const double* x_block_host, int64_t m);
-// tol > 0: until the relative Ritz residual of the d wanted pairs is <= tol, at most max_applies applications of the
-// operator (throws if not reached); tol <= 0: exactly max_applies plain subspace steps
-void pca_fit(Pca* p, int d, double tol, int max_applies, double* centers, double* rotation, double* sdev, int* applies_used,
-             double* resid);
-void pca_project(Pca* p, int batch, double* out_host);
+// ---- mnnDeltaVariance (delta_variance.hip): the tiling of its pair passes, which bmx_dev_get reports -------------
+constexpr int DELTA_GENE_TILE = 256;   // genes a workgroup of the pair passes owns
+constexpr int DELTA_PAIR_CHUNK = 128;  // pairs of one step a workgroup walks (fixed: the results do not depend on the grid)
 
 // ---- legacy natives (legacy.hip) -------------------------------------------------------------------
 void smooth_gaussian_kernel_device(hipStream_t stream, const double* averaged, int g, int U, const int32_t* index,

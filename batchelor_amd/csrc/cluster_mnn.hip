@@ -22,7 +22,6 @@
 #include <vector>
 
 #include "bmx_ops.hpp"
-#include "cluster_mnn.hpp"
 #include "host_xfer.hpp"
 #include "resident_batches.hpp"
 
@@ -292,6 +291,7 @@ __global__ __launch_bounds__(256) void smooth_kernel(double* __restrict__ cur, i
 
 }  // namespace
 
+// argument checks of Cluster::begin_batch, without a device (throws Error(BMX_ERR_ARG))
 void cluster_check_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t n_restrict) {
     check_cell_count(n);
     if (C < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cluster");
@@ -320,8 +320,10 @@ struct ClusterBatch : ResidentBatch {
     bool cos_norm = false;
 };
 
+// The batches stay resident between the centroid pass and the propagation of the centroids' corrections to the cells.
 class Cluster : ResidentBatches<ClusterBatch> {
   public:
+    // subset: 1-based genes (subset.row) the cosine norms and the projection are taken over, or null / ns = 0 for all
     Cluster(int device, int G, const int32_t* subset, int ns) : ResidentBatches(device, G, "bmx_cluster_begin_batch") {
         if (subset && ns > 0) sub0_host_.assign(subset, subset + ns);
         for (int32_t& s : sub0_host_) s -= 1;
@@ -334,6 +336,8 @@ class Cluster : ResidentBatches<ClusterBatch> {
     }
     ~Cluster() { retire(); }
 
+    // a batch of n cells: clusters0 [n] 0-based cluster ids below C, restrict_idx 1-based cells (null / nr < 0: all);
+    // its columns follow in one or more blocks, in order
     void begin_batch(int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx, int64_t nr, bool cos_norm) {
         cluster_check_batch(n, clusters0, C, restrict_idx, nr);
         const bool restricted = is_restricted(restrict_idx, nr);
@@ -408,6 +412,7 @@ class Cluster : ResidentBatches<ClusterBatch> {
     }
     int nrot() const { return sub0_host_.empty() ? G_ : (int)sub0_host_.size(); }
 
+    // .compute_centroids (R/clusterMNN.R:231-244): out [G x C_b] column-major host memory
     void centroids(int bi, double* out) {
         ClusterBatch& b = batch(bi);
         if (!out) throw Error(BMX_ERR_ARG, "'out' is missing");
@@ -431,6 +436,9 @@ class Cluster : ResidentBatches<ClusterBatch> {
         timer_.collect(ms_);
     }
 
+    // .propagate_to_cells for one batch (R/clusterMNN.R:262-282): rotation [rows x d] column-major and centers [rows] over
+    // the handle's genes (the subset's, in its order), cpcs / corr (the centroids' coordinates before and after the merge)
+    // [C_b x d] column-major, out [n_b x d]
     void propagate(int bi, const double* rotation, int d, const double* centers, const double* cpcs, const double* corr,
                    double* out, double* sigma_out) {
         ClusterBatch& b = batch(bi);
@@ -500,30 +508,74 @@ class Cluster : ResidentBatches<ClusterBatch> {
         timer_.collect(ms_);
     }
 
-    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+    // milliseconds since the handle was made: upload (host wall time of the staged copies), then HIP-event time of the
+    // centroid pass, the projection, nearest centroid + median, the smoothing
+    using ResidentBatches::stage_ms;
 
   private:
-    SpanTimer timer_;
     std::vector<int32_t> sub0_host_;
     DevBuf<int32_t> sub0_;
     DevBuf<double> part_, cen_, u_, small_, cur_, w_, dist_;
-    double ms_[5] = {0, 0, 0, 0, 0};
 };
 
-Cluster* cluster_create(int device, int G, const int32_t* subset, int nsubset) {
-    return new Cluster(device, G, subset, nsubset);
-}
-void cluster_destroy(Cluster* c) { delete c; }
-void cluster_begin_batch(Cluster* c, int64_t n, const int32_t* clusters0, int C, const int32_t* restrict_idx,
-                         int64_t n_restrict, int cos_norm) {
-    c->begin_batch(n, clusters0, C, restrict_idx, n_restrict, cos_norm != 0);
-}
-void cluster_add_block(Cluster* c, const double* x, int64_t m) { c->add_block(x, m); }
-void cluster_centroids(Cluster* c, int b, double* out) { c->centroids(b, out); }
-void cluster_propagate(Cluster* c, int b, const double* rotation, int d, const double* centers, const double* cpcs,
-                       const double* corr, double* out, double* sigma_out) {
-    c->propagate(b, rotation, d, centers, cpcs, corr, out, sigma_out);
-}
-void cluster_stage_ms(const Cluster* c, double* out5) { c->stage_ms(out5); }
-
 }  // namespace bmx
+
+/* ---------------------------------------------------------------- bmx_cluster_* --------------------------------- */
+struct bmx_cluster final : bmx::Cluster {
+    using Cluster::Cluster;
+};
+
+extern "C" {
+
+int32_t bmx_cluster_create(int32_t device, int32_t G, const int32_t* subset_row, int32_t n_subset_row, bmx_cluster_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "clusterMNN needs at least one gene");
+        if (n_subset_row < 0 || (n_subset_row > 0 && !subset_row)) throw bmx::Error(BMX_ERR_ARG, "invalid 'subset_row'");
+        for (int32_t i = 0; i < n_subset_row; ++i)
+            if (subset_row[i] < 1 || subset_row[i] > G) throw bmx::Error(BMX_ERR_SUBSET, "subset indices out of range");
+        *out = new bmx_cluster(device, G, subset_row, n_subset_row);
+    });
+}
+
+void bmx_cluster_destroy(bmx_cluster_t* h) { delete h; }
+
+int32_t bmx_cluster_begin_batch(bmx_cluster_t* h, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                                const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
+    return bmx::guarded([&] {
+        bmx::live(h).begin_batch(n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm != 0);
+    });
+}
+
+int32_t bmx_cluster_add_block(bmx_cluster_t* h, const double* x_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(h).add_block(x_block, n_block); });
+}
+
+int32_t bmx_cluster_add_batch(bmx_cluster_t* h, const double* x, int64_t n, const int32_t* clusters0, int32_t n_clusters,
+                              const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm) {
+    return bmx::guarded([&] {
+        if (!x) throw bmx::Error(BMX_ERR_ARG, "the batch is missing");
+        bmx::live(h).begin_batch(n, clusters0, n_clusters, restrict_idx, n_restrict, cos_norm != 0);
+        h->add_block(x, n);
+    });
+}
+
+int32_t bmx_cluster_centroids(bmx_cluster_t* h, int32_t batch, double* out) {
+    return bmx::guarded([&] { bmx::live(h).centroids(batch, out); });
+}
+
+int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rotation, int32_t d, const double* centers,
+                              const double* centroid_pcs, const double* corrected_pcs, double* out, double* sigma_out) {
+    return bmx::guarded([&] {
+        bmx::live(h).propagate(batch, rotation, d, centers, centroid_pcs, corrected_pcs, out, sigma_out);
+    });
+}
+
+int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5) {
+    return bmx::guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        h->stage_ms(out5);
+    });
+}
+
+}  // extern "C"

@@ -20,7 +20,6 @@
 #include <vector>
 
 #include "bmx_ops.hpp"
-#include "delta_variance.hpp"
 #include "host_xfer.hpp"
 #include "resident_batches.hpp"
 
@@ -266,6 +265,20 @@ __global__ __launch_bounds__(256) void total_reduce_kernel(const double* __restr
 
 }  // namespace
 
+// what Delta::run takes
+struct DeltaRun {
+    int cos_norm = 0;
+    const int32_t* norm_genes0 = nullptr;  // 0-based genes the cosine norms are taken over (null: all genes)
+    int n_norm_genes = 0;
+    int nsteps = 0;
+    const int32_t* const* left = nullptr;   // per step: 1-based columns of the batches in upload order
+    const int32_t* const* right = nullptr;
+    const int64_t* npairs = nullptr;
+    double* mean = nullptr;   // [G x nsteps] column-major
+    double* total = nullptr;  // [G x nsteps] column-major
+};
+
+// argument checks of Delta::begin_batch / run without a device (throw Error): G genes, N cells uploaded so far
 void delta_check_batch(int64_t n, int64_t cells_before) {
     check_cell_count(n);
     if (cells_before + n > 0x7fffffffll) throw Error(BMX_ERR_ARG, "the batches hold at most 2^31 - 1 cells together");
@@ -294,6 +307,7 @@ void delta_check_run(int G, int64_t N, const DeltaRun& a) {
 
 struct DeltaBatch : ResidentBatch {};
 
+// The batches stay resident; the per-gene mean and variance of the MNN-pair deltas of every merge step come out of one run.
 class Delta : ResidentBatches<DeltaBatch> {
   public:
     Delta(int device, int G) : ResidentBatches(device, G, "bmx_delta_begin_batch") {}
@@ -474,7 +488,9 @@ class Delta : ResidentBatches<DeltaBatch> {
         ms_[4] += now_ms() - t0;
     }
 
-    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+    // milliseconds since the handle was made: upload (host wall time), HIP-event time of the cell norms, of the two pair
+    // passes, of the pair preparation and the reductions over chunks, and the host wall time of the runs
+    using ResidentBatches::stage_ms;
 
   private:
     int64_t cells() const {
@@ -493,19 +509,62 @@ class Delta : ResidentBatches<DeltaBatch> {
             BMX_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream_));
     }
 
-    SpanTimer timer_;
     DevBuf<int32_t> left_, right_, chunk0_, genes_;
     DevBuf<int64_t> off_;
     DevBuf<double> pairs_, chunks_, base_, part_, stats_, l2_;  // (pairs_, chunks_, base_: records of 8-byte words)
     std::vector<double> host_;
-    double ms_[DELTA_STAGES] = {0, 0, 0, 0, 0};
 };
 
-Delta* delta_create(int device, int G) { return new Delta(device, G); }
-void delta_destroy(Delta* h) { delete h; }
-void delta_begin_batch(Delta* h, int64_t n) { h->begin_batch(n); }
-void delta_add_block(Delta* h, const double* x, int64_t m) { h->add_block(x, m); }
-void delta_run(Delta* h, const DeltaRun& a) { h->run(a); }
-void delta_stage_ms(const Delta* h, double* out5) { h->stage_ms(out5); }
-
 }  // namespace bmx
+
+/* ---------------------------------------------------------------- bmx_delta_* ----------------------------------- */
+struct bmx_delta final : bmx::Delta {
+    using Delta::Delta;
+};
+
+extern "C" {
+
+int32_t bmx_delta_create(int32_t device, int32_t G, bmx_delta_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "mnnDeltaVariance needs at least one gene");
+        *out = new bmx_delta(device, G);
+    });
+}
+
+void bmx_delta_destroy(bmx_delta_t* h) { delete h; }
+
+int32_t bmx_delta_begin_batch(bmx_delta_t* h, int64_t n) {
+    return bmx::guarded([&] { bmx::live(h).begin_batch(n); });
+}
+
+int32_t bmx_delta_add_block(bmx_delta_t* h, const double* x_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(h).add_block(x_block, n_block); });
+}
+
+int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_genes0, int32_t n_norm_genes, int32_t nsteps,
+                      const int32_t* const* left, const int32_t* const* right, const int64_t* npairs, double* mean,
+                      double* total) {
+    return bmx::guarded([&] {
+        bmx::DeltaRun a;
+        a.cos_norm = cos_norm;
+        a.norm_genes0 = norm_genes0;
+        a.n_norm_genes = n_norm_genes;
+        a.nsteps = nsteps;
+        a.left = left;
+        a.right = right;
+        a.npairs = npairs;
+        a.mean = mean;
+        a.total = total;
+        bmx::live(h).run(a);  // (delta_check_run comes before any device work)
+    });
+}
+
+int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5) {
+    return bmx::guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        h->stage_ms(out5);
+    });
+}
+
+}  // extern "C"

@@ -26,7 +26,6 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
-#include "linear_correct.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -221,8 +220,11 @@ __global__ __launch_bounds__(256) void residual_kernel(const double* __restrict_
 
 int mode_of(double log_base) { return log_base == 2.0 ? 1 : (log_base == 10.0 ? 2 : 3); }
 
+constexpr int LINEAR_MAX_P = 64;  // columns a design may have
+
 }  // namespace
 
+// argument checks of Linear::begin_batch / rescale / regress without a device (throw Error(BMX_ERR_ARG))
 void linear_check_batch(int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
     check_cell_count(n);
     check_restriction(n, restrict_idx, n_restrict);
@@ -258,6 +260,8 @@ struct LinearBatch : ResidentBatch {
     bool has_u = false;
 };
 
+// The batches stay resident between the pass that needs every cell (the per-gene statistics) and the pass that writes the
+// result.
 class Linear : ResidentBatches<LinearBatch> {
   public:
     Linear(int device, int G) : ResidentBatches(device, G, "bmx_linear_begin_batch") {
@@ -269,6 +273,9 @@ class Linear : ResidentBatches<LinearBatch> {
         if (landed_) (void)hipEventDestroy(landed_);
     }
 
+    // What the caller is going to ask for, said before the upload so that the per-gene sums of a column block run behind
+    // the upload of the next one: kind 0 nothing, 1 plain sums (regressBatches, default design), 2 sums of log_base^x -
+    // pseudo (rescaleBatches).  keep_unlogged != 0 (kind 2): the unlogged values are kept in HBM for the second pass.
     void expect(int kind, double log_base, double pseudo, int keep_unlogged) {
         if (kind < 0 || kind > 2) throw Error(BMX_ERR_ARG, "'kind' is 0, 1 or 2");
         if (kind == 2) linear_check_rescale(log_base, pseudo);
@@ -279,6 +286,7 @@ class Linear : ResidentBatches<LinearBatch> {
         keep_u_ = kind == 2 && keep_unlogged != 0;
     }
 
+    // a batch of n cells, restrict_idx 1-based cells (null / nr < 0: all); its columns follow in blocks, in order
     void begin_batch(int64_t n, const int32_t* restrict_idx, int64_t nr) {
         linear_check_batch(n, restrict_idx, nr);
         begin(n, [&](LinearBatch& b) {
@@ -320,6 +328,7 @@ class Linear : ResidentBatches<LinearBatch> {
         ms_[0] += now_ms() - t0;
     }
 
+    // outs[b]: [G x n_b] column-major host memory; avg_out [G x B], ref_out [G] (nullable)
     void rescale(double log_base, double pseudo, double* const* outs, double* avg_out, double* ref_out) {
         linear_check_rescale(log_base, pseudo);
         if (batches_.size() < 2) throw Error(BMX_ERR_ARG, "at least two batches must be specified");
@@ -360,6 +369,10 @@ class Linear : ResidentBatches<LinearBatch> {
         timer_.collect(ms_);
     }
 
+    // design null: one indicator column per batch, coef_out [G x B] (the batch means).  Otherwise design [N x p]
+    // column-major over the cells of all batches in upload order, w [R x p] column-major with coef = X[:, restricted] %*% w
+    // (R: the restricted cells, batch by batch, ascending within a batch), keep 1-based columns that are not regressed
+    // out; coef_out [G x p] (nullable)
     void regress(const double* design, int p, const double* w, const int32_t* keep, int n_keep, double* const* outs,
                  double* coef_out) {
         linear_check_regress(design, p, w, keep, n_keep);
@@ -444,6 +457,8 @@ class Linear : ResidentBatches<LinearBatch> {
         timer_.collect(ms_);
     }
 
+    // the batches as they were uploaded, back through the download ring with no kernel in between: what moving a call's
+    // bytes in and out costs at the least
     void fetch(double* const* outs) {
         check_ready(outs);
         CacheScope scope(&cache_);
@@ -457,7 +472,10 @@ class Linear : ResidentBatches<LinearBatch> {
         ms_[4] += now_ms() - t0;
     }
 
-    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+    // milliseconds since the handle was made: upload (host wall time), HIP-event time of the first pass (chunk sums or
+    // the product with w), of the statistics kernels, of the second pass's kernels, and the host wall time of the second
+    // pass with its downloads
+    using ResidentBatches::stage_ms;
 
   private:
     int mark() { return timer_.mark(kstream_); }  // a timing event recorded on the kernel stream now
@@ -542,32 +560,63 @@ class Linear : ResidentBatches<LinearBatch> {
 
     hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
     hipEvent_t landed_ = nullptr;
-    SpanTimer timer_;
     DevBuf<double> stats_, w_, d_, gpart_, out_[2];
     DevBuf<int32_t> drop_;
     int expect_kind_ = 0;
     double expect_base_ = 0.0, expect_pseudo_ = 0.0;
     bool keep_u_ = false;
-    double ms_[5] = {0, 0, 0, 0, 0};
 };
 
-Linear* linear_create(int device, int G) { return new Linear(device, G); }
-void linear_destroy(Linear* h) { delete h; }
-void linear_expect(Linear* h, int kind, double log_base, double pseudo_count, int keep_unlogged) {
-    h->expect(kind, log_base, pseudo_count, keep_unlogged);
-}
-void linear_begin_batch(Linear* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
-    h->begin_batch(n, restrict_idx, n_restrict);
-}
-void linear_add_block(Linear* h, const double* x, int64_t m) { h->add_block(x, m); }
-void linear_rescale(Linear* h, double log_base, double pseudo_count, double* const* outs, double* avg_out, double* ref_out) {
-    h->rescale(log_base, pseudo_count, outs, avg_out, ref_out);
-}
-void linear_regress(Linear* h, const double* design, int p, const double* w, const int32_t* keep, int n_keep,
-                    double* const* outs, double* coef_out) {
-    h->regress(design, p, w, keep, n_keep, outs, coef_out);
-}
-void linear_fetch(Linear* h, double* const* outs) { h->fetch(outs); }
-void linear_stage_ms(const Linear* h, double* out5) { h->stage_ms(out5); }
-
 }  // namespace bmx
+
+/* ---------------------------------------------------------------- bmx_linear_* ---------------------------------- */
+struct bmx_linear final : bmx::Linear {
+    using Linear::Linear;
+};
+
+extern "C" {
+
+int32_t bmx_linear_create(int32_t device, int32_t G, bmx_linear_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "the linear corrections need at least one gene");
+        *out = new bmx_linear(device, G);
+    });
+}
+
+void bmx_linear_destroy(bmx_linear_t* h) { delete h; }
+
+int32_t bmx_linear_expect(bmx_linear_t* h, int32_t kind, double log_base, double pseudo_count, int32_t keep_unlogged) {
+    return bmx::guarded([&] { bmx::live(h).expect(kind, log_base, pseudo_count, keep_unlogged); });
+}
+
+int32_t bmx_linear_begin_batch(bmx_linear_t* h, int64_t n, const int32_t* restrict_idx, int64_t n_restrict) {
+    return bmx::guarded([&] { bmx::live(h).begin_batch(n, restrict_idx, n_restrict); });
+}
+
+int32_t bmx_linear_add_block(bmx_linear_t* h, const double* x_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(h).add_block(x_block, n_block); });
+}
+
+int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count, double* const* outs, double* avg_out,
+                           double* ref_out) {
+    return bmx::guarded([&] { bmx::live(h).rescale(log_base, pseudo_count, outs, avg_out, ref_out); });
+}
+
+int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
+                           int32_t n_keep, double* const* outs, double* coef_out) {
+    return bmx::guarded([&] { bmx::live(h).regress(design, p, w, keep, n_keep, outs, coef_out); });
+}
+
+int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs) {
+    return bmx::guarded([&] { bmx::live(h).fetch(outs); });
+}
+
+int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5) {
+    return bmx::guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        h->stage_ms(out5);
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // multiBatchNorm() (R/multiBatchNorm.R:100-280, with scuttle's librarySizeFactors / calculateAverage / logNormCounts as
 // include/batchelor_mi355x.h defines them) on the device: genes x cells FP64 counts in R's layout, uploaded once (whole or
-// in column blocks) and kept in HBM.  S: the statistic rows (all rows, or the list given to norm_create).
+// in column blocks) and kept in HBM.  S: the statistic rows (all rows, or the list given to bmx_norm_create).
 //   upload  behind the copy of the next block, on a second stream:
 //             colsum_kernel        one wave a cell: its sum over S (the library size) in a fixed lane order, and the
 //                                  device flag for a negative or non-finite count
@@ -37,7 +37,6 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
-#include "multi_batch_norm.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -487,6 +486,7 @@ __global__ void zero_image_kernel(double pseudo, double* __restrict__ zero) {
 
 }  // namespace
 
+// argument checks of the handles' constructors / begin_batch / run without a device (throw Error(BMX_ERR_ARG))
 void norm_check_create(int G, const int32_t* stat_rows, int64_t n_stat) {
     if (G < 1) throw Error(BMX_ERR_ARG, "multiBatchNorm needs at least one gene");
     if (G > MAX_GENES) throw Error(BMX_ERR_ARG, "at most 16 776 960 genes");
@@ -511,6 +511,8 @@ void norm_check_run(double min_mean, int log, double pseudo_count) {
     if (!std::isfinite(pseudo_count)) throw Error(BMX_ERR_ARG, "'pseudo_count' must be finite");
 }
 
+// a block of m cells for a batch of n cells that holds `filled` so far, without a device (throws Error(BMX_ERR_ARG)):
+// indptr [m + 1] relative to the block (starts at 0, never decreases, ends at nnz); indices / data [nnz]
 void norm_check_sparse_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
                              const double* data, int64_t nnz) {
     if (!indptr) throw Error(BMX_ERR_ARG, "the block's 'indptr' is missing");
@@ -628,8 +630,13 @@ void upload_stat_rows(const int32_t* stat_rows, int64_t n_stat, int G, DevBuf<in
 
 }  // namespace
 
+// The count batches stay resident between the passes that need every cell (library sizes, per-gene averages), the ratio
+// stage and the pass that writes the normalized values.
 class Norm : ResidentBatches<NormBatch> {
   public:
+    // stat_rows: 1-based rows the size factors, averages and ratios are taken over (in the order given, a row named twice
+    // counts twice), n_stat of them; null / n_stat < 0: all G rows.  The values are written for all G rows either way.
+    // (the caller has checked them: norm_check_create)
     Norm(int device, int G, const int32_t* stat_rows, int64_t n_stat) : ResidentBatches(device, G, "bmx_norm_begin_batch") {
         CacheScope scope(&cache_);
         BMX_HIP(hipStreamCreateWithFlags(&kstream_, hipStreamNonBlocking));
@@ -648,6 +655,8 @@ class Norm : ResidentBatches<NormBatch> {
         if (landed_) (void)hipEventDestroy(landed_);
     }
 
+    // a batch of n cells, size_factors [n] (any scale; null: library sizes over the statistic rows); its columns follow
+    // in blocks, in order
     void begin_batch(int64_t n, const double* size_factors) {
         norm_check_batch(n, size_factors);
         begin(n, [&](NormBatch& b) {
@@ -679,6 +688,9 @@ class Norm : ResidentBatches<NormBatch> {
         ms_[0] += now_ms() - t0;
     }
 
+    // outs[b]: [G x n_b] column-major host memory.  Nullable: sf_out [cells of all batches in upload order] the size
+    // factors the values were divided by, ave_out [n_stat x B] column-major, ratios_out [B x B] row-major
+    // (ratios_out[i * B + j] is the median over the kept genes of ave_j / ave_i), smallest_out the 1-based reference batch.
     void run(double min_mean, int log, double pseudo, double* const* outs, double* sf_out, double* ave_out,
              double* ratios_out, int32_t* smallest_out) {
         norm_check_run(min_mean, log, pseudo);
@@ -726,7 +738,10 @@ class Norm : ResidentBatches<NormBatch> {
         throw_if_flagged(flags);
     }
 
-    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+    // milliseconds since the handle was made: upload (host wall time), HIP-event time of the statistics passes (column
+    // sums, per-gene sums, size factors, averages), of the ratio stage, of the output kernels, and the host wall time of
+    // the output pass with its downloads
+    using ResidentBatches::stage_ms;
 
   private:
     int mark() { return timer_.mark(kstream_); }
@@ -767,15 +782,14 @@ class Norm : ResidentBatches<NormBatch> {
 
     hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
     hipEvent_t landed_ = nullptr;
-    SpanTimer timer_;
     DevBuf<double> stats_, mult_, out_[2];
     DevBuf<int32_t> rows_, flags_;
     int nS_ = 0;
     bool subset_ = false;
-    double ms_[5] = {0, 0, 0, 0, 0};
 };
 
-// ---- sparse counts
+// ---- the same for sparse counts: a batch is kept as CSC (indptr int64, 0-based int32 rows, FP64 values), its cells
+// arrive in column blocks, and the values are written for the stored entries only.
 struct SparseNormBatch : BlockLedger, NormStats {
     static constexpr bool dense_x = false;
     DevBuf<int64_t> indptr;        // [n + 1] absolute positions
@@ -807,6 +821,7 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         if (landed_) (void)hipEventDestroy(landed_);
     }
 
+    // a batch of n cells with nnz stored entries in all; size_factors as for Norm::begin_batch
     void begin_batch(int64_t n, const double* size_factors, int64_t nnz) {
         norm_check_batch(n, size_factors);
         if (nnz < 0) throw Error(BMX_ERR_ARG, "the batch's number of stored entries is negative");
@@ -859,6 +874,8 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         ms_[0] += now_ms() - t0;
     }
 
+    // outs[b]: [nnz_b] the values of batch b's stored entries, in their order.  zero_out (nullable): what the same pass
+    // makes of a count of zero, log2(pseudo) by the device's log2 or 0.  The rest as for Norm::run.
     void run(double min_mean, int log, double pseudo, double* const* outs, double* sf_out, double* ave_out,
              double* ratios_out, int32_t* smallest_out, double* zero_out) {
         norm_check_run(min_mean, log, pseudo);
@@ -904,7 +921,7 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         throw_if_flagged(flags);
     }
 
-    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
+    using ResidentBatches::stage_ms;  // the stages of Norm
 
   private:
     int mark() { return timer_.mark(kstream_); }
@@ -989,43 +1006,105 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
 
     hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
     hipEvent_t landed_ = nullptr;
-    SpanTimer timer_;
     DevBuf<double> stats_, mult_, zero_, out_[2];
     DevBuf<int32_t> rows_, flags_;
     int nS_ = 0;
     bool subset_ = false;
-    double ms_[5] = {0, 0, 0, 0, 0};
 };
 
-Norm* norm_create(int device, int G, const int32_t* stat_rows, int64_t n_stat) {
-    norm_check_create(G, stat_rows, n_stat);
-    return new Norm(device, G, stat_rows, n_stat);
-}
-void norm_destroy(Norm* h) { delete h; }
-void norm_begin_batch(Norm* h, int64_t n, const double* size_factors) { h->begin_batch(n, size_factors); }
-void norm_add_block(Norm* h, const double* x, int64_t m) { h->add_block(x, m); }
-void norm_run(Norm* h, double min_mean, int log, double pseudo_count, double* const* outs, double* sf_out, double* ave_out,
-              double* ratios_out, int32_t* smallest_out) {
-    h->run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out);
-}
-void norm_stage_ms(const Norm* h, double* out5) { h->stage_ms(out5); }
-
-NormSparse* norm_sparse_create(int device, int G, const int32_t* stat_rows, int64_t n_stat) {
-    norm_check_create(G, stat_rows, n_stat);
-    return new NormSparse(device, G, stat_rows, n_stat);
-}
-void norm_sparse_destroy(NormSparse* h) { delete h; }
-void norm_sparse_begin_batch(NormSparse* h, int64_t n, const double* size_factors, int64_t nnz) {
-    h->begin_batch(n, size_factors, nnz);
-}
-void norm_sparse_add_block(NormSparse* h, int64_t m, const int64_t* indptr, const int32_t* indices, const double* data,
-                           int64_t nnz) {
-    h->add_block(m, indptr, indices, data, nnz);
-}
-void norm_sparse_run(NormSparse* h, double min_mean, int log, double pseudo_count, double* const* outs, double* sf_out,
-                     double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out) {
-    h->run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out, zero_out);
-}
-void norm_sparse_stage_ms(const NormSparse* h, double* out5) { h->stage_ms(out5); }
-
 }  // namespace bmx
+
+/* ---------------------------------------------------------------- bmx_norm_*, bmx_norm_sparse_* ----------------- */
+struct bmx_norm final : bmx::Norm {
+    using Norm::Norm;
+};
+struct bmx_norm_sparse final : bmx::NormSparse {
+    using NormSparse::NormSparse;
+};
+
+extern "C" {
+
+int32_t bmx_norm_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat, bmx_norm_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        bmx::norm_check_create(G, stat_rows, n_stat);
+        *out = new bmx_norm(device, G, stat_rows, n_stat);
+    });
+}
+
+void bmx_norm_destroy(bmx_norm_t* h) { delete h; }
+
+int32_t bmx_norm_check_create(int32_t G, const int32_t* stat_rows, int64_t n_stat) {
+    return bmx::guarded([&] { bmx::norm_check_create(G, stat_rows, n_stat); });
+}
+
+int32_t bmx_norm_check_batch(int64_t n, const double* size_factors) {
+    return bmx::guarded([&] { bmx::norm_check_batch(n, size_factors); });
+}
+
+int32_t bmx_norm_check_run(double min_mean, int32_t log, double pseudo_count) {
+    return bmx::guarded([&] { bmx::norm_check_run(min_mean, log, pseudo_count); });
+}
+
+int32_t bmx_norm_begin_batch(bmx_norm_t* h, int64_t n, const double* size_factors) {
+    return bmx::guarded([&] { bmx::live(h).begin_batch(n, size_factors); });
+}
+
+int32_t bmx_norm_add_block(bmx_norm_t* h, const double* x_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(h).add_block(x_block, n_block); });
+}
+
+int32_t bmx_norm_run(bmx_norm_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs, double* sf_out,
+                     double* ave_out, double* ratios_out, int32_t* smallest_out) {
+    return bmx::guarded([&] {
+        bmx::live(h).run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out);
+    });
+}
+
+int32_t bmx_norm_stage_ms(const bmx_norm_t* h, double* out5) {
+    return bmx::guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        h->stage_ms(out5);
+    });
+}
+
+int32_t bmx_norm_sparse_create(int32_t device, int32_t G, const int32_t* stat_rows, int64_t n_stat,
+                               bmx_norm_sparse_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        bmx::norm_check_create(G, stat_rows, n_stat);
+        *out = new bmx_norm_sparse(device, G, stat_rows, n_stat);
+    });
+}
+
+void bmx_norm_sparse_destroy(bmx_norm_sparse_t* h) { delete h; }
+
+int32_t bmx_norm_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
+                                    const int32_t* indices, const double* data, int64_t nnz) {
+    return bmx::guarded([&] { bmx::norm_check_sparse_block(n, filled, n_block, indptr, indices, data, nnz); });
+}
+
+int32_t bmx_norm_sparse_begin_batch(bmx_norm_sparse_t* h, int64_t n, const double* size_factors, int64_t nnz) {
+    return bmx::guarded([&] { bmx::live(h).begin_batch(n, size_factors, nnz); });
+}
+
+int32_t bmx_norm_sparse_add_block(bmx_norm_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                  const double* data, int64_t nnz) {
+    return bmx::guarded([&] { bmx::live(h).add_block(n_block, indptr, indices, data, nnz); });
+}
+
+int32_t bmx_norm_sparse_run(bmx_norm_sparse_t* h, double min_mean, int32_t log, double pseudo_count, double* const* outs,
+                            double* sf_out, double* ave_out, double* ratios_out, int32_t* smallest_out, double* zero_out) {
+    return bmx::guarded([&] {
+        bmx::live(h).run(min_mean, log, pseudo_count, outs, sf_out, ave_out, ratios_out, smallest_out, zero_out);
+    });
+}
+
+int32_t bmx_norm_sparse_stage_ms(const bmx_norm_sparse_t* h, double* out5) {
+    return bmx::guarded([&] {
+        if (!h || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        h->stage_ms(out5);
+    });
+}
+
+}  // extern "C"

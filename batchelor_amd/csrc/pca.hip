@@ -423,7 +423,8 @@ class Pca : ResidentBatches<PcaBatch> {
     // multiBatchPCA: centres [G], rotation [G x d] column-major, sdev [d] (singular values of the scaled matrix).
     // Chebyshev-filtered subspace iteration on a block of L = 64 (d <= 56) or 128 (d <= 120) vectors until the Ritz
     // residuals max_j |M x_j - theta_j x_j| / theta_1 of the d wanted pairs are <= tol (tol > 0), at most max_applies
-    // applications of M; tol <= 0: exactly max_applies plain subspace steps (the fixed-count form).
+    // applications of M (throws if they do not reach it, after the results have been written); tol <= 0: exactly
+    // max_applies plain subspace steps (the fixed-count form).
     void fit(int d, double tol, int max_applies, double* centers, double* rotation, double* sdev, int* applies_used,
              double* resid_out) {
         CacheScope scope(&cache_);
@@ -758,15 +759,61 @@ class Pca : ResidentBatches<PcaBatch> {
     bool fitted_ = false;
 };
 
-Pca* pca_create(int device, int G) { return new Pca(device, G); }
-void pca_destroy(Pca* p) { delete p; }
-void pca_add_batch(Pca* p, const double* x, int64_t n, double weight, int cos_norm) { p->add_batch(x, n, weight, cos_norm != 0); }
-void pca_begin_batch(Pca* p, int64_t n, double weight, int cos_norm) { p->begin_batch(n, weight, cos_norm != 0); }
-void pca_add_block(Pca* p, const double* x_block, int64_t m) { p->add_block(x_block, m); }
-void pca_fit(Pca* p, int d, double tol, int max_applies, double* centers, double* rotation, double* sdev, int* applies_used,
-             double* resid) {
-    p->fit(d, tol, max_applies, centers, rotation, sdev, applies_used, resid);
-}
-void pca_project(Pca* p, int b, double* out) { p->project(b, out); }
-
 }  // namespace bmx
+
+/* ---------------------------------------------------------------- bmx_pca_* ------------------------------------- */
+struct bmx_pca final : bmx::Pca {
+    using Pca::Pca;
+};
+
+extern "C" {
+
+int32_t bmx_pca_create(int32_t device, int32_t G, bmx_pca_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (G < 1) throw bmx::Error(BMX_ERR_ARG, "the PCA needs at least one gene");
+        *out = new bmx_pca(device, G);
+    });
+}
+
+void bmx_pca_destroy(bmx_pca_t* p) { delete p; }
+
+int32_t bmx_pca_add_batch(bmx_pca_t* p, const double* x, int64_t n, double weight, int32_t cos_norm) {
+    return bmx::guarded([&] { bmx::live(p).add_batch(x, n, weight, cos_norm != 0); });
+}
+
+int32_t bmx_pca_begin_batch(bmx_pca_t* p, int64_t n, double weight, int32_t cos_norm) {
+    return bmx::guarded([&] { bmx::live(p).begin_batch(n, weight, cos_norm != 0); });
+}
+
+int32_t bmx_pca_add_block(bmx_pca_t* p, const double* x_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(p).add_block(x_block, n_block); });
+}
+
+int32_t bmx_pca_fit(bmx_pca_t* p, int32_t d, int32_t iters, double* centers, double* rotation, double* sdev) {
+    return bmx::guarded([&] { bmx::live(p).fit(d, 0.0, iters, centers, rotation, sdev, nullptr, nullptr); });
+}
+
+int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, double* centers, double* rotation,
+                        double* sdev, int32_t* iters_used, double* residual) {
+    return bmx::guarded([&] {
+        if (!(tol > 0.0)) throw bmx::Error(BMX_ERR_ARG, "the PCA tolerance must be positive");
+        int used = 0;
+        double res = 0.0;
+        try {
+            bmx::live(p).fit(d, tol, max_iters, centers, rotation, sdev, &used, &res);
+        } catch (...) {
+            if (iters_used) *iters_used = used;
+            if (residual) *residual = res;
+            throw;
+        }
+        if (iters_used) *iters_used = used;
+        if (residual) *residual = res;
+    });
+}
+
+int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out) {
+    return bmx::guarded([&] { bmx::live(p).project(batch, out); });
+}
+
+}  // extern "C"

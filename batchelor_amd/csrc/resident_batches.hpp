@@ -1,11 +1,12 @@
-// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear, Norm) have in common: the argument checks
-// of a batch, the bookkeeping of a batch that arrives in column blocks, the store that owns the cache, the copy stream and
-// the batches, the event-pair stage timer and the blocked pass that writes every cell.  The checks and the bookkeeping
-// make no HIP call.
+// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear, Norm, NormSparse, Delta) have in common:
+// the guard their C entry points go through, the argument checks of a batch, the bookkeeping of a batch that arrives in
+// column blocks, the event-pair stage timer, the store that owns the cache, the copy stream, the batches and the stage
+// times, and the blocked pass that writes every cell.  The checks and the bookkeeping make no HIP call.
 #pragma once
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -18,6 +19,16 @@ namespace bmx {
 
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// ---- the extern "C" boundary (abi.hip).  Nothing throws across it: fn runs, an exception becomes its status code and
+// the thread's bmx_last_error() text.
+int guarded(const std::function<void()>& fn);
+// the handle an entry point was given
+template <class H>
+H& live(H* h) {
+    if (!h) throw Error(BMX_ERR_ARG, "null handle");
+    return *h;
 }
 
 // ---- argument checks, without a device (throw Error(BMX_ERR_ARG))
@@ -53,6 +64,44 @@ inline void check_block(const BlockLedger* open, const void* x_block, int64_t m,
     if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
 }
 
+// ---- device time by stage, from pairs of events
+class SpanTimer {
+  public:
+    ~SpanTimer() {
+        for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+    }
+    // a timing event recorded on `stream` now
+    int mark(hipStream_t stream) {
+        if (next_ == (int)events_.size()) {
+            hipEvent_t e = nullptr;
+            BMX_HIP(hipEventCreate(&e));
+            events_.push_back(e);
+        }
+        BMX_HIP(hipEventRecord(events_[(size_t)next_], stream));
+        return next_++;
+    }
+    hipEvent_t event(int i) const { return events_[(size_t)i]; }
+    void span(int stage, int a, int b) { spans_.push_back({stage, a, b}); }
+    // the spans since the last call go into ms[stage] and the events are free again (the streams marked are idle)
+    void collect(double* ms) {
+        for (const Span& s : spans_) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, events_[(size_t)s.a], events_[(size_t)s.b]) == hipSuccess) ms[s.stage] += (double)t;
+            (void)hipGetLastError();
+        }
+        spans_.clear();
+        next_ = 0;
+    }
+
+  private:
+    struct Span {
+        int stage, a, b;
+    };
+    std::vector<hipEvent_t> events_;
+    int next_ = 0;
+    std::vector<Span> spans_;
+};
+
 // ---- the store.  Batch: a struct derived from ResidentBatch with the handle's own per-batch buffers -- or, for a handle
 // that keeps its cells in another form (the sparse counts of multiBatchNorm), one derived from BlockLedger alone that
 // says `dense_x = false`: begin() then reserves nothing itself and add() is not for it.
@@ -70,6 +119,8 @@ class ResidentBatches {
     }
     ResidentBatches(const ResidentBatches&) = delete;
     ResidentBatches& operator=(const ResidentBatches&) = delete;
+    // milliseconds by stage since the handle was made (the handle says which five)
+    void stage_ms(double* out5) const { std::memcpy(out5, ms_, sizeof(ms_)); }
 
   protected:
     // Destruction.  A DevBuf hands its block to the cache DevBlockCache::current() names at that moment, so two things
@@ -128,44 +179,8 @@ class ResidentBatches {
     const char* begin_entry_;
     hipStream_t stream_ = nullptr;  // copies (and, in Pca and Cluster, the kernels)
     std::vector<std::unique_ptr<Batch>> batches_;
-};
-
-// ---- device time by stage, from pairs of events
-class SpanTimer {
-  public:
-    ~SpanTimer() {
-        for (hipEvent_t e : events_) (void)hipEventDestroy(e);
-    }
-    // a timing event recorded on `stream` now
-    int mark(hipStream_t stream) {
-        if (next_ == (int)events_.size()) {
-            hipEvent_t e = nullptr;
-            BMX_HIP(hipEventCreate(&e));
-            events_.push_back(e);
-        }
-        BMX_HIP(hipEventRecord(events_[(size_t)next_], stream));
-        return next_++;
-    }
-    hipEvent_t event(int i) const { return events_[(size_t)i]; }
-    void span(int stage, int a, int b) { spans_.push_back({stage, a, b}); }
-    // the spans since the last call go into ms[stage] and the events are free again (the streams marked are idle)
-    void collect(double* ms) {
-        for (const Span& s : spans_) {
-            float t = 0.0f;
-            if (hipEventElapsedTime(&t, events_[(size_t)s.a], events_[(size_t)s.b]) == hipSuccess) ms[s.stage] += (double)t;
-            (void)hipGetLastError();
-        }
-        spans_.clear();
-        next_ = 0;
-    }
-
-  private:
-    struct Span {
-        int stage, a, b;
-    };
-    std::vector<hipEvent_t> events_;
-    int next_ = 0;
-    std::vector<Span> spans_;
+    SpanTimer timer_;                 // the stages' event pairs, collected into ms_
+    double ms_[5] = {0, 0, 0, 0, 0};  // what stage_ms reports (Pca reports none and leaves both alone)
 };
 
 // ---- a pass that writes every cell of every batch (Linear, Norm), in blocks of at most `per` cells through the two

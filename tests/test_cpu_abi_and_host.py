@@ -129,3 +129,53 @@ def test_product_divide_into_batches_matches_oracle(oracle):
     pairings = [(rng.integers(1, 11, 20), np.arange(11, 31))]
     out = _reindex_pairings(pairings, S)
     assert np.array_equal(S[out[0][0] - 1], pairings[0][0]) and np.array_equal(S[out[0][1] - 1], pairings[0][1])
+
+
+# ---------------------------------------------------------------- the resident-batch handles refuse a null handle
+HANDLE_TYPES = ("pca", "cluster", "linear", "norm", "norm_sparse", "delta")
+
+
+def _handle_entry_points():
+    """(return type, name, parameter types) of every function of the public header whose first parameter is one of the
+    six resident-batch handle types."""
+    header = open(os.path.join(ROOT, "include", "batchelor_mi355x.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    first = re.compile(r"^(const )?bmx_(%s)_t\*$" % "|".join(HANDLE_TYPES))
+    out = []
+    for ret, name, params in re.findall(r"\b(int32_t|void)\s+(bmx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
+        types = [" ".join(p.split()).rsplit(" ", 1)[0].replace(" *", "*") for p in params.split(",")]
+        if first.match(types[0]):
+            out.append((ret, name, types))
+    return out
+
+
+def test_every_handle_entry_point_refuses_a_null_handle(built):
+    """Null handle, null pointers, 1 for every scalar: no entry point of the six handles touches the handle before it
+    has looked at it.  bmx_*_destroy(NULL) is a no-op; the others answer BMX_ERR_ARG and say "null handle", except that
+    the *_stage_ms say "null argument" (they check the handle and the output together) and bmx_cluster_add_batch says
+    "the batch is missing" (it checks the batch first)."""
+    lib = built.lib()
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+    entries = _handle_entry_points()
+    destroys = [e for e in entries if e[0] == "void"]
+    others = [e for e in entries if e[0] != "void"]
+    # (the header declares 37 such functions: 6 destroys, and 31 that return a status, 5 of them *_stage_ms)
+    assert sorted(n for _, n, _ in destroys) == sorted("bmx_%s_destroy" % t for t in HANDLE_TYPES)
+    assert len(others) == 31 and sum(n.endswith("_stage_ms") for _, n, _ in others) == 5
+    assert "bmx_cluster_add_batch" in [n for _, n, _ in others]
+    for ret, name, types in entries:
+        fn = getattr(lib, name)
+        args = [None if t.endswith("*") else scalars[t](1) for t in types]
+        saved = fn.argtypes, fn.restype
+        fn.argtypes = [ctypes.c_void_p if t.endswith("*") else scalars[t] for t in types]
+        fn.restype = None if ret == "void" else ctypes.c_int32
+        try:
+            rc = fn(*args)
+        finally:
+            fn.argtypes, fn.restype = saved
+        if ret == "void":
+            continue
+        want = ("null argument" if name.endswith("_stage_ms") else
+                "the batch is missing" if name == "bmx_cluster_add_batch" else "null handle")
+        assert rc == -6, (name, rc)
+        assert lib.bmx_last_error().decode() == want, (name, lib.bmx_last_error().decode())

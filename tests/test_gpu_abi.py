@@ -224,3 +224,155 @@ def test_restrict_with_repeats_under_variance_adjustment(oracle):
     assert np.array_equal(out.merge_info.pairs[0][1], ref.merge_info.pairs[0][1])
     close = np.isclose(out.corrected, ref.corrected, rtol=1e-5, atol=1e-9).all(axis=1)
     assert close.mean() > 0.99, close.mean()
+
+
+# ---------------------------------------------------------------- the resident-batch handles: lifetime through raw ctypes
+LIFE_G, LIFE_N, LIFE_CUT = 64, 300, 256     # 300 cells = one whole 256-cell chunk plus a tail, handed over in two blocks
+
+
+def _vp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _ptrs(arrays):
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def _csc_block(X, c0, c1):
+    """columns [c0, c1) of the genes x cells matrix X as a CSC block: indptr relative to the block, rows, values"""
+    nz = (X[:, c0:c1] != 0).T                                   # [cells][genes]: row-major order = column by column
+    indptr = np.concatenate([[0], np.cumsum(nz.sum(axis=1))]).astype(np.int64)
+    return indptr, np.nonzero(nz)[1].astype(np.int32), np.ascontiguousarray(X[:, c0:c1].T[nz])
+
+
+class _Life:
+    """One handle type driven through the C entry points alone: create(G, out), begin(h, X), block(h, X, c0, c1),
+    result(h, batches) -> list of arrays, nbatches."""
+
+    def __init__(self, L, kind):
+        self.L, self.kind = L, kind
+        self.nbatches = 3 if kind in ("norm", "norm_sparse") else 1
+        self.destroy = getattr(L, "bmx_%s_destroy" % kind)
+
+    def create(self, G, out):
+        L, dev, G = self.L, ctypes.c_int32(0), ctypes.c_int32(G)
+        if self.kind == "cluster":
+            return L.bmx_cluster_create(dev, G, None, ctypes.c_int32(0), ctypes.byref(out))
+        if self.kind in ("norm", "norm_sparse"):
+            return getattr(L, "bmx_%s_create" % self.kind)(dev, G, None, ctypes.c_int64(-1), ctypes.byref(out))
+        return getattr(L, "bmx_%s_create" % self.kind)(dev, G, ctypes.byref(out))
+
+    def begin(self, h, X):
+        L, n = self.L, ctypes.c_int64(X.shape[1])
+        if self.kind == "pca":
+            return L.bmx_pca_begin_batch(h, n, ctypes.c_double(1.0), ctypes.c_int32(1))
+        if self.kind == "cluster":
+            self._clusters = (np.arange(X.shape[1]) % 3).astype(np.int32)
+            return L.bmx_cluster_begin_batch(h, n, _vp(self._clusters), ctypes.c_int32(3), None, ctypes.c_int64(-1),
+                                             ctypes.c_int32(1))
+        if self.kind == "linear":
+            return L.bmx_linear_begin_batch(h, n, None, ctypes.c_int64(-1))
+        if self.kind == "norm":
+            return L.bmx_norm_begin_batch(h, n, None)
+        if self.kind == "norm_sparse":
+            return L.bmx_norm_sparse_begin_batch(h, n, None, ctypes.c_int64(int(np.count_nonzero(X))))
+        return L.bmx_delta_begin_batch(h, n)
+
+    def block(self, h, X, c0, c1):
+        if self.kind == "norm_sparse":
+            indptr, rows, vals = _csc_block(X, c0, c1)
+            return self.L.bmx_norm_sparse_add_block(h, ctypes.c_int64(c1 - c0), _vp(indptr), _vp(rows), _vp(vals),
+                                                    ctypes.c_int64(vals.size))
+        blk = np.asfortranarray(X[:, c0:c1])
+        return getattr(self.L, "bmx_%s_add_block" % self.kind)(h, _vp(blk), ctypes.c_int64(c1 - c0))
+
+    def result(self, h, batches):
+        L, G = self.L, LIFE_G
+        if self.kind == "pca":
+            out = [np.zeros(G), np.zeros((G, 2), order="F"), np.zeros(2)]
+            _lib_check(L, L.bmx_pca_fit(h, ctypes.c_int32(2), ctypes.c_int32(2), _vp(out[0]), _vp(out[1]), _vp(out[2])))
+            return out
+        if self.kind == "cluster":
+            out = [np.zeros((G, 3), order="F")]
+            _lib_check(L, L.bmx_cluster_centroids(h, ctypes.c_int32(0), _vp(out[0])))
+            return out
+        if self.kind == "linear":
+            out = [np.zeros(X.shape, order="F") for X in batches]
+            _lib_check(L, L.bmx_linear_fetch(h, _ptrs(out)))
+            return out
+        if self.kind in ("norm", "norm_sparse"):
+            B, N = len(batches), sum(X.shape[1] for X in batches)
+            sparse = self.kind == "norm_sparse"
+            outs = [np.zeros(int(np.count_nonzero(X))) if sparse else np.zeros(X.shape, order="F") for X in batches]
+            sf, ave, ratios = np.zeros(N), np.zeros((G, B), order="F"), np.zeros((B, B))
+            smallest, zero = ctypes.c_int32(0), ctypes.c_double(0.0)
+            args = [h, ctypes.c_double(1.0), ctypes.c_int32(1), ctypes.c_double(1.0), _ptrs(outs), _vp(sf), _vp(ave),
+                    _vp(ratios), ctypes.byref(smallest)]
+            if sparse:
+                _lib_check(L, L.bmx_norm_sparse_run(*args, ctypes.byref(zero)))
+            else:
+                _lib_check(L, L.bmx_norm_run(*args))
+            return outs + [sf, ave, ratios, np.asarray([smallest.value]), np.asarray([zero.value])]
+        left = np.arange(1, 9, dtype=np.int32)
+        right = np.arange(LIFE_N, LIFE_N - 8, -1, dtype=np.int32)
+        npairs = np.asarray([8], dtype=np.int64)
+        out = [np.zeros(G), np.zeros(G)]
+        _lib_check(L, L.bmx_delta_run(h, ctypes.c_int32(0), None, ctypes.c_int32(0), ctypes.c_int32(1), _ptrs([left]),
+                                      _ptrs([right]), _vp(npairs), _vp(out[0]), _vp(out[1])))
+        return out
+
+
+def _lib_check(L, rc):
+    assert rc == 0, L.bmx_last_error().decode()
+
+
+@pytest.mark.parametrize("kind", ["pca", "cluster", "linear", "norm", "norm_sparse", "delta"])
+def test_handle_lifetime_through_the_c_entry_points(kind):
+    """Ownership of a resident-batch handle as a C caller sees it: create / destroy with nothing uploaded, a refused
+    create, a handle destroyed between two blocks of a batch (a caller whose own code raised there), and afterwards the
+    device still answers: bmx_linear_fetch returns the upload bit for bit, every other handle's cheapest result equals
+    a second, identical handle's bit for bit."""
+    from batchelor_amd import _lib
+    L = _lib.lib()
+    life = _Life(L, kind)
+    rng = np.random.default_rng(20250314)
+    batches = [np.asfortranarray(rng.poisson(2.0, (LIFE_G, LIFE_N)).astype(np.float64)) for _ in range(life.nbatches)]
+    # 1. create and destroy, nothing uploaded
+    for _ in range(3):
+        h = ctypes.c_void_p()
+        _lib_check(L, life.create(LIFE_G, h))
+        assert h.value
+        life.destroy(h)
+    # 2. a refused create leaves *out null, and destroying that null is harmless
+    h = ctypes.c_void_p()
+    assert life.create(0, h) != 0 and not h.value
+    life.destroy(h)
+    # 3. an abandoned batch: one block of two has arrived (its upload is queued) when the handle goes
+    h = ctypes.c_void_p()
+    _lib_check(L, life.create(LIFE_G, h))
+    _lib_check(L, life.begin(h, batches[0]))
+    _lib_check(L, life.block(h, batches[0], 0, LIFE_CUT))
+    life.destroy(h)
+    # 4. the device still answers
+    results = []
+    for _ in range(2):
+        h = ctypes.c_void_p()
+        _lib_check(L, life.create(LIFE_G, h))
+        try:
+            for X in batches:
+                _lib_check(L, life.begin(h, X))
+                _lib_check(L, life.block(h, X, 0, LIFE_CUT))
+                _lib_check(L, life.block(h, X, LIFE_CUT, LIFE_N))
+            results.append(life.result(h, batches))
+        finally:
+            life.destroy(h)
+        if kind == "linear":
+            break
+    if kind == "linear":
+        for got, X in zip(results[0], batches):
+            assert np.array_equal(got, X)
+    else:
+        assert len(results[0]) == len(results[1])
+        for a, b in zip(*results):
+            assert np.array_equal(a, b, equal_nan=True)
+        assert all(np.isfinite(a).all() for a in results[0])
