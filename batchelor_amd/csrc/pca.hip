@@ -16,6 +16,10 @@
 // Both products run on the FP64 matrix cores (v_mfma_f64_16x16x4_f64): 64 x 64 output tiles per workgroup, operands
 // brought in by whole-row 16-byte loads one K step ahead (registers) and staged in the LDS with pitches that keep the
 // 32-lane fragment reads conflict-free.
+//
+// subset.row / get.all.genes / get.variance (R/multiBatchPCA.R:401-432): the handle holds the subset rows only; PcaGenes
+// (bmx_pca_genes_*) borrows it once fitted and streams the other rows through gemm_tn64_sums for their rotation rows and
+// centres, keeping none of them, and sums var.total over the resident rows.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -317,6 +321,163 @@ __global__ __launch_bounds__(256) void resid_partial(const double* __restrict__ 
     for (int j = threadIdx.x; j < L; j += 256) part[(int64_t)blockIdx.x * L + j] = (sm[0][j] + sm[1][j]) + (sm[2][j] + sm[3][j]);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The streaming pass over the genes outside subset.row (PcaGenes below): one read of a block X [n][G] of leftover rows
+// (cells x leftover genes, row-major = genes x cells column-major) gives both
+//     Apart[h][split][g][j] = sum_{r in split} X[r][g] * (rs[r] * Z_h[r][j])     h < NH halves of 64 subspace columns
+//     Spart[split][g]       = sum_{r in split} rs[r] * X[r][g]                   (the gene sums, for the centres)
+// gemm_tn64's tiling, operand layout and LDS pitch with NH Z tiles a step; the gene sums are kept by the lanes that
+// fetch X (each owns fixed genes and a fixed stride of cells) and reduced in a fixed order at the end.  Z_h [n][64] is at
+// Z + h * zhalf.  grid (ceil(G / 64), nsplit); no atomics: the parts are summed by reduce_parts.
+// ---------------------------------------------------------------------------------------------------
+template <int NH>
+__global__ __launch_bounds__(256) void gemm_tn64_sums(const double* __restrict__ X, int64_t n, int G,
+                                                      const double* __restrict__ Z, int64_t zhalf,
+                                                      const double* __restrict__ rs, int64_t rows_per_split,
+                                                      double* __restrict__ Apart, double* __restrict__ Spart) {
+    constexpr int P = 64 + 16;  // as gemm_tn64
+    __shared__ __attribute__((aligned(16))) double xs[KC * P];
+    __shared__ __attribute__((aligned(16))) double zs[NH][KC * P];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g0 = blockIdx.x * 64;
+    const int64_t rbeg = (int64_t)blockIdx.y * rows_per_split, rend = min(n, rbeg + rows_per_split);
+    d4 acc[NH][4];
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[h][t] = d4{0.0, 0.0, 0.0, 0.0};
+    auto multiply = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int kk = 0; kk < KC / 4; ++kk) {
+            const double a = xs[(4 * kk + (lane >> 4)) * P + 16 * w + (lane & 15)];  // A[row = gene][k = cell]
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const double b = zs[h][(4 * kk + (lane >> 4)) * P + 16 * t + (lane & 15)];  // B[k = cell][col = j]
+                    acc[h][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[h][t], 0, 0, 0);
+                }
+        }
+    };
+    int sum_rows;  // how many lanes hold a partial sum of each gene
+    if (g0 + 64 <= G) {
+        const int lr = tid >> 5, lg = (tid & 31) * 2;
+        d2u px[4], pz[NH][4];
+        d2u gs = d2u{0.0, 0.0};
+        auto fetch = [&](const int64_t r0) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t r = r0 + lr + 8 * i;
+                if (r < rend) {
+                    const double f = rs ? rs[r] : 1.0;
+                    px[i] = *reinterpret_cast<const d2u*>(X + r * G + g0 + lg);
+                    gs[0] += f * px[i][0];
+                    gs[1] += f * px[i][1];
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) {
+                        const d2u z = *reinterpret_cast<const d2u*>(Z + h * zhalf + r * 64 + lg);
+                        pz[h][i] = d2u{f * z[0], f * z[1]};
+                    }
+                } else {
+                    px[i] = d2u{0.0, 0.0};
+#pragma unroll
+                    for (int h = 0; h < NH; ++h) pz[h][i] = d2u{0.0, 0.0};
+                }
+            }
+        };
+        if (rbeg < rend) fetch(rbeg);
+        for (int64_t r0 = rbeg; r0 < rend; r0 += KC) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                *reinterpret_cast<d2u*>(&xs[(lr + 8 * i) * P + lg]) = px[i];
+#pragma unroll
+                for (int h = 0; h < NH; ++h) *reinterpret_cast<d2u*>(&zs[h][(lr + 8 * i) * P + lg]) = pz[h][i];
+            }
+            __syncthreads();
+            if (r0 + KC < rend) fetch(r0 + KC);
+            multiply();
+            __syncthreads();
+        }
+        *reinterpret_cast<d2u*>(&xs[lr * P + lg]) = gs;
+        sum_rows = 8;
+    } else {  // the ragged last gene tile, element by element
+        const int lr = tid >> 3, seg = (tid & 7) * 8;  // 32 rows x 8 segments of 8 doubles
+        double gs[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gs[e] = 0.0;
+        for (int64_t r0 = rbeg; r0 < rend; r0 += KC) {
+            const int64_t r = r0 + lr;
+            const double f = (r < rend && rs) ? rs[r] : 1.0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int g = g0 + seg + e;
+                const double x = (r < rend && g < G) ? X[r * G + g] : 0.0;
+                xs[lr * P + seg + e] = x;
+                gs[e] += f * x;
+#pragma unroll
+                for (int h = 0; h < NH; ++h) zs[h][lr * P + seg + e] = r < rend ? f * Z[h * zhalf + r * 64 + seg + e] : 0.0;
+            }
+            __syncthreads();
+            multiply();
+            __syncthreads();
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xs[lr * P + seg + e] = gs[e];
+        sum_rows = 32;
+    }
+    __syncthreads();
+    if (tid < 64 && g0 + tid < G) {
+        double s = 0.0;
+        for (int i = 0; i < sum_rows; ++i) s += xs[i * P + tid];
+        Spart[(int64_t)blockIdx.y * G + g0 + tid] = s;
+    }
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        double* out = Apart + ((int64_t)h * gridDim.y + blockIdx.y) * G * 64;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = 16 * t + (lane & 15);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int g = g0 + 16 * w + (lane >> 4) + 4 * reg;
+                if (g < G) out[(int64_t)g * 64 + j] = acc[h][t][reg];
+            }
+        }
+    }
+}
+
+// rotation rows of the leftover genes, column-major [d][G]:  out[j][g] = (A_h[g][j % 64] - mu[g] * t[j]) / s2[j],  h = j / 64
+__global__ void genes_rotation(const double* __restrict__ A, const double* __restrict__ mu, const double* __restrict__ t,
+                               const double* __restrict__ s2, int G, int d, double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)G * d) return;
+    const int j = (int)(e / G), g = (int)(e % G);
+    out[e] = (A[((int64_t)(j >> 6) * G + g) * 64 + (j & 63)] - mu[g] * t[j]) / s2[j];
+}
+
+// part[block] = sum over the block's cells c and all genes g of (rs[c] X[c][g] - mu[g])^2: one wave a cell, four cells in
+// flight a workgroup, deterministic
+__global__ __launch_bounds__(256) void centred_sq_partial(const double* __restrict__ X, const double* __restrict__ rs,
+                                                          const double* __restrict__ mu, int64_t n, int G,
+                                                          int64_t cells_per_block, double* __restrict__ part) {
+    __shared__ double sm[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t c0 = (int64_t)blockIdx.x * cells_per_block, c1 = min(n, c0 + cells_per_block);
+    double s = 0.0;
+    for (int64_t c = c0 + w; c < c1; c += 4) {
+        const double f = rs ? rs[c] : 1.0;
+        const double* col = X + c * G;
+        for (int g = lane; g < G; g += 64) {
+            const double v = f * col[g] - mu[g];
+            s += v * v;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) sm[w] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
 // ---- small dense helpers on the host (L x L, L = 64 or 128) --------------------------------------------------------
 // upper-triangular R with R^T R = S (S symmetric positive definite, row-major); returns false if not
 bool cholesky_upper(std::vector<double>& S, int n) {
@@ -393,6 +554,8 @@ struct PcaBatch : ResidentBatch {
 };
 
 class Pca : ResidentBatches<PcaBatch> {
+    friend class PcaGenes;  // the streaming pass over the genes outside subset.row borrows a fitted Pca (below)
+
   public:
     Pca(int device, int G) : ResidentBatches(device, G, "bmx_pca_begin_batch") {}
     ~Pca() { retire(); }
@@ -406,6 +569,7 @@ class Pca : ResidentBatches<PcaBatch> {
             if (cos_norm) b.inv.reserve((size_t)n);
         });
         fitted_ = false;
+        ++generation_;
     }
     void add_block(const double* x_block, int64_t m) {
         add(x_block, m, [&](PcaBatch& b, double* p) {
@@ -429,6 +593,7 @@ class Pca : ResidentBatches<PcaBatch> {
              double* resid_out) {
         CacheScope scope(&cache_);
         BMX_HIP(hipSetDevice(device_));
+        ++generation_;
         if (batches_.empty()) throw Error(BMX_ERR_ARG, "at least one batch must be specified");
         if (batches_.back()->filled != batches_.back()->n)
             throw Error(BMX_ERR_ARG, "the last batch has not received all its cells");
@@ -486,7 +651,9 @@ class Pca : ResidentBatches<PcaBatch> {
             BMX_HIP(hipStreamSynchronize(stream_));
         }
         orthonormalise(Y, Q);
-        std::vector<double> theta(L, 0.0), V;
+        std::vector<double>& theta = theta_;  // kept: the eigenvalues s^2 the leftover rotation is divided by
+        theta.assign(L, 0.0);
+        std::vector<double> V;
         std::vector<int> order(L);
         int applies = 0;
         double resid = std::numeric_limits<double>::infinity();
@@ -755,8 +922,219 @@ class Pca : ResidentBatches<PcaBatch> {
     }
 
     int d_ = 0, L_ = PL;
+    std::vector<double> theta_;          // [L] Ritz values of the last fit, descending
+    unsigned long long generation_ = 0;  // counts begin_batch and fit: what a PcaGenes was made for
     DevBuf<double> mu_, q_, y_, xr_, yr_, w_, qt_, ut_, z_, zt_, part_, small_;
     bool fitted_ = false;
+};
+
+// ---------------------------------------------------------------------------------------------------
+// The genes outside subset.row (R/multiBatchPCA.R:401-414, .make_pca_metadata with get.all.genes): their centres mu_L and
+// rotation rows  U_L = L_scaled V diag(1 / s),  V = S_scaled^T U diag(1 / s),  which with coef_b = w_b / n_b is
+//     U_L[g][j] = ( sum_b coef_b sum_c scale_c x_gc Z_b[c][j]  -  mu_L[g] sum_b coef_b sum_c Z_b[c][j] ) / s_j^2,
+// Z_b = C_b^T U the batch's projections.  The leftover rows of every batch stream through in column blocks and are not
+// kept: a block lands in one of two device buffers on the copy stream while the kernels of the block before it run on the
+// other.  The projections of a block's cells come from the RESIDENT subset rows of the borrowed, fitted Pca (gemm_nt64 on
+// its ut_ / muU, as Pca::project), so nothing but the leftover rows crosses the link.  scale is the batch's inv: the norms
+// over the subset rows (R/fastMNN.R:348-351).  The Pca must outlive this handle; one that was re-fitted or given another
+// batch since makes every later call an error.
+// ---------------------------------------------------------------------------------------------------
+class PcaGenes {
+  public:
+    PcaGenes(int GL, Pca* pca) : pca_(*pca), made_for_(pca->generation_), GL_(GL), device_(pca->device_) {
+        if (!pca_.fitted_) throw Error(BMX_ERR_ARG, "bmx_pca_fit has not been run");
+        nh_ = cdiv(pca_.d_, PL);
+        for (auto& bp : pca_.batches_) wsum_ += bp->weight;
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        BMX_HIP(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking));
+        BMX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+        for (int i = 0; i < 2; ++i) {
+            BMX_HIP(hipEventCreateWithFlags(&landed_[i], hipEventDisableTiming));
+            BMX_HIP(hipEventCreateWithFlags(&used_[i], hipEventDisableTiming));
+        }
+        const size_t GLn = (size_t)std::max(GL_, 1);
+        acc_.reserve((size_t)nh_ * GLn * PL);
+        sums_.reserve(GLn);
+        mu_.reserve(GLn);
+        tsum_.reserve((size_t)nh_ * PL + 2 * (size_t)PL * 2);
+        BMX_HIP(hipMemsetAsync(acc_.p, 0, (size_t)nh_ * GLn * PL * sizeof(double), stream_));
+        BMX_HIP(hipMemsetAsync(mu_.p, 0, GLn * sizeof(double), stream_));
+        BMX_HIP(hipMemsetAsync(tsum_.p, 0, (size_t)nh_ * PL * sizeof(double), stream_));
+    }
+    PcaGenes(const PcaGenes&) = delete;
+    PcaGenes& operator=(const PcaGenes&) = delete;
+    ~PcaGenes() {
+        (void)hipSetDevice(device_);
+        for (hipStream_t s : {copy_, stream_})
+            if (s) {
+                (void)hipStreamSynchronize(s);
+                (void)hipStreamDestroy(s);
+            }
+        for (int i = 0; i < 2; ++i) {
+            if (landed_[i]) (void)hipEventDestroy(landed_[i]);
+            if (used_[i]) (void)hipEventDestroy(used_[i]);
+        }
+        DevBlockCache::current() = &cache_;  // as ResidentBatches::retire(): the buffers below go back to cache_
+    }
+
+    // the leftover rows of batch b (0-based) follow in blocks; batches come 0, 1, ... in order
+    void begin_batch(int b) {
+        check_fresh();
+        check_begin(batch_ < 0 ? nullptr : &ledger_);
+        if (b < 0 || b >= pca_.nbatches()) throw Error(BMX_ERR_ARG, "batch index out of range");
+        if (b != batch_ + 1) throw Error(BMX_ERR_ARG, "the batches must be begun in order");
+        batch_ = b;
+        ledger_.n = pca_.ncells(b);
+        ledger_.filled = 0;
+    }
+    // the next m cells of the batch begun last: x_left_block is GL x m column-major host memory
+    void add_block(const double* x_left_block, int64_t m) {
+        check_fresh();
+        check_block(batch_ < 0 ? nullptr : &ledger_, x_left_block, m, "bmx_pca_genes_begin_batch");
+        if (GL_ < 1) throw Error(BMX_ERR_ARG, "the handle was made for no leftover genes");
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        PcaBatch& B = *pca_.batches_[(size_t)batch_];
+        const int64_t first = ledger_.filled;
+        const double coef = B.weight / (double)B.n;
+        const double* rs = B.cos_norm ? B.inv.p + first : nullptr;
+        const int G = GL_, GS = pca_.G_;
+        // ---- the shapes of this block's launches
+        const int gtiles = cdiv(G, 64);
+        int nsplit = (int)std::min<int64_t>(std::max<int64_t>(1, (int64_t)1024 / gtiles), std::max<int64_t>(1, m / 2048));
+        const int64_t per = round_up((m + nsplit - 1) / nsplit, KC);
+        nsplit = (int)((m + per - 1) / per);
+        const int nb = (int)std::min<int64_t>(4096, std::max<int64_t>(1, m / 256));
+        const int64_t rpb = (m + nb - 1) / nb;
+        if (m > cap_) {  // (a grown buffer may change hands: nothing of ours is in flight when it does)
+            BMX_HIP(hipStreamSynchronize(copy_));
+            BMX_HIP(hipStreamSynchronize(stream_));
+            for (int i = 0; i < 2; ++i) xl_[i].reserve((size_t)m * G);
+            z_.reserve((size_t)nh_ * m * PL);
+            cap_ = m;
+            busy_[0] = busy_[1] = false;
+        }
+        double* part = part_.reserve((size_t)nsplit * nh_ * G * PL + (size_t)nsplit * G + (size_t)nb * PL);
+        double* spart = part + (size_t)nsplit * nh_ * G * PL;
+        double* zpart = spart + (size_t)nsplit * G;
+        // ---- upload into the buffer the block before the last one has left
+        const int s = slot_;
+        slot_ ^= 1;
+        if (busy_[s]) BMX_HIP(hipStreamWaitEvent(copy_, used_[s], 0));
+        upload_pageable(xl_[s].p, x_left_block, (size_t)m * G * sizeof(double), copy_);
+        BMX_HIP(hipEventRecord(landed_[s], copy_));
+        ledger_.filled += m;
+        // ---- Z = C_b^T U for these cells, from the resident subset rows
+        const double* muU = pca_.small_.p + (size_t)3 * pca_.L_ * pca_.L_;
+        const int64_t zhalf = (int64_t)cap_ * PL;
+        for (int h = 0; h < nh_; ++h) {
+            hipLaunchKernelGGL(gemm_nt64, dim3((unsigned)cdiv(m, 64)), dim3(256), 0, stream_,
+                               (const double*)(B.x.p + first * GS), m, GS, (int64_t)GS,
+                               (const double*)(pca_.ut_.p + (size_t)h * PL * GS), (int64_t)GS, rs,
+                               (const double*)(muU + h * PL), z_.p + h * zhalf, (int64_t)PL);
+            hipLaunchKernelGGL(colsum64_partial, dim3(nb), dim3(256), 0, stream_, (const double*)(z_.p + h * zhalf),
+                               (const double*)nullptr, m, rpb, zpart);
+            hipLaunchKernelGGL(reduce_parts, dim3(1), dim3(64), 0, stream_, (const double*)zpart, nb, (int64_t)PL, coef, 1.0,
+                               tsum_.p + h * PL, PL, (int64_t)PL);
+            BMX_LAUNCH_CHECK();
+        }
+        // ---- one read of the leftover block: the product and the gene sums
+        BMX_HIP(hipStreamWaitEvent(stream_, landed_[s], 0));
+        if (nh_ == 1)
+            hipLaunchKernelGGL(gemm_tn64_sums<1>, dim3(gtiles, nsplit), dim3(256), 0, stream_, (const double*)xl_[s].p, m, G,
+                               (const double*)z_.p, zhalf, rs, per, part, spart);
+        else
+            hipLaunchKernelGGL(gemm_tn64_sums<2>, dim3(gtiles, nsplit), dim3(256), 0, stream_, (const double*)xl_[s].p, m, G,
+                               (const double*)z_.p, zhalf, rs, per, part, spart);
+        BMX_LAUNCH_CHECK();
+        BMX_HIP(hipEventRecord(used_[s], stream_));
+        busy_[s] = true;
+        for (int h = 0; h < nh_; ++h)
+            hipLaunchKernelGGL(reduce_parts, dim3((unsigned)cdiv((int64_t)G * PL, 256)), dim3(256), 0, stream_,
+                               (const double*)(part + (size_t)h * nsplit * G * PL), nsplit, (int64_t)G * PL, coef, 1.0,
+                               acc_.p + (size_t)h * G * PL, PL, (int64_t)PL);
+        hipLaunchKernelGGL(reduce_parts, dim3((unsigned)cdiv(G, 256)), dim3(256), 0, stream_, (const double*)spart, nsplit,
+                           (int64_t)G, 1.0, first == 0 ? 0.0 : 1.0, sums_.p, G, (int64_t)G);
+        BMX_LAUNCH_CHECK();
+        if (ledger_.complete()) {  // mu_L += (w_b / W) mean_b, as fit forms mu
+            hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)cdiv(G, 256)), dim3(256), 0, stream_, mu_.p, (const double*)sums_.p,
+                               (B.weight / wsum_) / (double)B.n, (int64_t)G);
+            BMX_LAUNCH_CHECK();
+        }
+    }
+    // centers_left [GL], rotation_left [GL x d] column-major; either may be null
+    void finish(double* centers_left, double* rotation_left) {
+        check_fresh();
+        if (batch_ != pca_.nbatches() - 1 || !ledger_.complete())
+            throw Error(BMX_ERR_ARG, "the last batch has not received all its cells");
+        if (GL_ < 1) return;
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        const int d = pca_.d_, G = GL_;
+        std::vector<double> s2((size_t)d);
+        for (int j = 0; j < d; ++j) {
+            const double sd = std::sqrt(std::max(0.0, pca_.theta_[(size_t)j]));  // the sdev fit reports
+            s2[(size_t)j] = sd * sd;
+        }
+        double* ds2 = tsum_.p + (size_t)nh_ * PL;
+        BMX_HIP(hipMemcpyAsync(ds2, s2.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream_));
+        double* rot = part_.reserve((size_t)G * d);  // (the stream orders this after the last block's reductions)
+        hipLaunchKernelGGL(genes_rotation, dim3((unsigned)cdiv((int64_t)G * d, 256)), dim3(256), 0, stream_,
+                           (const double*)acc_.p, (const double*)mu_.p, (const double*)tsum_.p, (const double*)ds2, G, d, rot);
+        BMX_LAUNCH_CHECK();
+        if (centers_left)
+            BMX_HIP(hipMemcpyAsync(centers_left, mu_.p, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        if (rotation_left)
+            BMX_HIP(hipMemcpyAsync(rotation_left, rot, (size_t)G * d * sizeof(double), hipMemcpyDeviceToHost, stream_));
+        BMX_HIP(hipStreamSynchronize(stream_));
+    }
+    // sum_b coef_b |C_b|_F^2 over the resident (subset) rows, in the centred form; the caller divides by the batches
+    void total_variance(double* var_total) {
+        check_fresh();
+        if (!var_total) throw Error(BMX_ERR_ARG, "null output pointer");
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        double total = 0.0;
+        for (auto& bp : pca_.batches_) {
+            PcaBatch& B = *bp;
+            const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, B.n / 64));
+            const int64_t cpb = (B.n + nb - 1) / nb;
+            BMX_HIP(hipStreamSynchronize(stream_));  // part_ may grow
+            double* part = part_.reserve((size_t)nb);
+            hipLaunchKernelGGL(centred_sq_partial, dim3(nb), dim3(256), 0, stream_, (const double*)B.x.p,
+                               (const double*)(B.cos_norm ? B.inv.p : nullptr), (const double*)pca_.mu_.p, B.n, pca_.G_, cpb,
+                               part);
+            BMX_LAUNCH_CHECK();
+            std::vector<double> h((size_t)nb);
+            BMX_HIP(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+            BMX_HIP(hipStreamSynchronize(stream_));
+            double s = 0.0;
+            for (double v : h) s += v;
+            total += (B.weight / (double)B.n) * s;
+        }
+        *var_total = total;
+    }
+
+  private:
+    void check_fresh() const {
+        if (pca_.generation_ != made_for_ || !pca_.fitted_)
+            throw Error(BMX_ERR_ARG, "the PCA was re-fitted or given a batch after bmx_pca_genes_create");
+    }
+
+    DevBlockCache cache_;  // first: destroyed after every DevBuf below (see ResidentBatches::retire)
+    Pca& pca_;
+    const unsigned long long made_for_;
+    int GL_, device_, nh_ = 1;
+    double wsum_ = 0.0;
+    hipStream_t copy_ = nullptr, stream_ = nullptr;  // uploads; kernels and downloads
+    hipEvent_t landed_[2] = {nullptr, nullptr}, used_[2] = {nullptr, nullptr};
+    bool busy_[2] = {false, false};
+    int slot_ = 0;
+    int batch_ = -1;      // the batch begun last
+    BlockLedger ledger_;  // its cells
+    int64_t cap_ = 0;     // cells xl_ and z_ hold
+    DevBuf<double> xl_[2], z_, part_, acc_, sums_, mu_, tsum_;
 };
 
 }  // namespace bmx
@@ -764,6 +1142,9 @@ class Pca : ResidentBatches<PcaBatch> {
 /* ---------------------------------------------------------------- bmx_pca_* ------------------------------------- */
 struct bmx_pca final : bmx::Pca {
     using Pca::Pca;
+};
+struct bmx_pca_genes final : bmx::PcaGenes {
+    using PcaGenes::PcaGenes;
 };
 
 extern "C" {
@@ -814,6 +1195,33 @@ int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, 
 
 int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out) {
     return bmx::guarded([&] { bmx::live(p).project(batch, out); });
+}
+
+/* ---------------------------------------------------------------- bmx_pca_genes_* ------------------------------- */
+int32_t bmx_pca_genes_create(int32_t n_genes_left, bmx_pca_t* fitted, bmx_pca_genes_t** out) {
+    return bmx::guarded([&] {
+        if (!out) throw bmx::Error(BMX_ERR_ARG, "null output pointer");
+        if (n_genes_left < 0) throw bmx::Error(BMX_ERR_ARG, "the number of leftover genes is negative");
+        *out = new bmx_pca_genes(n_genes_left, &bmx::live(fitted));
+    });
+}
+
+void bmx_pca_genes_destroy(bmx_pca_genes_t* h) { delete h; }
+
+int32_t bmx_pca_genes_begin_batch(bmx_pca_genes_t* h, int32_t batch) {
+    return bmx::guarded([&] { bmx::live(h).begin_batch(batch); });
+}
+
+int32_t bmx_pca_genes_add_block(bmx_pca_genes_t* h, const double* x_left_block, int64_t n_block) {
+    return bmx::guarded([&] { bmx::live(h).add_block(x_left_block, n_block); });
+}
+
+int32_t bmx_pca_genes_finish(bmx_pca_genes_t* h, double* centers_left, double* rotation_left) {
+    return bmx::guarded([&] { bmx::live(h).finish(centers_left, rotation_left); });
+}
+
+int32_t bmx_pca_genes_total_variance(bmx_pca_genes_t* h, double* var_total) {
+    return bmx::guarded([&] { bmx::live(h).total_variance(var_total); });
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .inputs import check_same_dim, divide_into_batches, reindex_pairings, unpack_batches
-from .multi_batch_pca import cosineNorm, multiBatchPCA, multiBatchPCA_host, project
+from .multi_batch_pca import _multi_batch_pca_host, _split_rows, cosineNorm, multiBatchPCA, project
 from .reduced_mnn import MnnResult, fast_mnn_core
 
 
@@ -21,42 +21,63 @@ class FastMnnResult:
     centers: np.ndarray
     merge_info: object
     stats: object = None
+    var_explained: np.ndarray = None   # get_variance: d^2 / nbatches and the total (R/multiBatchPCA.R:422-432)
+    var_total: float = None
+
+    def reconstructed(self, rows=None, cells=None):
+        """The `reconstructed` low-rank assay of convertPCsToSCE (R/convertPCsToSCE.R:60-66), LowRankMatrix(rotation,
+        corrected) = rotation %*% t(corrected), realised in numpy for the genes `rows` and the cells `cells` only
+        (anything numpy indexes an axis with, 0-based; None: all).  With correct_all the rows are those of the input."""
+        rot = self.rotation if rows is None else self.rotation[rows]
+        pcs = self.corrected if cells is None else self.corrected[cells]
+        return np.atleast_2d(rot) @ np.atleast_2d(pcs).T
 
 
-def _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit):
+def _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit, subset_row, correct_all, get_variance):
     """cosineNorm + multiBatchPCA + projection (R/fastMNN.R:348-354): (pca record, list of cells x d matrices)."""
     if pca not in ("device", "host"):
         raise ValueError("'pca' should be one of 'device', 'host'")
     if pca == "device":
-        rec = multiBatchPCA(*mats, d=d, weights=weights, cos_norm=cos_norm, tol=pca_tol, max_iters=pca_maxit, device=device)
+        rec = multiBatchPCA(*mats, d=d, weights=weights, cos_norm=cos_norm, tol=pca_tol, max_iters=pca_maxit, device=device,
+                            subset_row=subset_row, get_all_genes=correct_all, get_variance=get_variance)
         return rec, rec["pcs"]
-    l2 = [cosineNorm(m, mode="l2norm") for m in mats] if cos_norm else None  # R/fastMNN.R:348-351
-    rec = multiBatchPCA_host(*mats, d=d, weights=weights, l2=l2)             # R/fastMNN.R:353-354 (host)
-    return rec, [project(m, rec["rotation"], rec["centers"], cos_norm=cos_norm) for m in mats]
+    l2 = [cosineNorm(m, mode="l2norm", subset_row=subset_row) for m in mats] if cos_norm else None  # R/fastMNN.R:348-351
+    rec, rot, cen = _multi_batch_pca_host(mats, d, weights, l2, 65536, subset_row, correct_all, get_variance)  # :353-354
+    sub = _split_rows(subset_row, mats[0].shape[0])[0]
+    return rec, [project(m if sub is None else m[sub], rot, cen, cos_norm=cos_norm) for m in mats]
 
 
 def fastMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, cos_norm=True, ndist=3, d=50, weights=None,
             merge_order=None, auto_merge=False, min_batch_skip=0.0, names=None, device=0, pca="device",
-            pca_tol=1e-9, pca_maxit=500) -> FastMnnResult:
+            pca_tol=1e-9, pca_maxit=500, subset_row=None, correct_all=False, get_variance=False) -> FastMnnResult:
     """fastMNN(..., batch=, k=, prop.k=, restrict=, cos.norm=, ndist=, d=, weights=, merge.order=, auto.merge=,
-    min.batch.skip=) (R/fastMNN.R:283-331): several batches (`.fast_mnn_list`, :339-358) or ONE genes x cells object with
-    `batch=` naming each cell's batch (`.fast_mnn_single`, :364-388)."""
+    min.batch.skip=, subset.row=, correct.all=, get.variance=) (R/fastMNN.R:283-331): several batches (`.fast_mnn_list`,
+    :339-358) or ONE genes x cells object with `batch=` naming each cell's batch (`.fast_mnn_single`, :364-388).
+
+    subset_row (1-based integers or a logical mask): the genes the cosine norms and the PCA are taken over -- the run is
+    the run on x[subset_row].  correct_all: the result's rotation and centers cover every gene of the input (the others'
+    rotation rows come from multiBatchPCA's get.all.genes), so `reconstructed()` does.  get_variance: `var_explained` and
+    `var_total` of the PCA.  Not taken: d=NA, preserve.single, a character subset.row (there are no row names), deferred,
+    BSPARAM."""
     batches = unpack_batches(batches)
     if len(batches) == 1:
         return _fast_mnn_single(np.asarray(batches[0], dtype=np.float64), batch, k, prop_k, restrict, cos_norm, ndist, d,
-                                weights, merge_order, auto_merge, min_batch_skip, device, pca, pca_tol, pca_maxit)
+                                weights, merge_order, auto_merge, min_batch_skip, device, pca, pca_tol, pca_maxit,
+                                subset_row, correct_all, get_variance)
     if len(batches) < 2:
         raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
     mats = [np.asarray(b, dtype=np.float64) for b in batches]
     check_same_dim(mats, byrow=False)
-    rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit)
+    rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit, subset_row, correct_all, get_variance)
     out: MnnResult = fast_mnn_core(pcs, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device)
     return FastMnnResult(corrected=out.corrected, batch=out.batch, rotation=rec["rotation"], centers=rec["centers"],
-                         merge_info=out.merge_info, stats=out.stats)
+                         merge_info=out.merge_info, stats=out.stats, var_explained=rec.get("var_explained"),
+                         var_total=rec.get("var_total"))
 
 
 def _fast_mnn_single(x, batch, k, prop_k, restrict, cos_norm, ndist, d, weights, merge_order, auto_merge,
-                     min_batch_skip, device, pca, pca_tol, pca_maxit):
+                     min_batch_skip, device, pca, pca_tol, pca_maxit, subset_row=None, correct_all=False,
+                     get_variance=False):
     """.fast_mnn_single (R/fastMNN.R:364-388): the batches are the levels of factor(batch) in sorted order; the PCA sees
     them as separate batches (`.multi_pca_single`, R/multiBatchPCA.R:241-258), the merge engine too
     (divideIntoBatches), and rows and pairs come back in the caller's cell order."""
@@ -69,7 +90,7 @@ def _fast_mnn_single(x, batch, k, prop_k, restrict, cos_norm, ndist, d, weights,
     if len(levels) < 2:
         raise ValueError("at least two batches must be specified")
     mats = [x[:, batch == lev] for lev in levels]
-    rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit)
+    rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit, subset_row, correct_all, get_variance)
     # divideIntoBatches(mat, batch, restrict, byrow=TRUE) on the PCs (R/fastMNN.R:379): restrict is ONE subsetting vector
     # over the cells of x (1-based positions or a logical mask)
     r = restrict[0] if isinstance(restrict, (list, tuple)) and len(restrict) == 1 else restrict
@@ -82,4 +103,5 @@ def _fast_mnn_single(x, batch, k, prop_k, restrict, cos_norm, ndist, d, weights,
     reo = div.reorder                                            # R/fastMNN.R:383-385
     out.merge_info.pairs = reindex_pairings(out.merge_info.pairs, reo)
     return FastMnnResult(corrected=out.corrected[reo - 1], batch=out.batch[reo - 1], rotation=rec["rotation"],
-                         centers=rec["centers"], merge_info=out.merge_info, stats=out.stats)
+                         centers=rec["centers"], merge_info=out.merge_info, stats=out.stats,
+                         var_explained=rec.get("var_explained"), var_total=rec.get("var_total"))

@@ -15,14 +15,19 @@ import numpy as np
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import check_same_dim, unpack_batches
+from .inputs import check_same_dim, subset_index, unpack_batches
 
 
-def cosineNorm(x, mode="matrix"):
-    """cosineNorm(x, mode=c("matrix", "all", "l2norm")) (R/cosineNorm.R:53-82) on the GPU; x is genes x cells."""
-    _lib.require_gpu()
+def cosineNorm(x, mode="matrix", subset_row=None):
+    """cosineNorm(x, mode=c("matrix", "all", "l2norm"), subset.row=NULL) (R/cosineNorm.R:53-82) on the GPU; x is genes x
+    cells.  With subset_row (1-based integers or a logical mask; we have no row names) x is subset first (:54-56): the
+    norms are over those rows and the matrix returned has only them."""
     if mode not in ("matrix", "all", "l2norm"):
         raise ValueError("'arg' should be one of 'matrix', 'all', 'l2norm'")
+    idx = subset_index(subset_row, np.asarray(x).shape[0])
+    if idx is not None:
+        x = np.asarray(x)[idx.astype(np.int64) - 1]
+    _lib.require_gpu()
     x = _lib.as_f(x)
     G, n = x.shape
     l2 = np.zeros(n, dtype=np.float64)
@@ -124,13 +129,102 @@ class DevicePCA(ResidentHandle):
         _lib.check(_lib.lib().bmx_pca_project(self._h, int(b), _lib.f64p(out)))
         return np.ascontiguousarray(out)
 
+    def genes(self, n_left):
+        """The streaming pass over the n_left genes outside subset.row, on this fitted PCA (DevicePCAGenes)."""
+        return DevicePCAGenes(self, n_left)
+
+
+class DevicePCAGenes:
+    """bmx_pca_genes_t: multiBatchPCA's get.all.genes / get.variance (R/multiBatchPCA.R:401-432) for a DevicePCA that
+    holds the subset.row rows and has been fitted.  The rows outside the subset go through in column blocks, batch by batch
+    in the order the batches were added, and are not kept on the device; finish() returns their centres and rotation rows.
+    The wrapper keeps its DevicePCA alive; a fit() or a new batch on it makes every later call here an error."""
+
+    def __init__(self, pca, n_left):
+        self.pca = pca
+        self.n_left = int(n_left)
+        self._h = ctypes.c_void_p()
+        lib = _lib.lib()
+        lib.bmx_pca_genes_destroy.argtypes = [ctypes.c_void_p]
+        lib.bmx_pca_genes_destroy.restype = None
+        _lib.check(lib.bmx_pca_genes_create(ctypes.c_int32(self.n_left), pca._h, ctypes.byref(self._h)))
+
+    def begin_batch(self, b):
+        _lib.check(_lib.lib().bmx_pca_genes_begin_batch(self._h, ctypes.c_int32(int(b))))
+
+    def add_block(self, x_left_block):
+        """The next cells of the batch begun last: n_left x cells."""
+        x_left_block = _lib.as_f(x_left_block)
+        if x_left_block.ndim != 2 or x_left_block.shape[0] != self.n_left:
+            raise ValueError("number of rows is not the same across batches")
+        _lib.check(_lib.lib().bmx_pca_genes_add_block(self._h, _lib.f64p(x_left_block),
+                                                      ctypes.c_int64(x_left_block.shape[1])))
+
+    def finish(self):
+        """(centers [n_left], rotation [n_left x d]) of the leftover genes."""
+        centers = np.zeros(self.n_left)
+        rotation = np.zeros((self.n_left, self.pca.d), order="F")
+        _lib.check(_lib.lib().bmx_pca_genes_finish(self._h, _lib.f64p(centers), _lib.f64p(rotation)))
+        return centers, np.ascontiguousarray(rotation)
+
+    def total_variance(self):
+        """sum_b (w_b / n_b) |C_b|_F^2 over the rows the DevicePCA holds: var.total times the number of batches."""
+        out = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().bmx_pca_genes_total_variance(self._h, ctypes.byref(out)))
+        return out.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().bmx_pca_genes_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _split_rows(subset_row, G):
+    """(0-based subset rows in the caller's order, 0-based rows outside it ascending); (None, empty) without a subset."""
+    idx = subset_index(subset_row, G)
+    if idx is None:
+        return None, np.zeros(0, dtype=np.int64)
+    sub = idx.astype(np.int64) - 1
+    keep = np.ones(G, dtype=bool)
+    keep[sub] = False
+    return sub, np.flatnonzero(keep)
+
+
+def _all_genes(rec, G, sub, left, centers_left, rotation_left):
+    """rotation / centers over all G rows (R/multiBatchPCA.R:408-414): the subset rows assigned by index -- a row named
+    twice takes the later one, as R's `rotation[subset.row,] <- u` does -- and the others from the leftover pass."""
+    rotation = np.zeros((G, rec["rotation"].shape[1]))
+    centers = np.zeros(G)
+    rotation[sub] = rec["rotation"]
+    centers[sub] = rec["centers"]
+    rotation[left] = rotation_left
+    centers[left] = centers_left
+    rec["rotation"], rec["centers"] = rotation, centers
+
+
+_UPLOAD_BYTES = 1 << 28   # a column block of gathered rows on its way to the device
+
 
 def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_iters=500, iters=None, device=0,
-                  return_pcs=True, l2=None, block=65536):
-    """multiBatchPCA(..., d=, weights=) (R/multiBatchPCA.R:140-258) on the device.  Batches are genes x cells; with
-    cos_norm the cosine normalisation of fastMNN (R/fastMNN.R:348-351) is applied on the fly.
+                  return_pcs=True, l2=None, block=65536, subset_row=None, get_all_genes=False, get_variance=False):
+    """multiBatchPCA(..., d=, weights=, subset.row=, get.all.genes=, get.variance=) (R/multiBatchPCA.R:140-258) on the
+    device.  Batches are genes x cells; with cos_norm the cosine normalisation of fastMNN (R/fastMNN.R:348-351) is applied
+    on the fly.
     Returns {"rotation", "centers", "d", "weights", "iters_used", "residual", "path"} plus "pcs": the list of cells x d
     projections.
+
+    subset_row (1-based integers or a logical mask): the PCA runs on those rows, gathered on the host block by block --
+    the call is the call on x[subset_row], cosine norms included (they are taken over the subset, R/fastMNN.R:348-351).
+    get_all_genes: "rotation" and "centers" cover every row of the input; the rows outside the subset are streamed through
+    the device once (DevicePCAGenes) and never gathered whole (R/multiBatchPCA.R:401-414).  Without a subset, or with one
+    that leaves no row out, it changes nothing.  get_variance: "var_explained" = d^2 / nbatches and "var_total"
+    (:422-432).  Not taken: d=NA, preserve.single, a character subset.row (there are no row names), deferred, BSPARAM.
 
     The device path iterates until the relative Ritz residual is <= tol (the reference's irlba stops at 1e-5 on the
     singular triplets, R/multiBatchPCA.R:386-393) and raises when max_iters passes do not get there.  Inputs the blocked
@@ -140,20 +234,29 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
     batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
-    G = check_same_dim(batches, byrow=False)
+    G_all = check_same_dim(batches, byrow=False)
+    sub, left = _split_rows(subset_row, G_all)
+    G = G_all if sub is None else sub.size
+    if not get_all_genes:
+        left = left[:0]
     ncells = [np.asarray(m).shape[1] for m in batches]
     w = _weight_vector(ncells, weights)
     width = 64 if d <= 56 else 128
+
+    def rows(m, which, lo, hi):
+        """Columns [lo, hi) of the rows `which` (None: all) of a batch."""
+        blk = np.asarray(m)[:, lo:hi]
+        return blk if which is None else blk[which]
 
     def host(reason):
         if l2 is not None:
             norms = l2
         else:
-            norms = [cosineNorm(m, mode="l2norm") for m in batches] if cos_norm else None
-        out = multiBatchPCA_host(*batches, d=d, weights=weights, l2=norms, block=block)
+            norms = [cosineNorm(m, mode="l2norm", subset_row=subset_row) for m in batches] if cos_norm else None
+        out, rot, cen = _multi_batch_pca_host(batches, d, weights, norms, block, subset_row, get_all_genes, get_variance)
         out.update(iters_used=0, residual=0.0, path="host: " + reason)
         if return_pcs:
-            out["pcs"] = [project(m, out["rotation"], out["centers"], cos_norm=norms is not None) for m in batches]
+            out["pcs"] = [project(rows(m, sub, 0, None), rot, cen, cos_norm=norms is not None) for m in batches]
         return out
 
     if l2 is not None:
@@ -162,8 +265,14 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
         return host("fewer genes / cells than the device block, or d > 120")
     pca = DevicePCA(G, device)
     try:
-        for m, wi in zip(batches, w):
-            pca.add_batch(m, weight=wi, cos_norm=cos_norm)
+        for m, wi, n in zip(batches, w, ncells):
+            if sub is None:
+                pca.add_batch(m, weight=wi, cos_norm=cos_norm)
+                continue
+            pca.begin_batch(n, weight=wi, cos_norm=cos_norm)
+            per = max(1, _UPLOAD_BYTES // (8 * G))
+            for lo in range(0, n, per):
+                pca.add_block(rows(m, sub, lo, lo + per))
         try:
             out = pca.fit(d=d, tol=tol, max_iters=max_iters, iters=iters)
         except _lib.BatchelorMI355XError as exc:
@@ -175,22 +284,85 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
         out["path"] = "device"
         if return_pcs:
             out["pcs"] = [pca.project(b) for b in range(len(batches))]
+        if left.size or get_variance:
+            genes = pca.genes(left.size)
+            try:
+                if left.size:
+                    per = max(1, _UPLOAD_BYTES // (8 * left.size))
+                    for b, (m, n) in enumerate(zip(batches, ncells)):
+                        genes.begin_batch(b)
+                        for lo in range(0, n, per):
+                            genes.add_block(rows(m, left, lo, lo + per))
+                    _all_genes(out, G_all, sub, left, *genes.finish())
+                if get_variance:
+                    out["var_explained"] = out["d"] ** 2 / len(batches)
+                    out["var_total"] = genes.total_variance() / len(batches)
+            finally:
+                genes.close()
     finally:
         pca.close()
     return out
 
 
-def multiBatchPCA_host(*batches, d=50, weights=None, l2=None, block=65536):
+def multiBatchPCA_host(*batches, d=50, weights=None, l2=None, block=65536, subset_row=None, get_all_genes=False,
+                       get_variance=False):
     """Host PCA across batches (genes x cells each).  `l2` (optional list of per-cell norms) applies the cosine
     normalisation on the fly, so the normalised matrices are never materialised.
 
     Returns {"rotation": [G x d], "centers": [G], "d": singular values, "weights": w}.  Project with `project()`.
+
+    subset_row, get_all_genes, get_variance: as multiBatchPCA (R/multiBatchPCA.R:401-432), in float64 numpy; `l2` then
+    holds the norms over the subset rows (cosineNorm(x, "l2norm", subset_row=)) and scales every row.
     """
-    batches = unpack_batches(batches)
+    return _multi_batch_pca_host(unpack_batches(batches), d, weights, l2, block, subset_row, get_all_genes, get_variance)[0]
+
+
+def _multi_batch_pca_host(batches, d, weights, l2, block, subset_row, get_all_genes, get_variance):
+    """multiBatchPCA_host's record, and the rotation and centres of the rows the PCA ran on (what projects them)."""
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
-    mats = [np.asarray(b, dtype=np.float64) for b in batches]
-    G = check_same_dim(mats, byrow=False)
+    full = [np.asarray(b, dtype=np.float64) for b in batches]
+    G_all = check_same_dim(full, byrow=False)
+    sub, left = _split_rows(subset_row, G_all)
+    mats = full if sub is None else [m[sub] for m in full]
+    rec = _host_pca(mats, d, weights, l2, block)
+    rot, cen = rec["rotation"], rec["centers"]
+    w, nb = rec["weights"], len(mats)
+    inv = [None if l2 is None else 1.0 / np.maximum(1e-8, np.asarray(l2[i], dtype=np.float64)) for i in range(nb)]
+    if get_variance:
+        total = 0.0
+        for i, m in enumerate(mats):
+            for lo in range(0, m.shape[1], block):
+                c = m[:, lo:lo + block]
+                c = (c if inv[i] is None else c * inv[i][None, lo:lo + block]) - cen[:, None]
+                total += (w[i] / m.shape[1]) * float((c * c).sum())
+        rec["var_explained"] = rec["d"] ** 2 / nb
+        rec["var_total"] = total / nb
+    if get_all_genes and left.size:
+        # left.scaled %*% v swept by d, v = S_scaled^T u / d (R/multiBatchPCA.R:404-406): with Z_b = C_b^T u,
+        # ( sum_b coef_b L_b diag(scale_b) Z_b  -  mu_L sum_b coef_b 1^T Z_b ) / d^2
+        acc = np.zeros((left.size, rot.shape[1]))
+        zsum = np.zeros(rot.shape[1])
+        mu_left = np.zeros(left.size)
+        for i, (m, f) in enumerate(zip(mats, full)):
+            coef = w[i] / m.shape[1]
+            gsum = np.zeros(left.size)
+            for lo in range(0, m.shape[1], block):
+                sc = 1.0 if inv[i] is None else inv[i][None, lo:lo + block]
+                z = (m[:, lo:lo + block] * sc - cen[:, None]).T @ rot
+                lb = f[:, lo:lo + block][left] * sc
+                acc += coef * (lb @ z)
+                zsum += coef * z.sum(axis=0)
+                gsum += lb.sum(axis=1)
+            mu_left += (gsum / m.shape[1]) * w[i]
+        mu_left /= w.sum()
+        _all_genes(rec, G_all, sub, left, mu_left, (acc - np.outer(mu_left, zsum)) / rec["d"] ** 2)
+    return rec, rot, cen
+
+
+def _host_pca(mats, d, weights, l2, block):
+    """The PCA itself on float64 batches that all have the rows it runs on."""
+    G = mats[0].shape[0]
     w = _weight_vector([m.shape[1] for m in mats], weights)
     inv = [None if l2 is None else 1.0 / np.maximum(1e-8, np.asarray(l2[i], dtype=np.float64)) for i in range(len(mats))]
 

@@ -380,6 +380,32 @@ int32_t bmx_pca_fit(bmx_pca_t* p, int32_t d, int32_t iters, double* centers, dou
 /* crossprod(cosineNorm(x_b) - centers, rotation) (R/multiBatchPCA.R:236-239): out [n_b x d] column-major. */
 int32_t bmx_pca_project(bmx_pca_t* p, int32_t batch, double* out);
 
+/* multiBatchPCA(subset.row=, get.all.genes=TRUE, get.variance=TRUE) (R/multiBatchPCA.R:401-432).  The bmx_pca_t holds
+ * the subset.row rows only (the caller gathers them; cos_norm then norms over exactly those rows, R/fastMNN.R:348-351) and
+ * is fitted as above.  A bmx_pca_genes_t borrows the fitted handle and streams the n_genes_left rows OUTSIDE the subset
+ * through the device once, in column blocks that are not kept (two in HBM at a time: the upload of a block overlaps the
+ * kernels of the one before): per block the cells' projections are recomputed from the resident subset rows, and one
+ * read of the block on the FP64 matrix cores accumulates  sum_b (w_b / n_b) sum_c scale_c x_gc pcs_b[c][j]  and the gene
+ * sums.  bmx_pca_genes_finish then gives the leftover genes' grand centres (formed as the subset's) and rotation rows
+ *     ( that sum  -  center[g] * sum_b (w_b / n_b) sum_c pcs_b[c][j] ) / sdev[j]^2
+ * = left.scaled %*% v swept by d.  The fitted handle must outlive this one; after a bmx_pca_begin_batch / add_batch / fit
+ * on it every call here is BMX_ERR_ARG.  No floating-point atomics: the same calls give the same bits.
+ * n_genes_left may be 0 (bmx_pca_genes_total_variance alone). */
+typedef struct bmx_pca_genes bmx_pca_genes_t;
+int32_t bmx_pca_genes_create(int32_t n_genes_left, bmx_pca_t* fitted, bmx_pca_genes_t** out);
+void bmx_pca_genes_destroy(bmx_pca_genes_t* h);
+/* The leftover rows of batch `batch` (0-based) follow; batches come 0, 1, ... in the order they were added. */
+int32_t bmx_pca_genes_begin_batch(bmx_pca_genes_t* h, int32_t batch);
+/* The next n_block cells of that batch, in order: x_left_block is n_genes_left x n_block column-major host memory,
+ * pageable or pinned, read completely when the call returns (the staging ring of bmx_pca_add_block). */
+int32_t bmx_pca_genes_add_block(bmx_pca_genes_t* h, const double* x_left_block, int64_t n_block);
+/* Once every batch has all its cells: centers_left [n_genes_left], rotation_left [n_genes_left x d] column-major; either
+ * may be NULL. */
+int32_t bmx_pca_genes_finish(bmx_pca_genes_t* h, double* centers_left, double* rotation_left);
+/* *var_total = sum_b (w_b / n_b) |x_b diag(scale_b) - centers 1^T|_F^2 over the resident (subset) rows, summed in the
+ * centred form in a fixed order; var.total of R/multiBatchPCA.R:428-431 is this over the number of batches. */
+int32_t bmx_pca_genes_total_variance(bmx_pca_genes_t* h, double* var_total);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * clusterMNN() (R/clusterMNN.R:101-312): the two per-cell stages around the centroid-level merge.  The batches (genes x
  * cells, column-major) are uploaded once, whole or in column blocks through the pinned staging ring, and stay in HBM
