@@ -234,6 +234,8 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = (int64_t)t[n == "asv_ticks_literal" ? 4 : (n == "asv_ticks_chains" ? 5 : (n == "asv_literal_addends" ? 6 : 7))];
         } else if (n == "delta_gene_tile" || n == "delta_pair_chunk") {
             *value = n == "delta_gene_tile" ? bmx::DELTA_GENE_TILE : bmx::DELTA_PAIR_CHUNK;
+        } else if (n == "pca_sparse_row_segment") {
+            *value = bmx::PCA_SPARSE_ROW_SEGMENT;
         } else if (n == "asv_tally_reset") {
             bmx::asv_tally_read(t, true);
             *value = 0;

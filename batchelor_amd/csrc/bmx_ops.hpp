@@ -164,6 +164,7 @@ void cosnorm_project_device(hipStream_t stream, const double* x, int G, int n, c
 
 // ---- mnnDeltaVariance (delta_variance.hip): the tiling of its pair passes, which bmx_dev_get reports -------------
 constexpr int DELTA_GENE_TILE = 256;   // genes a workgroup of the pair passes owns
+constexpr int PCA_SPARSE_ROW_SEGMENT = 256;  // stored entries of a gene row one wave of the sparse PCA's by-gene pass adds
 constexpr int DELTA_PAIR_CHUNK = 128;  // pairs of one step a workgroup walks (fixed: the results do not depend on the grid)
 
 // ---- legacy natives (legacy.hip) -------------------------------------------------------------------

@@ -7,8 +7,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .inputs import check_same_dim, divide_into_batches, reindex_pairings, unpack_batches
-from .multi_batch_pca import _multi_batch_pca_host, _split_rows, cosineNorm, multiBatchPCA, project
+from .inputs import all_sparse, check_same_dim, check_same_rows, divide_into_batches, reindex_pairings, unpack_batches
+from .multi_batch_pca import _multi_batch_pca_host, _split_rows, cosineNorm, densify, multiBatchPCA, project
 from .reduced_mnn import MnnResult, fast_mnn_core
 
 
@@ -41,6 +41,8 @@ def _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit, subse
         rec = multiBatchPCA(*mats, d=d, weights=weights, cos_norm=cos_norm, tol=pca_tol, max_iters=pca_maxit, device=device,
                             subset_row=subset_row, get_all_genes=correct_all, get_variance=get_variance)
         return rec, rec["pcs"]
+    if all_sparse(mats, "fastMNN"):   # the host PCA and the projection behind it take dense batches
+        mats = densify(mats, "fastMNN")
     l2 = [cosineNorm(m, mode="l2norm", subset_row=subset_row) for m in mats] if cos_norm else None  # R/fastMNN.R:348-351
     rec, rot, cen = _multi_batch_pca_host(mats, d, weights, l2, 65536, subset_row, correct_all, get_variance)  # :353-354
     sub = _split_rows(subset_row, mats[0].shape[0])[0]
@@ -57,17 +59,24 @@ def fastMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, cos_norm=Tru
     subset_row (1-based integers or a logical mask): the genes the cosine norms and the PCA are taken over -- the run is
     the run on x[subset_row].  correct_all: the result's rotation and centers cover every gene of the input (the others'
     rotation rows come from multiBatchPCA's get.all.genes), so `reconstructed()` does.  get_variance: `var_explained` and
-    `var_total` of the PCA.  Not taken: d=NA, preserve.single, a character subset.row (there are no row names), deferred,
-    BSPARAM."""
+    `var_total` of the PCA.  Batches that are all scipy.sparse objects (several, or one with `batch=`, whose columns are
+    split sparse) stay sparse through the PCA (multiBatchPCA's sparse path); everything after it is unchanged.
+    Not taken: d=NA, preserve.single, a character subset.row (there are no row names), deferred, BSPARAM."""
     batches = unpack_batches(batches)
+    sparse = all_sparse(batches, "fastMNN")
     if len(batches) == 1:
-        return _fast_mnn_single(np.asarray(batches[0], dtype=np.float64), batch, k, prop_k, restrict, cos_norm, ndist, d,
+        x = batches[0].tocsc() if sparse else np.asarray(batches[0], dtype=np.float64)
+        return _fast_mnn_single(x, batch, k, prop_k, restrict, cos_norm, ndist, d,
                                 weights, merge_order, auto_merge, min_batch_skip, device, pca, pca_tol, pca_maxit,
                                 subset_row, correct_all, get_variance)
     if len(batches) < 2:
         raise ValueError("at least two batches must be specified")  # R/fastMNN.R:345
-    mats = [np.asarray(b, dtype=np.float64) for b in batches]
-    check_same_dim(mats, byrow=False)
+    if sparse:
+        mats = list(batches)
+        check_same_rows(mats)
+    else:
+        mats = [np.asarray(b, dtype=np.float64) for b in batches]
+        check_same_dim(mats, byrow=False)
     rec, pcs = _pca_step(mats, d, weights, cos_norm, device, pca, pca_tol, pca_maxit, subset_row, correct_all, get_variance)
     out: MnnResult = fast_mnn_core(pcs, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device)
     return FastMnnResult(corrected=out.corrected, batch=out.batch, rotation=rec["rotation"], centers=rec["centers"],

@@ -8,6 +8,7 @@ import ctypes
 from typing import NamedTuple, Optional
 
 import numpy as np
+import scipy.sparse as sp
 
 
 def unpack_batches(batches):
@@ -28,6 +29,50 @@ def check_same_dim(mats, byrow, see_batch=False):
         if m.ndim != 2 or m.shape[axis] != dim:
             raise ValueError(f"number of {what} is not the same across batches" + (f" (see batch {i + 1})" if see_batch else ""))
     return dim
+
+
+def all_sparse(batches, who):
+    """Whether the batches are scipy.sparse objects: all of them (True) or none (False); a mixture is refused."""
+    flags = [sp.issparse(b) for b in batches]
+    if any(flags) and not all(flags):
+        raise TypeError(f"{who} takes batches that are all sparse or all dense, not a mixture")
+    return len(flags) > 0 and all(flags)
+
+
+def check_same_rows(mats):
+    """check_same_dim(byrow=False) for scipy.sparse batches."""
+    for m in mats:
+        if m.ndim != 2 or m.shape[0] != mats[0].shape[0]:
+            raise ValueError("number of rows is not the same across batches")
+    return mats[0].shape[0]
+
+
+def canonical_csc(m):
+    """A scipy.sparse matrix or array of any format as canonical CSC: duplicates summed, rows ascending within a column,
+    float64 data, int32 indices; stored zeros stay.  Returns (csc, owned): the caller's object is never modified, and
+    `owned` is False when the result still shares its index arrays with it."""
+    c = m.tocsc()
+    owned = c is not m
+    if not c.has_canonical_format:
+        if not owned:
+            c, owned = c.copy(), True
+        c.sum_duplicates()  # (sorts the indices first)
+    if c.data.dtype != np.float64:
+        c = sp.csc_matrix((c.data.astype(np.float64), c.indices, c.indptr), shape=c.shape)
+    if c.indices.dtype != np.int32:
+        c = sp.csc_matrix((c.data, c.indices.astype(np.int32), c.indptr), shape=c.shape)
+        owned = True
+    return c, owned
+
+
+def csc_blocks(c, width):
+    """The column blocks of canonical CSC `c`, `width` cells each (the last one fewer), as the library takes them:
+    (cells, indptr relative to the block as int64, indices, data)."""
+    n = c.shape[1]
+    for a in range(0, n, width):
+        b = min(n, a + width)
+        k0, k1 = int(c.indptr[a]), int(c.indptr[b])
+        yield b - a, c.indptr[a:b + 1].astype(np.int64) - k0, c.indices[k0:k1], c.data[k0:k1]
 
 
 def check_unique_names(names):

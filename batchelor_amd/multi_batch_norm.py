@@ -34,7 +34,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import check_same_dim, divide_into_batches, subset_index, unpack_batches
+from .inputs import canonical_csc, check_same_dim, csc_blocks, divide_into_batches, subset_index, unpack_batches
 from .linear_correct import _as_matrices, _check_batch, _check_names
 
 BLOCK_BYTES = 1 << 28   # a batch above this size goes to the device in column blocks of about this many bytes
@@ -92,34 +92,6 @@ class _NormHandle(ResidentHandle):
                    ctypes.c_double(float(pseudo_count)), ptrs, _lib.f64p(sf), _lib.f64p(ave), _lib.f64p(ratios),
                    ctypes.byref(smallest))
         return out, sf, ave, ratios, int(smallest.value)
-
-
-def canonical_csc(m):
-    """A scipy.sparse matrix or array of any format as canonical CSC: duplicates summed, rows ascending within a column,
-    float64 data, int32 indices; stored zeros stay.  Returns (csc, owned): the caller's object is never modified, and
-    `owned` is False when the result still shares its index arrays with it."""
-    c = m.tocsc()
-    owned = c is not m
-    if not c.has_canonical_format:
-        if not owned:
-            c, owned = c.copy(), True
-        c.sum_duplicates()  # (sorts the indices first)
-    if c.data.dtype != np.float64:
-        c = sp.csc_matrix((c.data.astype(np.float64), c.indices, c.indptr), shape=c.shape)
-    if c.indices.dtype != np.int32:
-        c = sp.csc_matrix((c.data, c.indices.astype(np.int32), c.indptr), shape=c.shape)
-        owned = True
-    return c, owned
-
-
-def csc_blocks(c, width):
-    """The column blocks of canonical CSC `c`, `width` cells each (the last one fewer), as the library takes them:
-    (cells, indptr relative to the block as int64, indices, data)."""
-    n = c.shape[1]
-    for a in range(0, n, width):
-        b = min(n, a + width)
-        k0, k1 = int(c.indptr[a]), int(c.indptr[b])
-        yield b - a, c.indptr[a:b + 1].astype(np.int64) - k0, c.indices[k0:k1], c.data[k0:k1]
 
 
 class _SparseNormHandle(ResidentHandle):

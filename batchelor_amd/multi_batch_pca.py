@@ -12,18 +12,26 @@ from __future__ import annotations
 import ctypes
 
 import numpy as np
+import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import check_same_dim, subset_index, unpack_batches
+from .inputs import all_sparse, canonical_csc, check_same_dim, check_same_rows, csc_blocks, subset_index, unpack_batches
+
+# Sparse batches that the device path cannot take (multiBatchPCA's docstring) are made dense for the host path; beyond
+# this many bytes of dense float64 over all batches the call is refused instead.
+DENSIFY_CAP_BYTES = 8 << 30
 
 
 def cosineNorm(x, mode="matrix", subset_row=None):
     """cosineNorm(x, mode=c("matrix", "all", "l2norm"), subset.row=NULL) (R/cosineNorm.R:53-82) on the GPU; x is genes x
     cells.  With subset_row (1-based integers or a logical mask; we have no row names) x is subset first (:54-56): the
-    norms are over those rows and the matrix returned has only them."""
+    norms are over those rows and the matrix returned has only them.  A scipy.sparse x stays on the host (one pass over
+    its stored entries, less work than their transfer): the matrix comes back as canonical CSC, a zero stays a zero."""
     if mode not in ("matrix", "all", "l2norm"):
         raise ValueError("'arg' should be one of 'matrix', 'all', 'l2norm'")
+    if sp.issparse(x):
+        return _cosine_norm_sparse(x, mode, subset_row)
     idx = subset_index(subset_row, np.asarray(x).shape[0])
     if idx is not None:
         x = np.asarray(x)[idx.astype(np.int64) - 1]
@@ -35,6 +43,19 @@ def cosineNorm(x, mode="matrix", subset_row=None):
     _lib.check(_lib.lib().bmx_cosine_norm(_lib.f64p(x), G, n, _lib.f64p(l2), None if mat is None else _lib.f64p(mat)))
     if mode == "l2norm":
         return l2
+    return mat if mode == "matrix" else {"matrix": mat, "l2norm": l2}
+
+
+def _cosine_norm_sparse(x, mode, subset_row):
+    c = canonical_csc(x)[0]
+    idx = subset_index(subset_row, c.shape[0])
+    if idx is not None:
+        c = canonical_csc(c[idx.astype(np.int64) - 1])[0]
+    l2 = np.sqrt(np.asarray(c.multiply(c).sum(axis=0), dtype=np.float64).ravel())
+    if mode == "l2norm":
+        return l2
+    scale = 1.0 / np.maximum(1e-8, l2)
+    mat = sp.csc_matrix((c.data * np.repeat(scale, np.diff(c.indptr)), c.indices.copy(), c.indptr.copy()), shape=c.shape)
     return mat if mode == "matrix" else {"matrix": mat, "l2norm": l2}
 
 
@@ -185,6 +206,83 @@ class DevicePCAGenes:
             pass
 
 
+def sparse_row_segment():
+    """Stored entries of a gene row that one wave of the sparse PCA's by-gene pass adds (bmx_dev_get
+    "pca_sparse_row_segment"; needs no device): a row with more entries is cut into segments of this length."""
+    return _lib.dev_get("pca_sparse_row_segment")
+
+
+class DeviceSparsePCA(ResidentHandle):
+    """bmx_pca_sparse_t: DevicePCA for batches kept in HBM as CSC.  The handle holds n_rows rows of every batch, of which
+    the first n_rows_pca are the rows the PCA runs on (the subset in the caller's order) and the others the genes outside
+    the subset, ascending; they stay resident, so genes() needs no second pass over the host's data."""
+    PREFIX = "bmx_pca_sparse"
+    BLOCK_BYTES = 1 << 28   # a batch goes to the device in column blocks of about this many bytes of stored entries
+
+    def __init__(self, n_rows, n_rows_pca=None, device=0):
+        _lib.require_gpu()
+        self.n_pca = int(n_rows if n_rows_pca is None else n_rows_pca)
+        super().__init__(n_rows, device, ctypes.c_int32(self.n_pca))
+        self.d = 0
+        self.iters_used = 0
+        self.residual = float("nan")
+
+    def add_batch(self, c, weight=1.0, cos_norm=False, block_cells=None):
+        """c: canonical CSC (inputs.canonical_csc), n_rows x cells.  block_cells: cells per uploaded block (None: as many
+        as hold about BLOCK_BYTES of stored entries, 12 bytes each); the results do not depend on it."""
+        if c.ndim != 2 or c.shape[0] != self.G:
+            raise ValueError("number of rows is not the same across batches")
+        n, nnz = int(c.shape[1]), int(c.nnz)
+        per = max(1, self.BLOCK_BYTES * n // max(1, 12 * nnz)) if block_cells is None else max(1, int(block_cells))
+        self._call("begin_batch", ctypes.c_int64(n), ctypes.c_double(float(weight)), 1 if cos_norm else 0,
+                   ctypes.c_int64(nnz))
+        self.ncells.append(n)
+        for m, indptr, indices, data in csc_blocks(c, per):
+            self.add_block(m, indptr, indices, data)
+
+    def add_block(self, m, indptr, indices, data):
+        """The next m cells of the batch begun last: indptr [m + 1] int64 relative to the block, int32 rows, float64."""
+        self._call("add_block", ctypes.c_int64(int(m)), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
+                   _lib.f64p(data), ctypes.c_int64(int(data.size)))
+
+    def fit(self, d=50, tol=1e-9, max_iters=500, iters=None):
+        """As DevicePCA.fit, over the first n_rows_pca rows."""
+        centers = np.zeros(self.n_pca)
+        rotation = np.zeros((self.n_pca, d), order="F")
+        sdev = np.zeros(d)
+        if iters is not None:
+            self._call("fit", int(d), int(iters), _lib.f64p(centers), _lib.f64p(rotation), _lib.f64p(sdev))
+            self.iters_used, self.residual = int(iters), float("nan")
+        else:
+            used, res = ctypes.c_int32(0), ctypes.c_double(0.0)
+            rc = self._entry("fit_tol")(self._h, int(d), ctypes.c_double(float(tol)), int(max_iters), _lib.f64p(centers),
+                                        _lib.f64p(rotation), _lib.f64p(sdev), ctypes.byref(used), ctypes.byref(res))
+            self.iters_used, self.residual = used.value, res.value
+            _lib.check(rc)
+        self.d = int(d)
+        return {"rotation": np.ascontiguousarray(rotation), "centers": centers, "d": sdev,
+                "iters_used": self.iters_used, "residual": self.residual}
+
+    def project(self, b):
+        out = np.zeros((self.ncells[b], self.d), order="F")
+        self._call("project", int(b), _lib.f64p(out))
+        return np.ascontiguousarray(out)
+
+    def genes(self):
+        """(centers [n_rows - n_rows_pca], rotation [n_rows - n_rows_pca x d]) of the rows outside the subset."""
+        n_left = self.G - self.n_pca
+        centers = np.zeros(n_left)
+        rotation = np.zeros((n_left, self.d), order="F")
+        self._call("genes", _lib.f64p(centers), _lib.f64p(rotation))
+        return centers, np.ascontiguousarray(rotation)
+
+    def total_variance(self):
+        """sum_b (w_b / n_b) |C_b|_F^2 over the PCA rows: var.total times the number of batches."""
+        out = ctypes.c_double(0.0)
+        self._call("total_variance", ctypes.byref(out))
+        return out.value
+
+
 def _split_rows(subset_row, G):
     """(0-based subset rows in the caller's order, 0-based rows outside it ascending); (None, empty) without a subset."""
     idx = subset_index(subset_row, G)
@@ -230,10 +328,19 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
     singular triplets, R/multiBatchPCA.R:386-393) and raises when max_iters passes do not get there.  Inputs the blocked
     iteration cannot take -- fewer genes or cells than its block of 64 / 128 vectors, d > 120, data of rank below the
     block -- go to multiBatchPCA_host (north_star keeps multiBatchPCA on the host path anyway), as does a call in
-    round 1's form with per-cell norms `l2=` (and its `block=`)."""
+    round 1's form with per-cell norms `l2=` (and its `block=`).
+
+    Batches that are all scipy.sparse objects (a mixture with dense ones is a TypeError) go up as canonical CSC and stay
+    sparse in HBM (DeviceSparsePCA, "path": "device-sparse"): every batch as [x[subset_row]; the other rows, ascending] by
+    one sparse row-indexing, so the leftover rows of get_all_genes are resident too and nothing is streamed; all the
+    arguments above work as for dense batches.  Under the fallback conditions above the sparse batches are made dense
+    for the host path; that is refused with a ValueError above DENSIFY_CAP_BYTES (8 GiB of float64 over all batches)."""
     batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
+    if all_sparse(batches, "multiBatchPCA"):
+        return _multi_batch_pca_sparse(batches, d, weights, cos_norm, tol, max_iters, iters, device, return_pcs, l2, block,
+                                       subset_row, get_all_genes, get_variance)
     G_all = check_same_dim(batches, byrow=False)
     sub, left = _split_rows(subset_row, G_all)
     G = G_all if sub is None else sub.size
@@ -249,15 +356,8 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
         return blk if which is None else blk[which]
 
     def host(reason):
-        if l2 is not None:
-            norms = l2
-        else:
-            norms = [cosineNorm(m, mode="l2norm", subset_row=subset_row) for m in batches] if cos_norm else None
-        out, rot, cen = _multi_batch_pca_host(batches, d, weights, norms, block, subset_row, get_all_genes, get_variance)
-        out.update(iters_used=0, residual=0.0, path="host: " + reason)
-        if return_pcs:
-            out["pcs"] = [project(rows(m, sub, 0, None), rot, cen, cos_norm=norms is not None) for m in batches]
-        return out
+        return _host_route(batches, reason, d, weights, cos_norm, l2, block, subset_row, sub, get_all_genes, get_variance,
+                           return_pcs)
 
     if l2 is not None:
         return host("per-cell norms given (round-1 signature)")
@@ -299,6 +399,82 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
                     out["var_total"] = genes.total_variance() / len(batches)
             finally:
                 genes.close()
+    finally:
+        pca.close()
+    return out
+
+
+def _host_route(batches, reason, d, weights, cos_norm, l2, block, subset_row, sub, get_all_genes, get_variance, return_pcs):
+    """multiBatchPCA's record from the host path (dense batches), with the device's projection."""
+    if l2 is not None:
+        norms = l2
+    else:
+        norms = [cosineNorm(m, mode="l2norm", subset_row=subset_row) for m in batches] if cos_norm else None
+    out, rot, cen = _multi_batch_pca_host(batches, d, weights, norms, block, subset_row, get_all_genes, get_variance)
+    out.update(iters_used=0, residual=0.0, path="host: " + reason)
+    if return_pcs:
+        out["pcs"] = [project(np.asarray(m) if sub is None else np.asarray(m)[sub], rot, cen, cos_norm=norms is not None)
+                      for m in batches]
+    return out
+
+
+def densify(batches, who):
+    """scipy.sparse batches as dense float64 for a host path; refused above DENSIFY_CAP_BYTES over all batches."""
+    need = sum(8 * int(m.shape[0]) * int(m.shape[1]) for m in batches)
+    if need > DENSIFY_CAP_BYTES:
+        raise ValueError(f"{who}: the host path needs the sparse batches dense, {need} bytes of float64; more than "
+                         f"{DENSIFY_CAP_BYTES} bytes are not densified")
+    return [np.asarray(m.toarray(), dtype=np.float64) for m in batches]
+
+
+def _csc_rows(m, rows):
+    """Batch m as canonical CSC with the rows `rows` (0-based, in that order, repeats allowed; None: all)."""
+    c = canonical_csc(m)[0]
+    return c if rows is None else canonical_csc(c[rows])[0]
+
+
+def _multi_batch_pca_sparse(batches, d, weights, cos_norm, tol, max_iters, iters, device, return_pcs, l2, block,
+                            subset_row, get_all_genes, get_variance):
+    """multiBatchPCA for scipy.sparse batches: [subset rows; leftover rows] of every batch resident as CSC
+    (DeviceSparsePCA), or -- under the dense path's fallback conditions -- the host path on the densified batches."""
+    G_all = check_same_rows(batches)
+    sub, left = _split_rows(subset_row, G_all)
+    G = G_all if sub is None else sub.size
+    if not get_all_genes:
+        left = left[:0]
+    ncells = [m.shape[1] for m in batches]
+    w = _weight_vector(ncells, weights)
+    width = 64 if d <= 56 else 128
+
+    def host(reason):
+        return _host_route(densify(batches, "multiBatchPCA"), reason, d, weights, cos_norm, l2, block, subset_row, sub,
+                           get_all_genes, get_variance, return_pcs)
+
+    if l2 is not None:
+        return host("per-cell norms given (round-1 signature)")
+    if d > 120 or G < width or sum(ncells) <= width:
+        return host("fewer genes / cells than the device block, or d > 120")
+    order = None if sub is None else np.concatenate([sub, left])
+    pca = DeviceSparsePCA(G + left.size, G, device)
+    try:
+        for m, wi in zip(batches, w):
+            pca.add_batch(_csc_rows(m, order), weight=wi, cos_norm=cos_norm)
+        try:
+            out = pca.fit(d=d, tol=tol, max_iters=max_iters, iters=iters)
+        except _lib.BatchelorMI355XError as exc:
+            if "rank below the subspace width" in str(exc):
+                pca.close()
+                return host("data of rank below the device block")
+            raise
+        out["weights"] = w
+        out["path"] = "device-sparse"
+        if return_pcs:
+            out["pcs"] = [pca.project(b) for b in range(len(batches))]
+        if left.size:
+            _all_genes(out, G_all, sub, left, *pca.genes())
+        if get_variance:
+            out["var_explained"] = out["d"] ** 2 / len(batches)
+            out["var_total"] = pca.total_variance() / len(batches)
     finally:
         pca.close()
     return out

@@ -406,6 +406,51 @@ int32_t bmx_pca_genes_finish(bmx_pca_genes_t* h, double* centers_left, double* r
  * centred form in a fixed order; var.total of R/multiBatchPCA.R:428-431 is this over the number of batches. */
 int32_t bmx_pca_genes_total_variance(bmx_pca_genes_t* h, double* var_total);
 
+/* multiBatchPCA over batches kept in HBM as CSC -- per batch indptr [n + 1] (int64), 0-based int32 row indices and FP64
+ * values, the rows of a column strictly ascending (explicit zeros are values like any other) -- as bmx_norm_sparse_t keeps
+ * its counts.  Row layout: the handle holds all n_rows rows of every batch; the first n_rows_pca are the rows the PCA
+ * runs on (x[subset.row] in the caller's order, duplicates included), the others are the genes outside the subset,
+ * ascending (n_rows_pca == n_rows: no subset, or no get.all.genes).  Rows ascend within a column, so the PCA rows of a
+ * cell are a prefix of its column; the cut is found once per column at upload, and cos_norm norms over that prefix only.
+ * After a batch's last block the device builds a row-major companion (rows of cos-scaled values with their cells,
+ * ascending) by a counting sort without atomics.  The operator  M Q = sum_b (w_b / n_b) C_b C_b^T Q  is two gathers on the
+ * FP64 vector ALUs, 64 subspace columns at a time with a lane per column: by cell from the CSC (Z = C_b^T Q) and by gene
+ * from the companion (rows cut into segments of bmx_dev_get "pca_sparse_row_segment" entries, a row's segments added in
+ * ascending order by a second kernel).  The iteration around it -- Chebyshev filter, Cholesky QR 2, Rayleigh-Ritz,
+ * residual, starting block -- is bmx_pca_t's, with its kernels for the dense n_rows_pca x 64 blocks.  No floating-point
+ * atomics: the same calls give the same bits, however the batches were cut into blocks.
+ * What only the device sees of the pattern is flagged at upload and reported by the fit: "a row index is outside [0,
+ * number of genes)", "the row indices of a column should be strictly ascending".  Such entries are skipped by every
+ * kernel, never used as an address.  A batch holds at most 2^31 - 1 cells and any number of stored entries. */
+typedef struct bmx_pca_sparse bmx_pca_sparse_t;
+int32_t bmx_pca_sparse_create(int32_t device, int32_t n_rows, int32_t n_rows_pca, bmx_pca_sparse_t** out);
+void bmx_pca_sparse_destroy(bmx_pca_sparse_t* h);
+/* The checks of a block on their own (no device), as bmx_norm_check_sparse_block: a block of n_block cells for a batch
+ * of n cells of which `filled` have arrived; indptr [n_block + 1] relative to the block starts at 0, never decreases and
+ * ends at nnz; indices and data [nnz] may be NULL only when nnz is 0. */
+int32_t bmx_pca_sparse_check_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
+                                   const int32_t* indices, const double* data, int64_t nnz);
+/* A batch of n cells with nnz stored entries in all (reserved once); weight and cos_norm as for bmx_pca_add_batch.  Its
+ * cells follow in one or more blocks, in order (host memory, read completely when the call returns). */
+int32_t bmx_pca_sparse_begin_batch(bmx_pca_sparse_t* h, int64_t n, double weight, int32_t cos_norm, int64_t nnz);
+int32_t bmx_pca_sparse_add_block(bmx_pca_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                 const double* data, int64_t nnz);
+/* As bmx_pca_fit_tol / bmx_pca_fit over the first n_rows_pca rows: the same meaning, limits (d <= 120, a block of 64 or
+ * 128 vectors, "rank below the subspace width") and messages; centers [n_rows_pca], rotation [n_rows_pca x d]
+ * column-major, sdev [d]. */
+int32_t bmx_pca_sparse_fit_tol(bmx_pca_sparse_t* h, int32_t d, double tol, int32_t max_iters, double* centers,
+                               double* rotation, double* sdev, int32_t* iters_used, double* residual);
+int32_t bmx_pca_sparse_fit(bmx_pca_sparse_t* h, int32_t d, int32_t iters, double* centers, double* rotation,
+                           double* sdev);
+/* crossprod(cosineNorm(x_b) - centers, rotation) over the PCA rows: out [n_b x d] column-major. */
+int32_t bmx_pca_sparse_project(bmx_pca_sparse_t* h, int32_t batch, double* out);
+/* Once fitted, the rows outside the subset (resident: nothing is streamed): centers_left [n_rows - n_rows_pca] and
+ * rotation_left [(n_rows - n_rows_pca) x d] column-major by the formula of bmx_pca_genes_finish; either may be NULL. */
+int32_t bmx_pca_sparse_genes(bmx_pca_sparse_t* h, double* centers_left, double* rotation_left);
+/* *var_total as bmx_pca_genes_total_variance, over the PCA rows, in the centred form per gene:
+ * sum over the stored entries of (scale_c x_gc - center[g])^2  +  (n_b - stored entries of g) * center[g]^2. */
+int32_t bmx_pca_sparse_total_variance(bmx_pca_sparse_t* h, double* var_total);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * clusterMNN() (R/clusterMNN.R:101-312): the two per-cell stages around the centroid-level merge.  The batches (genes x
  * cells, column-major) are uploaded once, whole or in column blocks through the pinned staging ring, and stay in HBM

@@ -1,0 +1,219 @@
+"""The host side of multiBatchPCA / fastMNN / cosineNorm on scipy.sparse batches, without a GPU: the float64 restatement
+of the sparse algorithm (tests/pca_sparse_ref.py) against the allowances that tests/test_gpu_pca_sparse.py holds the device
+to, with planted faults; the row assembly; canonicalisation; the refusals; the host fallback; the C entry points."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import batchelor_amd as bx
+from batchelor_amd import multi_batch_pca as mbp
+from batchelor_amd.inputs import canonical_csc
+from tests import pca_sparse_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from batchelor_amd import _lib
+    return _lib.lib()
+
+
+# ------------------------------------------------------------------------------------- the allowances
+@pytest.mark.parametrize("name", list(ref.CASES))
+def test_float64_restatement_meets_the_allowances(name):
+    c = ref.CASES[name]
+    rec = ref.sparse_f64(name, c.iters or ref.pca_ref.F64_ITERS_CONVERGED)
+    r = ref.all_ratios(name, rec, tol=None if c.iters else ref.TOL)
+    print(f"case {name}: float64 error / allowance {r}")
+    assert all(v <= 1.0 for v in r.values()), r
+
+
+# which figure each fault must push far outside its allowance, and on which case it can show
+FAULT_SHOWS = {
+    "drop_last_entry": ("g130-d60-cos-w-i2", ("ritz", "projection")),
+    "cut_at_n_rows":   ("sub66of90-d5-cos-i2", ("ritz", "projection")),
+    "no_zero_term":    ("sub66of90-d5-cos-i2", ("var_total",)),
+    "scale_all_rows":  ("sub66of90-d5-cos-i2", ("centers", "projection")),
+}
+
+
+@pytest.mark.parametrize("fault", ref.FAULTS)
+def test_planted_faults_are_far_outside(fault):
+    name, keys = FAULT_SHOWS[fault]
+    c = ref.CASES[name]
+    r = ref.all_ratios(name, ref.sparse_f64(name, c.iters, fault=fault))
+    print(f"case {name}, fault {fault}: error / allowance {r}")
+    assert max(r[k] for k in keys) > 1e3, (fault, r)
+
+
+# ------------------------------------------------------------------------------------- rows and canonical form
+def test_rows_are_subset_then_left_with_duplicates_and_any_order():
+    rng = np.random.default_rng(5)
+    m = sp.random(40, 30, 0.2, format="csr", random_state=7)
+    subset1 = np.array([33, 2, 17, 2, 40, 1])                  # unordered, one row twice
+    sub, left = mbp._split_rows(subset1, 40)
+    assert np.array_equal(sub, subset1 - 1) and np.array_equal(left, np.setdiff1d(np.arange(40), sub))
+    got = mbp._csc_rows(m, np.concatenate([sub, left]))
+    assert left.size == 35 and got.shape == (6 + 35, 30) and got.has_canonical_format
+    assert np.array_equal(got.toarray(), m.toarray()[np.concatenate([sub, left])])
+    rec = {"rotation": rng.standard_normal((6, 3)), "centers": rng.standard_normal(6)}
+    want_rot, want_cen = rec["rotation"].copy(), rec["centers"].copy()
+    mbp._all_genes(rec, 40, sub, left, np.zeros(35), np.zeros((35, 3)))
+    assert np.array_equal(rec["rotation"][1], want_rot[3]) and rec["centers"][1] == want_cen[3]   # the later one wins
+    assert np.array_equal(rec["rotation"][32], want_rot[0])
+
+
+def _forms(dense):
+    """The same matrix in forms that are not canonical CSC."""
+    r, c = np.nonzero(dense)
+    half = dense[r, c] / 2
+    coo_dup = sp.coo_matrix((np.concatenate([half, half]), (np.concatenate([r, r]), np.concatenate([c, c]))), shape=dense.shape)
+    csc = sp.csc_matrix(dense)
+    unsorted = sp.csc_matrix(dense)
+    for j in range(dense.shape[1]):
+        a, b = unsorted.indptr[j], unsorted.indptr[j + 1]
+        unsorted.indices[a:b] = unsorted.indices[a:b][::-1].copy()
+        unsorted.data[a:b] = unsorted.data[a:b][::-1].copy()
+    unsorted.has_sorted_indices = False
+    wide = sp.csc_matrix((csc.data, csc.indices.astype(np.int64), csc.indptr.astype(np.int64)), shape=dense.shape)
+    return {"coo with duplicates": coo_dup, "csr": sp.csr_matrix(dense), "unsorted indices": unsorted,
+            "float32": csc.astype(np.float32), "int64 indices": wide}
+
+
+def test_any_form_is_canonicalised_and_the_callers_object_untouched():
+    dense = np.round(sp.random(25, 20, 0.3, random_state=3).toarray() * 8) / 8     # (exact in float32, halves exact)
+    for label, m in _forms(dense).items():
+        before = [np.array(a, copy=True) for a in ((m.row, m.col, m.data) if label.startswith("coo") else
+                                                   (m.indptr, m.indices, m.data))]
+        c, owned = canonical_csc(m)
+        after = (m.row, m.col, m.data) if label.startswith("coo") else (m.indptr, m.indices, m.data)
+        assert all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip(before, after)), label
+        assert c.format == "csc" and c.has_canonical_format and c.data.dtype == np.float64 and c.indices.dtype == np.int32
+        assert np.array_equal(c.toarray(), dense), label
+        for a in (m.row, m.col, m.data) if label.startswith("coo") else (m.indices, m.data):
+            assert not np.shares_memory(a, c.data) or not owned
+
+
+def test_old_import_path_of_the_csc_helpers():
+    from batchelor_amd import multi_batch_norm
+    assert multi_batch_norm.canonical_csc is canonical_csc and multi_batch_norm.csc_blocks is bx.inputs.csc_blocks
+
+
+# ------------------------------------------------------------------------------------- refusals and the host path
+def test_a_mixture_of_sparse_and_dense_is_a_type_error():
+    a, b = sp.random(70, 40, 0.2, format="csc", random_state=1), np.ones((70, 40))
+    for call in (lambda: bx.multiBatchPCA(a, b, d=5), lambda: bx.fastMNN(a, b, d=5), lambda: bx.multiBatchPCA([b, a], d=5)):
+        with pytest.raises(TypeError, match="takes batches that are all sparse or all dense, not a mixture"):
+            call()
+
+
+@pytest.mark.parametrize("kwargs", [dict(d=5), dict(d=130), dict(d=5, weights=False, subset_row=[9, 3, 3, 20, 21, 22, 5],
+                                                                 get_all_genes=True, get_variance=True)])
+def test_sparse_host_fallback_is_the_dense_host_path(kwargs):
+    """Fewer genes than the block (or d > 120): the batches are densified and take the existing host code, so the
+    results are equal bit for bit."""
+    B = [sp.random(50, n, 0.3, format=f, random_state=n) for n, f in ((40, "csc"), (55, "coo"), (30, "csr"))]
+    got = bx.multiBatchPCA(*B, return_pcs=False, **kwargs)
+    want = bx.multiBatchPCA(*[m.toarray() for m in B], return_pcs=False, **kwargs)
+    assert got["path"].startswith("host: fewer genes") and got["path"] == want["path"]
+    for k in want:
+        if k != "path":
+            assert np.array_equal(got[k], want[k]), k
+    direct = bx.multiBatchPCA_host(*[m.toarray() for m in B], **{k: v for k, v in kwargs.items()})
+    assert np.array_equal(got["rotation"], direct["rotation"])
+
+
+def test_densifying_beyond_the_cap_is_refused():
+    huge = sp.csc_matrix((30, 10 ** 9))                         # 30 genes: the host path; 240 GB dense
+    assert 8 * 30 * 10 ** 9 > mbp.DENSIFY_CAP_BYTES == 8 << 30
+    with pytest.raises(ValueError, match="are not densified"):
+        bx.multiBatchPCA(huge, huge, d=5, return_pcs=False)
+    with pytest.raises(ValueError, match="are not densified"):
+        bx.fastMNN(huge, huge, d=5, pca="host")
+
+
+def test_cosine_norm_on_sparse_input():
+    dense = sp.random(30, 25, 0.3, random_state=9).toarray()
+    dense[:, 4] = 0.0                                           # an empty column: the 1e-8 clamp, and 0 stays 0
+    subset1 = np.array([7, 2, 2, 30])
+    for m in (sp.csc_matrix(dense), sp.coo_matrix(dense), sp.csr_matrix(dense)):
+        for sub, d in ((None, dense), (subset1, dense[subset1 - 1])):
+            l2 = np.sqrt((d * d).sum(axis=0))
+            got = bx.cosineNorm(m, mode="all", subset_row=sub)
+            assert sp.issparse(got["matrix"]) and got["matrix"].format == "csc"
+            assert np.allclose(got["l2norm"], l2, rtol=(d.shape[0] + 2) * ref.pca_ref.U, atol=0)
+            assert np.allclose(got["matrix"].toarray(), d / np.maximum(1e-8, l2), rtol=(d.shape[0] + 4) * ref.pca_ref.U, atol=0)
+            assert got["matrix"][:, 4].nnz == 0
+            assert np.array_equal(bx.cosineNorm(m, mode="l2norm", subset_row=sub), got["l2norm"])
+            assert np.array_equal(bx.cosineNorm(m, subset_row=sub).toarray(), got["matrix"].toarray())
+
+
+# ------------------------------------------------------------------------------------- the C entry points
+def _declared():
+    header = open(os.path.join(ROOT, "include", "batchelor_mi355x.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    return re.findall(r"\b(int32_t|void)\s+(bmx_pca_sparse_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)
+
+
+def test_new_symbols_are_declared_and_exported(lib):
+    names = sorted(n for _, n, _ in _declared())
+    assert names == sorted("bmx_pca_sparse_" + s for s in (
+        "create", "destroy", "check_block", "begin_batch", "add_block", "fit_tol", "fit", "project", "genes",
+        "total_variance"))
+    assert all(hasattr(lib, n) for n in names)
+    assert {"DeviceSparsePCA", "sparse_row_segment"} <= set(dir(bx))
+    assert bx.sparse_row_segment() == 256
+
+
+def test_every_entry_point_refuses_a_null_handle_before_any_device(lib):
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double}
+    seen = 0
+    for ret, name, params in _declared():
+        types = [" ".join(p.split()).rsplit(" ", 1)[0].replace(" *", "*") for p in params.split(",")]
+        if types[0] != "bmx_pca_sparse_t*":
+            continue
+        fn = getattr(lib, name)
+        saved = fn.argtypes, fn.restype
+        fn.argtypes = [ctypes.c_void_p if t.endswith("*") else scalars[t] for t in types]
+        fn.restype = None if ret == "void" else ctypes.c_int32
+        try:
+            rc = fn(*[None if t.endswith("*") else scalars[t](1) for t in types])
+        finally:
+            fn.argtypes, fn.restype = saved
+        seen += 1
+        if ret != "void":
+            assert rc == -6 and lib.bmx_last_error().decode() == "null handle", (name, rc, lib.bmx_last_error())
+    assert seen == 8      # destroy, begin_batch, add_block, fit_tol, fit, project, genes, total_variance
+
+
+def test_check_block_refusals(lib):
+    fn = lib.bmx_pca_sparse_check_block
+    fn.argtypes = [ctypes.c_int64] * 3 + [ctypes.c_void_p] * 3 + [ctypes.c_int64]
+    fn.restype = ctypes.c_int32
+    idx, val = np.array([0, 2, 1], dtype=np.int32), np.ones(3)
+
+    def check(n, filled, m, indptr, nnz, indices=idx, data=val):
+        p = None if indptr is None else np.asarray(indptr, dtype=np.int64)
+        rc = fn(n, filled, m, None if p is None else p.ctypes.data, None if indices is None else indices.ctypes.data,
+                None if data is None else data.ctypes.data, nnz)
+        return rc, lib.bmx_last_error().decode()
+
+    assert check(5, 0, 2, [0, 2, 3], 3)[0] == 0
+    assert check(5, 3, 2, [0, 0, 0], 0, None, None)[0] == 0
+    for args, text in (((5, 0, 2, None, 3), "'indptr' is missing"),
+                       ((5, 0, 2, [0, 2, 3], -1), "number of stored entries is negative"),
+                       ((5, 0, 2, [0, 2, 3], 3, None, val), "'indices' or 'data' is missing"),
+                       ((5, 4, 2, [0, 2, 3], 3), "does not fit into the batch announced"),
+                       ((5, 0, 0, [0], 0), "does not fit into the batch announced"),
+                       ((5, 0, 2, [1, 2, 3], 3), "does not start at 0"),
+                       ((5, 0, 2, [0, 3, 2], 2), "decreases"),
+                       ((5, 0, 2, [0, 2, 2], 3), "does not end at its number of stored entries")):
+        rc, msg = check(*args)
+        assert rc == -6 and text in msg, (args, rc, msg)
