@@ -328,12 +328,18 @@ CASES = {
     "g129-split2-d120-wn-i2": Case(129, (4100, 300), 120, weights=False, iters=2),
     "g128-split3-d57-cos-i1": Case(128, (6149,), 57, cos_norm=True, iters=1),
     "g191-cells-L+1-d80-i1": Case(191, (60, 69), 80, iters=1),
+    # ---- genes beyond one split of the Gram / Rayleigh-Ritz products (TN over genes: a split per 512 rows, KC = 32 rows a
+    # step): 1100 genes are two splits of 576 + 524 rows, the second ending in a 12-row step; 2100 four, 1600 three.  One
+    # step: after two, a product that loses whole genes satisfies the Ritz identity (test_cpu_pca.py, drop_last_gene)
+    "g1100-gsplit2-cos-w-i1": Case(1100, (257, 513), 10, weights=(2.0, 1.0), cos_norm=True, iters=1),
+    "g2100-gsplit4-d57-i1": Case(2100, (70, 257, 300), 57, iters=1),
     # ---- converged (default tol): the filter recurrence and the reported residual
     "conv-g130-chunks":    Case(130, (257, 513), 10),
     "conv-g70-split2-cos-w": Case(70, (4100, 300), 10, weights=(1.0, 2.5), cos_norm=True, zero=(0, 2050)),
     "conv-g333-small-wn":  Case(333, (31, 33, 64, 65), 10, weights=False),
     "conv-g191-d57-cos":   Case(191, (257, 513), 57, cos_norm=True, rank=60),
     "conv-g96-split3-d1":  Case(96, (6149,), 1),
+    "conv-g1600-gsplit3":  Case(1600, (257, 513), 10),
 }
 FIXED = [k for k, c in CASES.items() if c.iters is not None]
 CONVERGED = [k for k, c in CASES.items() if c.iters is None]

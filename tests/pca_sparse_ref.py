@@ -23,9 +23,15 @@ TOL = pca_ref.TOL
 
 
 class Case:
-    def __init__(self, G_all, nS, sizes, d, density, weights=None, cos_norm=False, iters=None, seed=0):
+    """twice: the subset names one row twice (nS - 1 different rows).  f64_iters: the plain steps that take the float64
+    restatement of a converged case below TOL (None: pca_ref.F64_ITERS_CONVERGED).  signal: factor on the low-rank part.
+    empty_prefix: the batch of that index stores nothing in the PCA rows (every entry lies in a leftover row)."""
+
+    def __init__(self, G_all, nS, sizes, d, density, weights=None, cos_norm=False, iters=None, seed=0, twice=True,
+                 f64_iters=None, signal=1.0, empty_prefix=None):
         self.G_all, self.nS, self.sizes, self.d, self.density = G_all, nS, sizes, d, density
         self.weights, self.cos_norm, self.iters, self.seed = weights, cos_norm, iters, seed
+        self.twice, self.f64_iters, self.signal, self.empty_prefix = twice, f64_iters, signal, empty_prefix
 
     def kwargs(self):
         return {"d": self.d, "weights": self.weights, "cos_norm": self.cos_norm}
@@ -45,6 +51,36 @@ CASES = {
     "sub66of90-d5-cos-i2":  Case(90, 66, (67, 200, 513), 5, 0.3, cos_norm=True, iters=2),
     "sub130of150-d60-w":    Case(150, 130, (200, 513), 60, 0.3, weights=(2.0, 1.0)),
 }
+
+# Beyond one tile of the counting sort (GT = 4096 rows), one row a thread of the row scan (1024), one 64-entry pass of a
+# column's prefix, one block of mu_dot (256 rows) and one split of the Gram products (512 rows); what each case reaches
+# is asserted from its pattern in tests/test_cpu_pca_sparse.py::test_edge_cases_reach_their_branches.  (257, 512, 513)
+# cells: the full row has exactly SEG, 2 SEG and 2 SEG + 1 entries, batch 0 having the empty cell.
+# One step (-i1): Q is still the random start block, so a fault that zeroes whole rows of the by-gene product shows at
+# full size; after two steps such rows are zero in Q as well, R is supported on the surviving rows and R^T M R = diag(s^2)
+# holds to rounding (test_rows_lost_by_gene_show_after_one_step_only).  A one-step case names no subset row twice: R = Q V
+# still carries the random start block, the two copies of a row differ, and the assembly over all rows keeps the later.
+SEG, TILE = 256, 4096     # entries a row segment holds; rows a tile of the counting sort holds
+EDGE_CASES = {
+    "g65-d5-i1":             Case(65, None, (67, 200, 513), 5, 0.3, iters=1),
+    "g1025-d60-cos-w-i1":    Case(1025, None, (257, 512), 60, 0.1, weights=(1.0, 3.0), cos_norm=True, iters=1),
+    "g4097-i1":              Case(4097, None, (257, 513), 5, 0.1, iters=1),
+    "g4300-i1":              Case(4300, None, (257, 512, 513), 5, 0.1, iters=1),
+    "g4300-i2":              Case(4300, None, (257, 512, 513), 5, 0.1, iters=2),
+    # density 0.1 leaves 40 plain steps at residual 2e-6 (the mask's noise fills the block); at 0.9 the restatement is at
+    # 2.6e-8 after 12 steps and falls by 0.28 a step: 16 steps, 1.4e-10
+    "g4300-conv":            Case(4300, None, (257, 513), 5, 0.9, f64_iters=16),
+    "sub130of4300-i2":       Case(4300, 130, (257, 513), 5, 0.3, iters=2),
+    "sub4200of8300-cos-i2":  Case(8300, 4200, (257, 513), 5, 0.03, cos_norm=True, iters=2),
+    "sub4200of8300-i1":      Case(8300, 4200, (257, 513), 5, 0.03, iters=1, twice=False),
+    # a third batch with nothing stored in the PCA rows: its cuts are the columns' starts, it has no segment in the PCA
+    # rows, and under cos_norm every one of its scales is 1e8
+    "sub130of4300-empty-i2":     Case(4300, 130, (257, 513, 150), 5, 0.3, iters=2, empty_prefix=2),
+    "sub130of4300-empty-cos-i2": Case(4300, 130, (257, 513, 150), 5, 0.3, cos_norm=True, iters=2, empty_prefix=2),
+}
+EDGE = list(EDGE_CASES)
+TWO_TILES = ["g4097-i1", "g4300-i1", "g4300-i2", "g4300-conv"]
+CASES.update(EDGE_CASES)
 FIXED = [k for k, c in CASES.items() if c.iters is not None]
 CONVERGED = [k for k, c in CASES.items() if c.iters is None]
 SUBSETS = [k for k, c in CASES.items() if c.nS is not None]
@@ -65,14 +101,17 @@ def case(name):
     rng = np.random.default_rng([c.G_all, c.d, sum(c.sizes), c.seed, int(c.density * 100)])
     subset1 = None
     if c.nS is not None:
-        subset1 = rng.permutation(c.G_all)[:c.nS - 1] + 1
-        subset1 = np.concatenate([subset1, subset1[3:4]])       # one row named twice
+        if c.twice:
+            subset1 = rng.permutation(c.G_all)[:c.nS - 1] + 1
+            subset1 = np.concatenate([subset1, subset1[3:4]])   # one row named twice
+        else:
+            subset1 = rng.permutation(c.G_all)[:c.nS] + 1
         assert np.any(np.diff(subset1) < 0)
         subset1.setflags(write=False)
     src = np.arange(c.G_all) if subset1 is None else subset1 - 1
     zero_row, full_row = int(src[ZERO_ROW]), int(src[FULL_ROW])
     rank = 8
-    load = np.abs(rng.standard_normal((c.G_all, rank))) * np.linspace(2.0, 0.5, rank)
+    load = np.abs(rng.standard_normal((c.G_all, rank))) * np.linspace(2.0, 0.5, rank) * c.signal
     out = []
     for i, n in enumerate(c.sizes):
         x = load @ np.abs(rng.standard_normal((rank, n))) + 0.3 * np.abs(rng.standard_normal((c.G_all, n))) + 0.1 * i
@@ -82,6 +121,8 @@ def case(name):
         if i == EMPTY_CELL[0]:
             mask[:, EMPTY_CELL[1]] = False
             mask[full_row, EMPTY_CELL[1]] = False
+        if i == c.empty_prefix:
+            mask[src] = False
         m = sp.csc_matrix(np.where(mask, np.log2(1.0 + x), 0.0))
         assert m.has_canonical_format and m.indices.dtype == np.int32
         out.append(m)
@@ -143,7 +184,13 @@ def all_ratios(name, fit, tol=None):
 
 
 # ---------------------------------------------------------------------------------------------- float64 restatement
-FAULTS = ("drop_last_entry", "cut_at_n_rows", "no_zero_term", "scale_all_rows")
+FAULTS = ("drop_last_entry", "cut_at_n_rows", "no_zero_term", "scale_all_rows",
+          # edge-shaped: what a kernel that mishandles a tile, a lane stride or a segment boundary would do
+          "tile_rows_lost_by_gene",     # the by-gene product (not the centres) loses every row >= TILE
+          "first_row_of_tile_entry",    # the by-gene product loses one entry of row TILE
+          "entry_65_by_cell",           # the by-cell product loses the 65th entry of one column's prefix
+          "cut_at_tile_edge",           # the prefix (product and norm) ends at the last tile edge below n_rows_pca
+          "third_segment")              # a row of exactly 2 SEG entries loses its second segment in the by-gene product
 
 
 def rows_first(m, subset1, get_all=True):
@@ -166,9 +213,12 @@ def sparse_f64(name, iters, fault=None, seed=0):
     mats, Gp = zip(*[rows_first(m, subset1) for m in B])
     Gp, G = Gp[0], mats[0].shape[0]
     L = pca_ref.width(c.d)
-    cells, rowsP, scaled = [], [], []
+    cells, rowsP, by_gene, scaled = [], [], [], []
     for m in mats:
         pre = m[:Gp].tocsc()                                      # the PCA prefix of every column
+        if fault == "cut_at_tile_edge":
+            assert Gp % TILE not in (0, Gp)
+            pre = sp.vstack([m[:Gp - Gp % TILE], sp.csr_matrix((Gp % TILE, m.shape[1]))]).tocsc()
         over = m if fault == "scale_all_rows" else pre
         l2 = np.sqrt(np.asarray(over.multiply(over).sum(axis=0)).ravel())
         inv = 1.0 / np.maximum(1e-8, l2) if c.cos_norm else np.ones(m.shape[1])
@@ -179,9 +229,20 @@ def sparse_f64(name, iters, fault=None, seed=0):
         if fault == "cut_at_n_rows" and G > Gp:                   # the leftover rows read on into the block (wrapped)
             wrap = sp.csr_matrix((np.ones(G - Gp), (np.arange(G - Gp), np.arange(G - Gp) % Gp)), shape=(G - Gp, Gp))
             by_cell = (pre + (wrap.T @ m[Gp:]).tocsc()).tocsc()
+        if fault == "entry_65_by_cell" and len(cells) == 0:       # (batch 0) the first column with 65 entries or more
+            col = np.flatnonzero(np.diff(by_cell.indptr) >= 65)[0]
+            by_cell.data[by_cell.indptr[col] + 64] = 0.0
         comp = (m @ sp.diags(inv)).tocsr()                        # the companion: scaled values by row
+        gene = comp[:Gp].copy()                                   # what the by-gene product reads of the companion
+        if fault == "first_row_of_tile_entry" and len(cells) == 0:
+            assert gene.indptr[TILE + 1] > gene.indptr[TILE]
+            gene.data[gene.indptr[TILE]] = 0.0
+        if fault == "third_segment":
+            for g in np.flatnonzero(np.diff(gene.indptr) == 2 * SEG):
+                gene.data[gene.indptr[g] + SEG:gene.indptr[g + 1]] = 0.0
         cells.append((by_cell, inv))
         rowsP.append(comp[:Gp])
+        by_gene.append(gene)
         scaled.append(comp)
     mu = np.zeros(G)
     for wb, s in zip(w, scaled):
@@ -189,15 +250,18 @@ def sparse_f64(name, iters, fault=None, seed=0):
     muP = mu[:Gp]
     coef = [wb / m.shape[1] for wb, m in zip(w, mats)]
 
-    def by_cell(i, Q):
+    def project(i, Q):
         x, inv = cells[i]
         return inv[:, None] * (x.T @ Q) - (muP @ Q)[None, :]
 
     def apply(Q):
         Y = np.zeros_like(Q)
         for i in range(len(mats)):
-            Z = by_cell(i, Q)
-            Y += coef[i] * (rowsP[i] @ Z - np.outer(muP, Z.sum(axis=0)))
+            Z = project(i, Q)
+            Y += coef[i] * (by_gene[i] @ Z - np.outer(muP, Z.sum(axis=0)))
+        if fault == "tile_rows_lost_by_gene":
+            assert Gp > TILE
+            Y[TILE:] = 0.0
         return Y
 
     Q = np.linalg.qr(np.random.default_rng(seed).standard_normal((Gp, L)))[0]
@@ -212,7 +276,7 @@ def sparse_f64(name, iters, fault=None, seed=0):
     Xr, Yr = Q @ V, Y @ V
     R, s = np.ascontiguousarray(Xr[:, :c.d]), np.sqrt(np.maximum(theta[:c.d], 0.0))
     D = Yr[:, :c.d] - Xr[:, :c.d] * theta[None, :c.d]
-    pcs = [by_cell(i, R) for i in range(len(mats))]
+    pcs = [project(i, R) for i in range(len(mats))]
     rec = {"rotation": R, "centers": muP.copy(), "d": s, "pcs": pcs,
            "residual": float(np.sqrt((D * D).sum(axis=0)).max() / theta[0]), "var_explained": s ** 2 / len(mats)}
     total = 0.0

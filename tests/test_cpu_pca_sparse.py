@@ -29,7 +29,7 @@ def lib():
 @pytest.mark.parametrize("name", list(ref.CASES))
 def test_float64_restatement_meets_the_allowances(name):
     c = ref.CASES[name]
-    rec = ref.sparse_f64(name, c.iters or ref.pca_ref.F64_ITERS_CONVERGED)
+    rec = ref.sparse_f64(name, c.iters or c.f64_iters or ref.pca_ref.F64_ITERS_CONVERGED)
     r = ref.all_ratios(name, rec, tol=None if c.iters else ref.TOL)
     print(f"case {name}: float64 error / allowance {r}")
     assert all(v <= 1.0 for v in r.values()), r
@@ -41,6 +41,11 @@ FAULT_SHOWS = {
     "cut_at_n_rows":   ("sub66of90-d5-cos-i2", ("ritz", "projection")),
     "no_zero_term":    ("sub66of90-d5-cos-i2", ("var_total",)),
     "scale_all_rows":  ("sub66of90-d5-cos-i2", ("centers", "projection")),
+    "tile_rows_lost_by_gene":  ("g4300-i1", ("ritz",)),
+    "first_row_of_tile_entry": ("g4300-i2", ("ritz",)),
+    "entry_65_by_cell":        ("g1025-d60-cos-w-i1", ("ritz", "projection")),
+    "cut_at_tile_edge":        ("sub4200of8300-cos-i2", ("ritz", "projection")),
+    "third_segment":           ("g4300-i2", ("ritz",)),
 }
 
 
@@ -51,6 +56,78 @@ def test_planted_faults_are_far_outside(fault):
     r = ref.all_ratios(name, ref.sparse_f64(name, c.iters, fault=fault))
     print(f"case {name}, fault {fault}: error / allowance {r}")
     assert max(r[k] for k in keys) > 1e3, (fault, r)
+
+
+def test_rows_lost_by_gene_show_after_one_step_only():
+    """Why the table has one-step cases.  A by-gene product that loses every row of the second tile returns Y with those
+    rows zero.  After two steps Q = qr(Y) is zero there too, so R = Q V is supported on the surviving rows, where the
+    faulty operator and M agree as a quadratic form: R^T M R = R^T Y V = diag(s^2) holds to rounding and nothing is seen.
+    After one step Q is the random start block, nonzero in every row, and the defect has the size of the lost rows."""
+    two = ref.all_ratios("g4300-i2", ref.sparse_f64("g4300-i2", 2, fault="tile_rows_lost_by_gene"))
+    one = ref.all_ratios("g4300-i1", ref.sparse_f64("g4300-i1", 1, fault="tile_rows_lost_by_gene"))
+    print(f"rows >= {ref.TILE} lost by the by-gene product: error / allowance after two steps {two}, after one {one}")
+    assert all(v <= 1.0 for v in two.values()), two
+    assert one["ritz"] > 1e3, one
+
+
+def _pca_order(name):
+    """A case's batches as the handle holds them ([subset; leftover rows], canonical CSC) and the number of PCA rows."""
+    c, B, subset1 = ref.case(name)
+    mats, Gp = zip(*[ref.rows_first(m, subset1) for m in B])
+    return c, [m.tocsc() for m in mats], Gp[0]
+
+
+def _prefix_lengths(m, Gp):
+    return np.diff(m[:Gp].tocsc().indptr)
+
+
+def test_edge_cases_reach_their_branches():
+    """From the patterns alone: every edge case still reaches what tests/pca_sparse_ref.py names it for."""
+    seg, tile = ref.SEG, ref.TILE
+    assert seg == bx.sparse_row_segment()
+    rowlen = lambda m: np.diff(m.tocsr().indptr)
+    for name in ref.TWO_TILES + ["sub130of4300-i2"]:
+        c, mats, Gp = _pca_order(name)
+        assert mats[0].shape[0] > tile
+        for m in mats:     # a column with more than 256 entries in the first tile: a second stride of the sort's walk
+            assert np.diff(m[:tile].tocsc().indptr).max() > 256, name
+    for name in ref.TWO_TILES:
+        c, mats, Gp = _pca_order(name)
+        assert all(rowlen(m)[tile] > 0 for m in mats), name                       # the first row of the second tile
+    assert ref.CASES["g4097-i1"].G_all == tile + 1                                 # a tile of a single row
+    c, mats, Gp = _pca_order("sub130of4300-i2")
+    assert np.diff(mats[1][:tile].tocsc().indptr).max() > 5 * 256                  # six strides
+    for name in ("g1025-d60-cos-w-i1", "g4300-i1", "g4300-i2", "g4300-conv", "sub4200of8300-cos-i2", "sub4200of8300-i1"):
+        c, mats, Gp = _pca_order(name)
+        assert all(_prefix_lengths(m, Gp).max() > 64 for m in mats), name          # a second 64-entry pass by cell
+    # the row scan: several rows a thread, the last thread's range clipped; mu_dot in 4 blocks; two splits of the products
+    G = ref.CASES["g1025-d60-cos-w-i1"].G_all
+    per = -(-G // 1024)
+    assert per == 2 and 1023 * per > G and G // 256 == 4 and G % (-(-G // 4)) != 0 and G // 512 == 2
+    assert ref.pca_ref.width(ref.CASES["g1025-d60-cos-w-i1"].d) == 128
+    # rows of exactly seg and exactly 2 seg entries (and one more)
+    for name, want in (("g1025-d60-cos-w-i1", (seg, 2 * seg)), ("g4300-i1", (seg, 2 * seg, 2 * seg + 1)),
+                       ("g4300-i2", (seg, 2 * seg, 2 * seg + 1))):
+        c, mats, Gp = _pca_order(name)
+        assert tuple(int(rowlen(m)[ref.FULL_ROW]) for m in mats) == want, name
+    # the cut inside a tile, and leftover rows stored beyond the first tile (over several tiles)
+    for name in ("sub4200of8300-cos-i2", "sub4200of8300-i1"):
+        c, mats, Gp = _pca_order(name)
+        assert Gp == 4200 and Gp % tile not in (0, Gp) and mats[0].shape[0] > 2 * tile
+        assert all(rowlen(m)[2 * tile:].sum() > 0 and rowlen(m)[Gp:2 * tile].sum() > 0 for m in mats), name
+    c, mats, Gp = _pca_order("sub130of4300-i2")
+    assert Gp == 130 and all(rowlen(m)[tile:].sum() > 0 for m in mats)
+    assert len(set(ref.case("sub4200of8300-i1")[2].tolist())) == 4200             # one step: no row named twice
+    assert len(set(ref.case("sub4200of8300-cos-i2")[2].tolist())) == 4199
+    # a batch with nothing in the PCA rows and something behind them
+    for name in ("sub130of4300-empty-i2", "sub130of4300-empty-cos-i2"):
+        c, mats, Gp = _pca_order(name)
+        m = mats[c.empty_prefix]
+        assert m[:Gp].nnz == 0 and m[Gp:].nnz > 0 and rowlen(m)[tile:].sum() > 0, name
+        assert all(x[:Gp].nnz > 0 for i, x in enumerate(mats) if i != c.empty_prefix)
+    for name in ref.EDGE:      # every fixed-count edge case is where its name says
+        assert (ref.CASES[name].iters is None) == name.endswith("-conv")
+        assert ref.CASES[name].iters is None or name.endswith(f"-i{ref.CASES[name].iters}")
 
 
 # ------------------------------------------------------------------------------------- rows and canonical form

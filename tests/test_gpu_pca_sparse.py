@@ -26,16 +26,26 @@ def device_record(name):
 
 def test_cases_reach_what_they_are_for():
     seg = bx.sparse_row_segment()
+    assert seg == ref.SEG              # (tests/test_cpu_pca_sparse.py asserts the edge cases' patterns with that figure)
     for name in ref.CASES:
         c, B, subset1 = ref.case(name)
         src = np.arange(c.G_all) if subset1 is None else subset1 - 1
-        assert max(c.sizes) > 2 * seg, (name, seg)                 # the full row has at least three segments
+        if name not in ref.EDGE:
+            assert max(c.sizes) > 2 * seg, (name, seg)             # the full row has at least three segments
         for i, m in enumerate(B):
+            if i == c.empty_prefix:                                # nothing in the PCA rows: no segment there at all
+                assert m[src].nnz == 0 and m.nnz > 0
+                continue
             full = m[int(src[ref.FULL_ROW])].nnz
             assert full == m.shape[1] - (1 if i == ref.EMPTY_CELL[0] else 0)
             assert m[int(src[ref.ZERO_ROW])].nnz == 0
         b, cell = ref.EMPTY_CELL
         assert B[b][:, cell].nnz == 0
+    # rows whose length sits on a segment boundary: (rowlen + seg - 1) / seg with rowlen = seg, 2 seg and 2 seg + 1
+    for name, want in (("g1025-d60-cos-w-i1", (seg, 2 * seg)), ("g4300-i1", (seg, 2 * seg, 2 * seg + 1)),
+                       ("g4300-i2", (seg, 2 * seg, 2 * seg + 1))):
+        c, B, subset1 = ref.case(name)
+        assert tuple(m[ref.FULL_ROW].nnz for m in B) == want, (name, seg)
 
 
 @pytest.mark.parametrize("name", ref.FIXED)
@@ -105,33 +115,57 @@ def test_bitwise_repeat_blocks_and_formats():
         assert all(same.values()), (label, same)
 
 
+def test_bitwise_repeat_and_blocks_across_tiles():
+    """Two tiles of the counting sort, columns of two strides, rows of exactly one, two and two-and-a-bit segments: the
+    companion is built after the last block, so neither the tile walk nor a result may depend on the blocks."""
+    name = "g4300-i2"
+    runs = {"whole": _direct(name), "again": _direct(name), "blocks of 37": _direct(name, block_cells=37)}
+    front, base = device_record(name), runs["whole"]
+    for label, out in list(runs.items()) + [("multiBatchPCA", front)]:
+        same = {k: bool(np.array_equal(base[k], out[k])) for k in ("centers", "rotation", "d")}
+        same["pcs"] = all(np.array_equal(p, q) for p, q in zip(base["pcs"], out["pcs"]))
+        print(f"case {name}, {label}: bitwise equal to one whole upload {same}")
+        assert all(same.values()), (label, same)
+
+
 def test_bad_pattern_is_refused_by_the_fit():
     """A row index equal to n_rows, and a descending pair, handed straight to the handle: the entries are skipped by
-    every kernel by construction, and the fit says what is wrong."""
-    c, B, subset1 = ref.case("g65-d5-i2")
+    every kernel by construction, and the fit says what is wrong.  In a column of 66 entries or more the pair sits at
+    positions 63 / 64 and the high index at the last position (>= 64): the order check looks back across the lane
+    stride, and the second 64-entry pass of the column is checked like the first."""
+    _refusals("g65-d5-i2", 11, 2, 5)       # column 11: its first two entries
+    long_col = int(np.flatnonzero(np.diff(ref.case("g1025-d60-cos-w-i1")[1][0].indptr) >= 66)[0])
+    _refusals("g1025-d60-cos-w-i1", long_col, 66, 60)
+
+
+def _refusals(name, col, col_len, d):
+    c, B, subset1 = ref.case(name)
+    G = c.G_all
     good = [canonical_csc(m)[0] for m in B]
 
     def run(bad):
-        pca = bx.DeviceSparsePCA(65)
+        pca = bx.DeviceSparsePCA(G)
         try:
             for m in [bad] + good[1:]:
                 pca.add_batch(m)
-            pca.fit(d=5, iters=1)
+            pca.fit(d=d, iters=1)
         finally:
             pca.close()
 
-    k = int(good[0].indptr[11])            # the first entry of a column that has at least two
-    assert good[0].indptr[12] - k >= 2
+    k, end = int(good[0].indptr[col]), int(good[0].indptr[col + 1])
+    assert end - k >= col_len
+    a = k if col_len == 2 else k + 63      # the descending pair: the column's first two entries, or positions 63 / 64
     def stand_in(indices):   # (what add_batch reads of a CSC matrix, without scipy's own checks in the way)
         return SimpleNamespace(ndim=2, shape=good[0].shape, nnz=good[0].nnz, indptr=good[0].indptr, indices=indices,
                                data=good[0].data)
 
     high = good[0].indices.copy()
-    high[int(good[0].indptr[12]) - 1] = 65
+    high[end - 1] = G
+    assert col_len == 2 or end - 1 - k >= 64
     with pytest.raises(_lib.BatchelorMI355XError, match=r"a row index is outside \[0, number of genes\)"):
         run(stand_in(high))
     desc = good[0].indices.copy()
-    desc[k], desc[k + 1] = good[0].indices[k + 1], good[0].indices[k]
+    desc[a], desc[a + 1] = good[0].indices[a + 1], good[0].indices[a]
     with pytest.raises(_lib.BatchelorMI355XError, match="strictly ascending"):
         run(stand_in(desc))
     run(good[0])                            # and the same calls with the good pattern go through
