@@ -1,6 +1,7 @@
 // The kernels and the small host routines of the blocked subspace iteration of multiBatchPCA, shared by the dense handle
 // (pca.hip) and the sparse one (pca_sparse.hip): the two FP64 matrix-core products over 64-wide tiles, the fixed-order
-// reductions, the filter's recurrence, the residual, and Cholesky / triangular inverse / Jacobi on the L x L matrices.
+// reductions, the filter's recurrence, the residual, two launch sequences both handles use, and Cholesky / triangular
+// inverse / Jacobi on the L x L matrices.  The iteration built on them is pca_iteration.hpp.
 // Everything is in an unnamed namespace: each of the two files gets its own copy.
 #pragma once
 #include <algorithm>
@@ -454,6 +455,40 @@ __global__ __launch_bounds__(256) void centred_sq_partial(const double* __restri
     if (lane == 0) sm[w] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+// ---- two launch sequences the handles share ------------------------------------------------------------------------
+// out[j] = beta out[j] + alpha * sum_c Z[c][j] for Z [n][64], two stages in a fixed order; zpart holds colsum_blocks(n)
+// rows of 64
+inline int colsum_blocks(int64_t n) { return (int)std::min<int64_t>(4096, std::max<int64_t>(1, n / 256)); }
+inline void column_sums64(hipStream_t stream, const double* Z, int64_t n, double* zpart, double alpha, double beta,
+                          double* out) {
+    const int nb = colsum_blocks(n);
+    const int64_t rpb = (n + nb - 1) / nb;
+    hipLaunchKernelGGL(colsum64_partial, dim3(nb), dim3(256), 0, stream, Z, (const double*)nullptr, n, rpb, zpart);
+    hipLaunchKernelGGL(reduce_parts, dim3(1), dim3(64), 0, stream, (const double*)zpart, nb, (int64_t)PL, alpha, beta, out,
+                       PL, (int64_t)PL);
+    BMX_LAUNCH_CHECK();
+}
+// The last step of the pass over G leftover genes: their rotation rows into rot [d][G] (genes_rotation) from their sums
+// acc, centres mu and the projections' column sums tsum, divided by s2[j] = sdev_j^2 with sdev as fit reports it (ds2: d
+// doubles on the device); then mu and rot go to the host (either pointer may be null) and the stream is drained
+inline void leftover_rotation(hipStream_t stream, const std::vector<double>& theta, int d, const double* acc,
+                              const double* mu, const double* tsum, double* ds2, int G, double* rot,
+                              double* centers_left, double* rotation_left) {
+    std::vector<double> s2((size_t)d);
+    for (int j = 0; j < d; ++j) {
+        const double sd = std::sqrt(std::max(0.0, theta[(size_t)j]));
+        s2[(size_t)j] = sd * sd;
+    }
+    BMX_HIP(hipMemcpyAsync(ds2, s2.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(genes_rotation, dim3((unsigned)cdiv((int64_t)G * d, 256)), dim3(256), 0, stream, acc, mu, tsum,
+                       (const double*)ds2, G, d, rot);
+    BMX_LAUNCH_CHECK();
+    if (centers_left) BMX_HIP(hipMemcpyAsync(centers_left, mu, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (rotation_left)
+        BMX_HIP(hipMemcpyAsync(rotation_left, rot, (size_t)G * d * sizeof(double), hipMemcpyDeviceToHost, stream));
+    BMX_HIP(hipStreamSynchronize(stream));
 }
 
 // ---- small dense helpers on the host (L x L, L = 64 or 128) --------------------------------------------------------

@@ -23,8 +23,9 @@
 // how the batch was cut into blocks.  The per-batch gene sums (centres), the leftover rows' rotation and var.total read
 // the same companion.  A row index is compared with its bounds before it addresses anything; a failing entry is skipped.
 //
-// The iteration (start block, Cholesky QR 2, Rayleigh-Ritz, Chebyshev filter, residual) is Pca::fit's, restated here on
-// pca_kernels.hpp so that the dense handle keeps its code, launch order and bits.
+// The iteration (start block, Cholesky QR 2, Rayleigh-Ritz, Chebyshev filter, residual) is SubspaceIteration
+// (pca_iteration.hpp), the one the dense handle runs: this file brings the sparse operator and keeps the centre, the
+// rotation and the projections.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -35,7 +36,7 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
-#include "pca_kernels.hpp"
+#include "pca_iteration.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -419,14 +420,9 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
         fitted_ = false;
         if (batches_.empty()) throw Error(BMX_ERR_ARG, "at least one batch must be specified");
         if (!batches_.back()->complete()) throw Error(BMX_ERR_ARG, "the last batch has not received all its cells");
-        if (d < 1 || d > 2 * PL - 8) throw Error(BMX_ERR_ARG, "the device PCA takes 1 <= d <= 120");
-        if (d > Gp_) throw Error(BMX_ERR_ARG, "d exceeds the number of genes");
-        if (max_applies < 1) throw Error(BMX_ERR_ARG, "the PCA needs at least one iteration");
-        const int L = d <= PL - 8 ? PL : 2 * PL;
         int64_t ncells = 0;
         for (auto& bp : batches_) ncells += bp->n;
-        if (Gp_ < L || ncells <= L)
-            throw Error(BMX_ERR_ARG, "PCA: the data has rank below the subspace width (fewer genes or cells than the block)");
+        const int L = SubspaceIteration::width_for(d, Gp_, ncells, max_applies);
         {
             int32_t flags[F_WORDS] = {0, 0};
             BMX_HIP(hipMemcpyAsync(flags, flags_.p, sizeof(flags), hipMemcpyDeviceToHost, stream_));
@@ -435,8 +431,6 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
             if (flags[F_ORDER])
                 throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
         }
-        L_ = L;
-        d_ = d;
         const int G = Gp_;
         // ---- grand centre of ALL rows: weighted mean of the batch means (R/multiBatchPCA.R:268-281)
         double* mu = mu_.reserve((size_t)G_);
@@ -453,92 +447,13 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
                                b.weight / wsum, (int64_t)G_);
             BMX_LAUNCH_CHECK();
         }
-        // ---- starting block: Pca::fit's fixed pseudo-random G x L matrix, orthonormalised
-        const size_t GL = (size_t)G * L;
-        double* Q = q_.reserve(GL);
-        double* Y = y_.reserve(GL);
-        double* Xr = xr_.reserve(GL);  // Ritz vectors Q V
-        double* Yr = yr_.reserve(GL);  // their images Y V
-        double* W = w_.reserve(GL);    // filter scratch
-        small_.reserve((size_t)L * L * 3 + 4 * (size_t)L);
-        {
-            std::vector<double> h(GL);
-            unsigned long long st = 0x9E3779B97F4A7C15ull;
-            for (auto& v : h) {  // splitmix64 -> uniform in (-1, 1)
-                st += 0x9E3779B97F4A7C15ull;
-                unsigned long long z = st;
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                z ^= z >> 31;
-                v = (double)(z >> 11) * (1.0 / 4503599627370496.0) - 1.0;
-            }
-            BMX_HIP(hipMemcpyAsync(Y, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-            BMX_HIP(hipStreamSynchronize(stream_));
-        }
-        orthonormalise(Y, Q);
-        std::vector<double>& theta = theta_;
-        theta.assign(L, 0.0);
-        std::vector<double> V;
-        std::vector<int> order(L);
-        int applies = 0;
-        double resid = std::numeric_limits<double>::infinity();
-        const bool fixed = !(tol > 0.0);
-        for (;;) {
-            apply_operator(Q, Y);  // Y = M Q
-            ++applies;
-            const bool last_fixed = fixed && applies >= max_applies;
-            if (fixed && !last_fixed) {  // plain subspace iteration, no convergence test
-                orthonormalise(Y, Q);
-                continue;
-            }
-            // ---- Rayleigh-Ritz on (Q, Y = M Q): T = Q^T Y = V diag(theta) V^T; Ritz vectors Xr = Q V, images Yr = Y V
-            rayleigh_ritz(Q, Y, theta, V, order);
-            rotate(Q, V, order, Xr);
-            rotate(Y, V, order, Yr);
-            resid = residual(Yr, Xr, theta, d);
-            if (last_fixed || resid <= tol || applies >= max_applies) break;
-            // ---- next block: p(M) Xr, p the Chebyshev polynomial bounded on [0, theta_L], degree capped (Pca::fit)
-            const double lam = theta[0], cut = theta[L - 1];
-            int deg = 1;
-            if (cut > 0.0 && lam > cut * (1.0 + 1e-12)) {
-                const double x = 2.0 * lam / cut - 1.0;
-                deg = (int)std::floor(std::log(1e5) / std::acosh(x));
-                deg = std::max(1, std::min({deg, 12, max_applies - applies + 1}));
-            }
-            if (deg <= 1) {
-                orthonormalise(Yr, Q);
-                continue;
-            }
-            const double c = 0.5 * cut, e = 0.5 * cut;
-            const double sg1 = e / (lam - c);
-            double sg = sg1;
-            const int64_t nel = (int64_t)GL;
-            const unsigned nblk = (unsigned)cdiv(nel, 256);
-            double* X0 = Xr;
-            double* X1 = W;
-            hipLaunchKernelGGL(lincomb3, dim3(nblk), dim3(256), 0, stream_, X1, sg1 / e, (const double*)Yr, -c * sg1 / e,
-                               (const double*)Xr, 0.0, (const double*)nullptr, nel);
-            BMX_LAUNCH_CHECK();
-            double* spare = Yr;  // Yr is free once X1 exists
-            for (int i = 2; i <= deg; ++i) {
-                const double sg2 = 1.0 / (2.0 / sg1 - sg);
-                apply_operator(X1, Y);
-                ++applies;
-                hipLaunchKernelGGL(lincomb3, dim3(nblk), dim3(256), 0, stream_, spare, 2.0 * sg2 / e, (const double*)Y,
-                                   -2.0 * c * sg2 / e, (const double*)X1, -sg * sg2, (const double*)X0, nel);
-                BMX_LAUNCH_CHECK();
-                double* t = X0;
-                X0 = X1;
-                X1 = spare;
-                spare = t;
-                sg = sg2;
-            }
-            orthonormalise(X1, Q);
-        }
-        // ---- results: rotation = the first d Ritz vectors; xr_ keeps them row-major for the projections' gathers
-        const double* R = Xr;
-        double* Ut = ut_.reserve(GL);  // [L][G]: the rotation column-major
-        double* muU = small_.p + (size_t)3 * L * L;
+        off_.reserve(4 * (size_t)PL);
+        const SubspaceIteration::Outcome outcome =
+            it_.run(stream_, G, d, tol, max_applies, [&](const double* Q, double* Y) { apply_operator(Q, Y); });
+        // ---- results: rotation = the first d Ritz vectors; the iteration keeps them row-major for the projections' gathers
+        const double* R = it_.ritz_vectors();
+        double* Ut = ut_.reserve((size_t)G * L);  // [L][G]: the rotation column-major
+        double* muU = off_.p + 2 * PL;
         for (int h = 0; h < L / PL; ++h) {
             hipLaunchKernelGGL(transpose64, dim3((unsigned)cdiv(G, 64)), dim3(256), 0, stream_, (const double*)(R + h * PL),
                                (int64_t)L, (int64_t)G, Ut + (size_t)h * PL * G);
@@ -549,18 +464,8 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
         if (rotation)
             BMX_HIP(hipMemcpyAsync(rotation, Ut, (size_t)G * d * sizeof(double), hipMemcpyDeviceToHost, stream_));
         BMX_HIP(hipStreamSynchronize(stream_));
-        if (sdev)
-            for (int j = 0; j < d; ++j) sdev[j] = std::sqrt(std::max(0.0, theta[j]));
-        if (applies_used) *applies_used = applies;
-        if (resid_out) *resid_out = resid;
         fitted_ = true;
-        if (!fixed && !(resid <= tol)) {
-            char msg[256];
-            std::snprintf(msg, sizeof(msg),
-                          "PCA: the subspace iteration did not reach the tolerance within %d applications of the operator "
-                          "(relative residual %.3g, tolerance %.3g)", applies, resid, tol);
-            throw Error(BMX_ERR_ARG, msg);
-        }
+        it_.report(tol, outcome, sdev, applies_used, resid_out);
     }
 
     // crossprod(x_b - centers, rotation) over the PCA rows: [n_b x d] column-major
@@ -573,12 +478,13 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
         SparsePcaBatch& B = *batches_[(size_t)b];
         double* Z = z_.reserve((size_t)B.n * PL);
         double* Zt = zt_.reserve((size_t)B.n * PL);
-        for (int h = 0; h * PL < d_; ++h) {
-            by_cell(B, xr_.p + h * PL, small_.p + (size_t)3 * L_ * L_ + h * PL, Z);
+        const int d = it_.d();
+        for (int h = 0; h * PL < d; ++h) {
+            by_cell(B, it_.ritz_vectors() + h * PL, mu_dot_u() + h * PL, Z);
             hipLaunchKernelGGL(transpose64, dim3((unsigned)cdiv(B.n, 64)), dim3(256), 0, stream_, (const double*)Z, (int64_t)PL,
                                B.n, Zt);
             BMX_LAUNCH_CHECK();
-            const int cols = std::min(PL, d_ - h * PL);
+            const int cols = std::min(PL, d - h * PL);
             BMX_HIP(hipMemcpyAsync(out + (size_t)h * PL * B.n, Zt, (size_t)B.n * cols * sizeof(double), hipMemcpyDeviceToHost,
                                    stream_));
             BMX_HIP(hipStreamSynchronize(stream_));  // Z / Zt are reused by the next half
@@ -591,7 +497,7 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
         CacheScope scope(&cache_);
         BMX_HIP(hipSetDevice(device_));
         if (!fitted_) throw Error(BMX_ERR_ARG, "bmx_pca_sparse_fit has not been run");
-        const int GL = G_ - Gp_, d = d_, nh = cdiv(d_, PL);
+        const int GL = G_ - Gp_, d = it_.d(), nh = cdiv(d, PL);
         if (GL < 1) return;
         double* acc = acc_.reserve((size_t)nh * GL * PL);
         double* tsum = tsum_.reserve((size_t)nh * PL + 2 * (size_t)PL);
@@ -602,27 +508,14 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
             const double coef = B.weight / (double)B.n;
             double* Z = z_.reserve((size_t)B.n * PL);
             for (int h = 0; h < nh; ++h) {
-                by_cell(B, xr_.p + h * PL, small_.p + (size_t)3 * L_ * L_ + h * PL, Z);
+                by_cell(B, it_.ritz_vectors() + h * PL, mu_dot_u() + h * PL, Z);
                 column_sums(Z, B.n, coef, 1.0, tsum + h * PL);
                 by_gene(B, Gp_, G_, Z, coef, 1.0, nullptr, nullptr, acc + (size_t)h * GL * PL, PL);
             }
         }
-        std::vector<double> s2((size_t)d);
-        for (int j = 0; j < d; ++j) {
-            const double sd = std::sqrt(std::max(0.0, theta_[(size_t)j]));  // the sdev fit reports
-            s2[(size_t)j] = sd * sd;
-        }
-        double* ds2 = tsum + (size_t)nh * PL;
-        BMX_HIP(hipMemcpyAsync(ds2, s2.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, stream_));
         double* rot = part_.reserve((size_t)GL * d);
-        hipLaunchKernelGGL(genes_rotation, dim3((unsigned)cdiv((int64_t)GL * d, 256)), dim3(256), 0, stream_, (const double*)acc,
-                           (const double*)(mu_.p + Gp_), (const double*)tsum, (const double*)ds2, GL, d, rot);
-        BMX_LAUNCH_CHECK();
-        if (centers_left)
-            BMX_HIP(hipMemcpyAsync(centers_left, mu_.p + Gp_, (size_t)GL * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        if (rotation_left)
-            BMX_HIP(hipMemcpyAsync(rotation_left, rot, (size_t)GL * d * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        BMX_HIP(hipStreamSynchronize(stream_));
+        leftover_rotation(stream_, it_.theta(), d, acc, mu_.p + Gp_, tsum, tsum + (size_t)nh * PL, GL, rot, centers_left,
+                          rotation_left);
     }
 
     // sum_b coef_b |C_b|_F^2 over the PCA rows, per gene in the centred form; the caller divides by the batches
@@ -688,7 +581,7 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
     // Z [n][64] = diag(scale) x_S^T Q - 1 off^T for 64 columns of a row-major [n_rows_pca][L_] block at Q
     void by_cell(SparsePcaBatch& b, const double* Q, const double* off, double* Z) {
         hipLaunchKernelGGL(sp_by_cell_kernel, dim3((unsigned)cdiv(b.n, 4)), dim3(256), 0, stream_, (const int64_t*)b.indptr.p,
-                           (const int64_t*)b.cut.p, (const int32_t*)b.indices.p, (const double*)b.data.p, b.n, Q, (int64_t)L_,
+                           (const int64_t*)b.cut.p, (const int32_t*)b.indices.p, (const double*)b.data.p, b.n, Q, (int64_t)it_.L(),
                            Gp_, (const double*)(b.cos_norm ? b.inv.p : nullptr), off, Z);
         BMX_LAUNCH_CHECK();
     }
@@ -710,20 +603,14 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
     }
     // out[j] = beta out[j] + alpha * sum_c Z[c][j], two stages in a fixed order
     void column_sums(const double* Z, int64_t n, double alpha, double beta, double* out) {
-        const int nb = (int)std::min<int64_t>(4096, std::max<int64_t>(1, n / 256));
-        const int64_t rpb = (n + nb - 1) / nb;
-        double* zpart = zpart_.reserve((size_t)4096 * PL);
-        hipLaunchKernelGGL(colsum64_partial, dim3(nb), dim3(256), 0, stream_, Z, (const double*)nullptr, n, rpb, zpart);
-        hipLaunchKernelGGL(reduce_parts, dim3(1), dim3(64), 0, stream_, (const double*)zpart, nb, (int64_t)PL, alpha, beta, out,
-                           PL, (int64_t)PL);
-        BMX_LAUNCH_CHECK();
+        column_sums64(stream_, Z, n, zpart_.reserve((size_t)4096 * PL), alpha, beta, out);
     }
     // out[j] = mu . Q[:, j] for 64 columns of a row-major [n_rows_pca][L_] block at Q
     void mu_dot(const double* Q, double* out) {
         const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, Gp_ / 256));
         const int64_t rpb = ((int64_t)Gp_ + nb - 1) / nb;
         double* zpart = zpart_.reserve((size_t)4096 * PL);
-        hipLaunchKernelGGL(mu_dot_partial, dim3(nb), dim3(256), 0, stream_, Q, (int64_t)L_, (const double*)mu_.p, (int64_t)Gp_,
+        hipLaunchKernelGGL(mu_dot_partial, dim3(nb), dim3(256), 0, stream_, Q, (int64_t)it_.L(), (const double*)mu_.p, (int64_t)Gp_,
                            rpb, zpart);
         hipLaunchKernelGGL(reduce_parts, dim3(1), dim3(64), 0, stream_, (const double*)zpart, nb, (int64_t)PL, 1.0, 0.0, out, PL,
                            (int64_t)PL);
@@ -731,10 +618,10 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
     }
     // Y = M Q = sum_b (w_b / n_b) C_b C_b^T Q for a block of L vectors, 64 at a time
     void apply_operator(const double* Q, double* Y) {
-        const int G = Gp_, L = L_;
+        const int G = Gp_, L = it_.L();
         BMX_HIP(hipMemsetAsync(Y, 0, (size_t)G * L * sizeof(double), stream_));
-        double* muQ = small_.p + (size_t)2 * L * L;
-        double* zsum = muQ + PL;
+        double* muQ = off_.p;
+        double* zsum = off_.p + PL;
         for (int h = 0; h < L / PL; ++h) {
             mu_dot(Q + h * PL, muQ);
             for (auto& bp : batches_) {
@@ -746,106 +633,12 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
             }
         }
     }
-
-    // ---- Pca's dense pieces on [n_rows_pca][L] blocks, with its kernels and launch shapes
-    // out [L][L] row-major = A^T B for A, B [rows][L]
-    void product_tn(const double* A, const double* Bm, int64_t rows, double* out) {
-        const int L = L_;
-        const int nsplit = (int)std::min<int64_t>(256, std::max<int64_t>(1, rows / 512));
-        const int64_t per = round_up((rows + nsplit - 1) / nsplit, KC);
-        double* part = part_.reserve((size_t)nsplit * L * PL);
-        for (int h = 0; h < L / PL; ++h) {
-            hipLaunchKernelGGL(gemm_tn64, dim3(L / PL, nsplit), dim3(256), 0, stream_, A, rows, L, (int64_t)L, Bm + h * PL,
-                               (int64_t)L, (const double*)nullptr, per, part);
-            hipLaunchKernelGGL(reduce_parts, dim3((unsigned)cdiv(L * PL, 256)), dim3(256), 0, stream_, (const double*)part,
-                               nsplit, (int64_t)L * PL, 1.0, 0.0, out + h * PL, PL, (int64_t)L);
-            BMX_LAUNCH_CHECK();
-        }
-    }
-    // dst [G][L] = src [G][L] * Bt^T for a host matrix Bt [L][L] row-major
-    void times_small(const double* src, const std::vector<double>& Bt, double* dst) {
-        const int L = L_;
-        double* dB = small_.p + (size_t)L * L;
-        BMX_HIP(hipMemcpyAsync(dB, Bt.data(), Bt.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-        for (int h = 0; h < L / PL; ++h) {
-            hipLaunchKernelGGL(gemm_nt64, dim3((unsigned)cdiv(Gp_, 64)), dim3(256), 0, stream_, src, (int64_t)Gp_, L, (int64_t)L,
-                               (const double*)(dB + (size_t)h * PL * L), (int64_t)L, (const double*)nullptr,
-                               (const double*)nullptr, dst + h * PL, (int64_t)L);
-            BMX_LAUNCH_CHECK();
-        }
-        BMX_HIP(hipStreamSynchronize(stream_));  // Bt may go out of scope
-    }
-    // Q = Y R^-1 with R^T R = Y^T Y, twice (Cholesky QR 2).  Y is overwritten.
-    void orthonormalise(double* Y, double* Q) {
-        const int L = L_;
-        double* S = small_.p;
-        double* src = Y;
-        double* dst = Q;
-        for (int pass = 0; pass < 2; ++pass) {
-            product_tn(src, src, (int64_t)Gp_, S);
-            std::vector<double> h((size_t)L * L);
-            BMX_HIP(hipMemcpyAsync(h.data(), S, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            BMX_HIP(hipStreamSynchronize(stream_));
-            if (!cholesky_upper(h, L)) throw Error(BMX_ERR_ARG, "PCA: the data has rank below the subspace width");
-            invert_upper(h, L);
-            std::vector<double> bt((size_t)L * L);
-            for (int i = 0; i < L; ++i)
-                for (int j = 0; j < L; ++j) bt[(size_t)j * L + i] = h[(size_t)i * L + j];
-            times_small(src, bt, dst);
-            std::swap(src, dst);
-        }
-        BMX_HIP(hipMemcpyAsync(Q, Y, (size_t)Gp_ * L * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    }
-    void rayleigh_ritz(const double* Q, const double* Y, std::vector<double>& theta, std::vector<double>& V,
-                       std::vector<int>& order) {
-        const int L = L_;
-        double* T = small_.p;
-        product_tn(Q, Y, (int64_t)Gp_, T);
-        std::vector<double> hT((size_t)L * L);
-        BMX_HIP(hipMemcpyAsync(hT.data(), T, hT.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        BMX_HIP(hipStreamSynchronize(stream_));
-        for (int i = 0; i < L; ++i)
-            for (int j = i + 1; j < L; ++j) {
-                const double v = 0.5 * (hT[(size_t)i * L + j] + hT[(size_t)j * L + i]);
-                hT[(size_t)i * L + j] = hT[(size_t)j * L + i] = v;
-            }
-        jacobi_eigen(hT, V, L);
-        for (int i = 0; i < L; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return hT[(size_t)a * L + a] > hT[(size_t)b * L + b]; });
-        for (int j = 0; j < L; ++j) theta[j] = hT[(size_t)order[j] * L + order[j]];
-    }
-    // dst = src V with the columns of V taken in `order`
-    void rotate(const double* src, const std::vector<double>& V, const std::vector<int>& order, double* dst) {
-        const int L = L_;
-        std::vector<double> Bt((size_t)L * L);
-        for (int j = 0; j < L; ++j)
-            for (int i = 0; i < L; ++i) Bt[(size_t)j * L + i] = V[(size_t)i * L + order[j]];
-        times_small(src, Bt, dst);
-    }
-    // max_j<d |Yr_j - theta_j Xr_j| / theta_0
-    double residual(const double* Yr, const double* Xr, const std::vector<double>& theta, int d) {
-        const int L = L_;
-        double* dth = small_.p + (size_t)3 * L * L + L;
-        double* dres = dth + L;
-        BMX_HIP(hipMemcpyAsync(dth, theta.data(), (size_t)L * sizeof(double), hipMemcpyHostToDevice, stream_));
-        const int nb = cdiv(Gp_, 256);
-        double* part = part_.reserve((size_t)nb * L);
-        hipLaunchKernelGGL(resid_partial, dim3(nb), dim3(256), 0, stream_, Yr, Xr, (const double*)dth, (int64_t)Gp_, L, part);
-        hipLaunchKernelGGL(reduce_parts, dim3((unsigned)cdiv(L, 256)), dim3(256), 0, stream_, (const double*)part, nb, (int64_t)L,
-                           1.0, 0.0, dres, L, (int64_t)L);
-        BMX_LAUNCH_CHECK();
-        std::vector<double> h(L);
-        BMX_HIP(hipMemcpyAsync(h.data(), dres, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        BMX_HIP(hipStreamSynchronize(stream_));
-        double worst = 0.0;
-        for (int j = 0; j < d; ++j) worst = std::max(worst, std::sqrt(std::max(0.0, h[j])));
-        return theta[0] > 0.0 ? worst / theta[0] : 0.0;
-    }
+    const double* mu_dot_u() const { return off_.p + 2 * PL; }  // [L]: mu . u_j of the last fit
 
     int Gp_;  // the rows the PCA runs on: the first Gp_ of the G_ resident rows
-    int d_ = 0, L_ = PL;
-    std::vector<double> theta_;  // [L] Ritz values of the last fit, descending
-    DevBuf<double> mu_, mean_, q_, y_, xr_, yr_, w_, ut_, z_, zt_, part_, seg_part_, zpart_, small_, acc_, tsum_;
+    SubspaceIteration it_;
+    // off_: mu . Q of the block being applied [PL], the column sums of Z [PL], mu . u_j [2 PL]
+    DevBuf<double> mu_, mean_, ut_, z_, zt_, part_, seg_part_, zpart_, off_, acc_, tsum_;
     DevBuf<int32_t> cnt_, flags_;
     bool fitted_ = false;
 };
@@ -892,19 +685,7 @@ int32_t bmx_pca_sparse_fit(bmx_pca_sparse_t* h, int32_t d, int32_t iters, double
 int32_t bmx_pca_sparse_fit_tol(bmx_pca_sparse_t* h, int32_t d, double tol, int32_t max_iters, double* centers,
                                double* rotation, double* sdev, int32_t* iters_used, double* residual) {
     return bmx::guarded([&] {
-        bmx::PcaSparse& p = bmx::live(h);
-        if (!(tol > 0.0)) throw bmx::Error(BMX_ERR_ARG, "the PCA tolerance must be positive");
-        int used = 0;
-        double res = 0.0;
-        try {
-            p.fit(d, tol, max_iters, centers, rotation, sdev, &used, &res);
-        } catch (...) {
-            if (iters_used) *iters_used = used;
-            if (residual) *residual = res;
-            throw;
-        }
-        if (iters_used) *iters_used = used;
-        if (residual) *residual = res;
+        bmx::fit_to_tolerance(bmx::live(h), d, tol, max_iters, centers, rotation, sdev, iters_used, residual);
     });
 }
 

@@ -9,6 +9,7 @@ takes its top eigenvectors -- the same subspace and, up to sign, the same vector
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -91,18 +92,52 @@ def _weight_vector(ncells, weights):
     return w
 
 
-class DevicePCA(ResidentHandle):
+class _ResidentPCA(ResidentHandle):
+    """What DevicePCA and DeviceSparsePCA share: fit() and project() on a handle whose PCA runs on _fit_rows rows."""
+
+    def __init__(self, n_rows, device=0, *create_args):
+        _lib.require_gpu()
+        super().__init__(n_rows, device, *create_args)
+        self.d = 0
+        self.iters_used = 0
+        self.residual = float("nan")
+
+    @property
+    def _fit_rows(self):
+        return self.G
+
+    def fit(self, d=50, tol=1e-9, max_iters=500, iters=None):
+        """tol: relative Ritz residual at which the iteration stops (raises if max_iters applications of the operator do
+        not reach it; the handle is fitted all the same).  iters=N: the fixed-count form of round 2 (N plain subspace
+        iterations, no test).  A fit refused for another reason leaves the handle unfitted: project() raises."""
+        centers = np.zeros(self._fit_rows)
+        rotation = np.zeros((self._fit_rows, d), order="F")
+        sdev = np.zeros(d)
+        out = (_lib.f64p(centers), _lib.f64p(rotation), _lib.f64p(sdev))
+        if iters is not None:
+            rc = self._entry("fit")(self._h, int(d), int(iters), *out)
+            self.iters_used, self.residual = int(iters), float("nan")
+        else:
+            used, res = ctypes.c_int32(0), ctypes.c_double(0.0)
+            rc = self._entry("fit_tol")(self._h, int(d), ctypes.c_double(float(tol)), int(max_iters), *out,
+                                        ctypes.byref(used), ctypes.byref(res))
+            self.iters_used, self.residual = used.value, res.value
+        self.d = int(d)   # before the status is looked at: a run that missed its tolerance has fitted the handle with d
+        _lib.check(rc)
+        return {"rotation": np.ascontiguousarray(rotation), "centers": centers, "d": sdev,
+                "iters_used": self.iters_used, "residual": self.residual}
+
+    def project(self, b):
+        out = np.zeros((self.ncells[b], self.d), order="F")
+        self._call("project", int(b), _lib.f64p(out))
+        return np.ascontiguousarray(out)
+
+
+class DevicePCA(_ResidentPCA):
     """bmx_pca_t: the batches (genes x cells) stay in HBM; fit() = multiBatchPCA (R/multiBatchPCA.R:211-322) by
     Chebyshev-filtered subspace iteration on the FP64 matrix cores, run until the Ritz residual is below `tol`;
     project(b) = crossprod(cosineNorm(x_b) - centers, rotation)."""
     PREFIX = "bmx_pca"
-
-    def __init__(self, n_genes, device=0):
-        _lib.require_gpu()
-        super().__init__(n_genes, device)
-        self.d = 0
-        self.iters_used = 0
-        self.residual = float("nan")
 
     def _check_rows(self, x):
         if x.ndim != 2 or x.shape[0] != self.G:
@@ -123,32 +158,6 @@ class DevicePCA(ResidentHandle):
         x_block = _lib.as_f(x_block)
         self._check_rows(x_block)
         self._call("add_block", _lib.f64p(x_block), ctypes.c_int64(x_block.shape[1]))
-
-    def fit(self, d=50, tol=1e-9, max_iters=500, iters=None):
-        """tol: relative Ritz residual at which the iteration stops (raises if max_iters applications of the operator do
-        not reach it).  iters=N: the fixed-count form of round 2 (N plain subspace iterations, no test)."""
-        centers = np.zeros(self.G)
-        rotation = np.zeros((self.G, d), order="F")
-        sdev = np.zeros(d)
-        if iters is not None:
-            _lib.check(_lib.lib().bmx_pca_fit(self._h, int(d), int(iters), _lib.f64p(centers), _lib.f64p(rotation),
-                                              _lib.f64p(sdev)))
-            self.iters_used, self.residual = int(iters), float("nan")
-        else:
-            used, res = ctypes.c_int32(0), ctypes.c_double(0.0)
-            rc = _lib.lib().bmx_pca_fit_tol(self._h, int(d), ctypes.c_double(float(tol)), int(max_iters),
-                                            _lib.f64p(centers), _lib.f64p(rotation), _lib.f64p(sdev), ctypes.byref(used),
-                                            ctypes.byref(res))
-            self.iters_used, self.residual = used.value, res.value
-            _lib.check(rc)
-        self.d = int(d)
-        return {"rotation": np.ascontiguousarray(rotation), "centers": centers, "d": sdev,
-                "iters_used": self.iters_used, "residual": self.residual}
-
-    def project(self, b):
-        out = np.zeros((self.ncells[b], self.d), order="F")
-        _lib.check(_lib.lib().bmx_pca_project(self._h, int(b), _lib.f64p(out)))
-        return np.ascontiguousarray(out)
 
     def genes(self, n_left):
         """The streaming pass over the n_left genes outside subset.row, on this fitted PCA (DevicePCAGenes)."""
@@ -212,7 +221,7 @@ def sparse_row_segment():
     return _lib.dev_get("pca_sparse_row_segment")
 
 
-class DeviceSparsePCA(ResidentHandle):
+class DeviceSparsePCA(_ResidentPCA):
     """bmx_pca_sparse_t: DevicePCA for batches kept in HBM as CSC.  The handle holds n_rows rows of every batch, of which
     the first n_rows_pca are the rows the PCA runs on (the subset in the caller's order) and the others the genes outside
     the subset, ascending; they stay resident, so genes() needs no second pass over the host's data."""
@@ -220,12 +229,12 @@ class DeviceSparsePCA(ResidentHandle):
     BLOCK_BYTES = 1 << 28   # a batch goes to the device in column blocks of about this many bytes of stored entries
 
     def __init__(self, n_rows, n_rows_pca=None, device=0):
-        _lib.require_gpu()
         self.n_pca = int(n_rows if n_rows_pca is None else n_rows_pca)
         super().__init__(n_rows, device, ctypes.c_int32(self.n_pca))
-        self.d = 0
-        self.iters_used = 0
-        self.residual = float("nan")
+
+    @property
+    def _fit_rows(self):
+        return self.n_pca
 
     def add_batch(self, c, weight=1.0, cos_norm=False, block_cells=None):
         """c: canonical CSC (inputs.canonical_csc), n_rows x cells.  block_cells: cells per uploaded block (None: as many
@@ -244,29 +253,6 @@ class DeviceSparsePCA(ResidentHandle):
         """The next m cells of the batch begun last: indptr [m + 1] int64 relative to the block, int32 rows, float64."""
         self._call("add_block", ctypes.c_int64(int(m)), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
                    _lib.f64p(data), ctypes.c_int64(int(data.size)))
-
-    def fit(self, d=50, tol=1e-9, max_iters=500, iters=None):
-        """As DevicePCA.fit, over the first n_rows_pca rows."""
-        centers = np.zeros(self.n_pca)
-        rotation = np.zeros((self.n_pca, d), order="F")
-        sdev = np.zeros(d)
-        if iters is not None:
-            self._call("fit", int(d), int(iters), _lib.f64p(centers), _lib.f64p(rotation), _lib.f64p(sdev))
-            self.iters_used, self.residual = int(iters), float("nan")
-        else:
-            used, res = ctypes.c_int32(0), ctypes.c_double(0.0)
-            rc = self._entry("fit_tol")(self._h, int(d), ctypes.c_double(float(tol)), int(max_iters), _lib.f64p(centers),
-                                        _lib.f64p(rotation), _lib.f64p(sdev), ctypes.byref(used), ctypes.byref(res))
-            self.iters_used, self.residual = used.value, res.value
-            _lib.check(rc)
-        self.d = int(d)
-        return {"rotation": np.ascontiguousarray(rotation), "centers": centers, "d": sdev,
-                "iters_used": self.iters_used, "residual": self.residual}
-
-    def project(self, b):
-        out = np.zeros((self.ncells[b], self.d), order="F")
-        self._call("project", int(b), _lib.f64p(out))
-        return np.ascontiguousarray(out)
 
     def genes(self):
         """(centers [n_rows - n_rows_pca], rotation [n_rows - n_rows_pca x d]) of the rows outside the subset."""
@@ -338,41 +324,33 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
     batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least one batch must be specified")
-    if all_sparse(batches, "multiBatchPCA"):
-        return _multi_batch_pca_sparse(batches, d, weights, cos_norm, tol, max_iters, iters, device, return_pcs, l2, block,
-                                       subset_row, get_all_genes, get_variance)
-    G_all = check_same_dim(batches, byrow=False)
+    sparse = all_sparse(batches, "multiBatchPCA")
+    G_all = check_same_rows(batches) if sparse else check_same_dim(batches, byrow=False)
     sub, left = _split_rows(subset_row, G_all)
     G = G_all if sub is None else sub.size
     if not get_all_genes:
         left = left[:0]
-    ncells = [np.asarray(m).shape[1] for m in batches]
+    ncells = [(m if sparse else np.asarray(m)).shape[1] for m in batches]
     w = _weight_vector(ncells, weights)
     width = 64 if d <= 56 else 128
 
-    def rows(m, which, lo, hi):
-        """Columns [lo, hi) of the rows `which` (None: all) of a batch."""
-        blk = np.asarray(m)[:, lo:hi]
-        return blk if which is None else blk[which]
-
     def host(reason):
-        return _host_route(batches, reason, d, weights, cos_norm, l2, block, subset_row, sub, get_all_genes, get_variance,
-                           return_pcs)
+        return _host_route(densify(batches, "multiBatchPCA") if sparse else batches, reason, d, weights, cos_norm, l2,
+                           block, subset_row, sub, get_all_genes, get_variance, return_pcs)
 
     if l2 is not None:
         return host("per-cell norms given (round-1 signature)")
     if d > 120 or G < width or sum(ncells) <= width:
         return host("fewer genes / cells than the device block, or d > 120")
-    pca = DevicePCA(G, device)
+    # what differs between the two device routes: the handle and how it is filled, and where the leftover rows come from
+    if sparse:
+        fill, leftovers, path = _fill_sparse, _resident_leftovers, "device-sparse"
+        pca = DeviceSparsePCA(G + left.size, G, device)
+    else:
+        fill, leftovers, path = _fill_dense, _streamed_leftovers, "device"
+        pca = DevicePCA(G, device)
     try:
-        for m, wi, n in zip(batches, w, ncells):
-            if sub is None:
-                pca.add_batch(m, weight=wi, cos_norm=cos_norm)
-                continue
-            pca.begin_batch(n, weight=wi, cos_norm=cos_norm)
-            per = max(1, _UPLOAD_BYTES // (8 * G))
-            for lo in range(0, n, per):
-                pca.add_block(rows(m, sub, lo, lo + per))
+        fill(pca, batches, w, ncells, sub, left, cos_norm)
         try:
             out = pca.fit(d=d, tol=tol, max_iters=max_iters, iters=iters)
         except _lib.BatchelorMI355XError as exc:
@@ -381,27 +359,66 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
                 return host("data of rank below the device block")
             raise
         out["weights"] = w
-        out["path"] = "device"
+        out["path"] = path
         if return_pcs:
             out["pcs"] = [pca.project(b) for b in range(len(batches))]
         if left.size or get_variance:
-            genes = pca.genes(left.size)
-            try:
+            with leftovers(pca, batches, ncells, left) as (finish, total_variance):
                 if left.size:
-                    per = max(1, _UPLOAD_BYTES // (8 * left.size))
-                    for b, (m, n) in enumerate(zip(batches, ncells)):
-                        genes.begin_batch(b)
-                        for lo in range(0, n, per):
-                            genes.add_block(rows(m, left, lo, lo + per))
-                    _all_genes(out, G_all, sub, left, *genes.finish())
+                    _all_genes(out, G_all, sub, left, *finish())
                 if get_variance:
                     out["var_explained"] = out["d"] ** 2 / len(batches)
-                    out["var_total"] = genes.total_variance() / len(batches)
-            finally:
-                genes.close()
+                    out["var_total"] = total_variance() / len(batches)
     finally:
         pca.close()
     return out
+
+
+def _rows(m, which, lo, hi):
+    """Columns [lo, hi) of the rows `which` (None: all) of a dense batch."""
+    blk = np.asarray(m)[:, lo:hi]
+    return blk if which is None else blk[which]
+
+
+def _fill_dense(pca, batches, w, ncells, sub, left, cos_norm):
+    """The subset rows of every batch into a DevicePCA, gathered on the host block by block."""
+    for m, wi, n in zip(batches, w, ncells):
+        if sub is None:
+            pca.add_batch(m, weight=wi, cos_norm=cos_norm)
+            continue
+        pca.begin_batch(n, weight=wi, cos_norm=cos_norm)
+        per = max(1, _UPLOAD_BYTES // (8 * pca.G))
+        for lo in range(0, n, per):
+            pca.add_block(_rows(m, sub, lo, lo + per))
+
+
+def _fill_sparse(pca, batches, w, ncells, sub, left, cos_norm):
+    """Every batch as [x[subset_row]; the other rows, ascending] into a DeviceSparsePCA."""
+    order = None if sub is None else np.concatenate([sub, left])
+    for m, wi in zip(batches, w):
+        pca.add_batch(_csc_rows(m, order), weight=wi, cos_norm=cos_norm)
+
+
+@contextlib.contextmanager
+def _streamed_leftovers(pca, batches, ncells, left):
+    """(finish, total_variance) of a DevicePCAGenes that the rows `left` of the dense batches have streamed through."""
+    genes = pca.genes(left.size)
+    try:
+        if left.size:
+            per = max(1, _UPLOAD_BYTES // (8 * left.size))
+            for b, (m, n) in enumerate(zip(batches, ncells)):
+                genes.begin_batch(b)
+                for lo in range(0, n, per):
+                    genes.add_block(_rows(m, left, lo, lo + per))
+        yield genes.finish, genes.total_variance
+    finally:
+        genes.close()
+
+
+@contextlib.contextmanager
+def _resident_leftovers(pca, batches, ncells, left):
+    """(finish, total_variance) of a DeviceSparsePCA: the leftover rows are resident."""
+    yield pca.genes, pca.total_variance
 
 
 def _host_route(batches, reason, d, weights, cos_norm, l2, block, subset_row, sub, get_all_genes, get_variance, return_pcs):
@@ -431,53 +448,6 @@ def _csc_rows(m, rows):
     """Batch m as canonical CSC with the rows `rows` (0-based, in that order, repeats allowed; None: all)."""
     c = canonical_csc(m)[0]
     return c if rows is None else canonical_csc(c[rows])[0]
-
-
-def _multi_batch_pca_sparse(batches, d, weights, cos_norm, tol, max_iters, iters, device, return_pcs, l2, block,
-                            subset_row, get_all_genes, get_variance):
-    """multiBatchPCA for scipy.sparse batches: [subset rows; leftover rows] of every batch resident as CSC
-    (DeviceSparsePCA), or -- under the dense path's fallback conditions -- the host path on the densified batches."""
-    G_all = check_same_rows(batches)
-    sub, left = _split_rows(subset_row, G_all)
-    G = G_all if sub is None else sub.size
-    if not get_all_genes:
-        left = left[:0]
-    ncells = [m.shape[1] for m in batches]
-    w = _weight_vector(ncells, weights)
-    width = 64 if d <= 56 else 128
-
-    def host(reason):
-        return _host_route(densify(batches, "multiBatchPCA"), reason, d, weights, cos_norm, l2, block, subset_row, sub,
-                           get_all_genes, get_variance, return_pcs)
-
-    if l2 is not None:
-        return host("per-cell norms given (round-1 signature)")
-    if d > 120 or G < width or sum(ncells) <= width:
-        return host("fewer genes / cells than the device block, or d > 120")
-    order = None if sub is None else np.concatenate([sub, left])
-    pca = DeviceSparsePCA(G + left.size, G, device)
-    try:
-        for m, wi in zip(batches, w):
-            pca.add_batch(_csc_rows(m, order), weight=wi, cos_norm=cos_norm)
-        try:
-            out = pca.fit(d=d, tol=tol, max_iters=max_iters, iters=iters)
-        except _lib.BatchelorMI355XError as exc:
-            if "rank below the subspace width" in str(exc):
-                pca.close()
-                return host("data of rank below the device block")
-            raise
-        out["weights"] = w
-        out["path"] = "device-sparse"
-        if return_pcs:
-            out["pcs"] = [pca.project(b) for b in range(len(batches))]
-        if left.size:
-            _all_genes(out, G_all, sub, left, *pca.genes())
-        if get_variance:
-            out["var_explained"] = out["d"] ** 2 / len(batches)
-            out["var_total"] = pca.total_variance() / len(batches)
-    finally:
-        pca.close()
-    return out
 
 
 def multiBatchPCA_host(*batches, d=50, weights=None, l2=None, block=65536, subset_row=None, get_all_genes=False,

@@ -372,7 +372,9 @@ int32_t bmx_pca_add_block(bmx_pca_t* p, const double* x_block, int64_t n_block);
  * (one pass over every batch each), then BMX_ERR_ARG with the residual reached in the message.  iters_used / residual
  * (nullable) are written in both cases.  centers [n_genes], rotation [n_genes x d] column-major (columns defined up to
  * sign, as any SVD's), sdev [d] singular values of the scaled matrix; any may be NULL.  Needs n_genes and the total
- * number of cells above the block width. */
+ * number of cells above the block width.  A run that ends without reaching tol has written its results and leaves the
+ * handle fitted; a fit that fails for any other reason leaves it unfitted (bmx_pca_project then refuses), whatever an
+ * earlier fit had left. */
 int32_t bmx_pca_fit_tol(bmx_pca_t* p, int32_t d, double tol, int32_t max_iters, double* centers, double* rotation,
                         double* sdev, int32_t* iters_used, double* residual);
 /* Fixed-count form: exactly `iters` plain subspace iterations, no convergence test (kept for callers of round 2). */
@@ -417,7 +419,7 @@ int32_t bmx_pca_genes_total_variance(bmx_pca_genes_t* h, double* var_total);
  * FP64 vector ALUs, 64 subspace columns at a time with a lane per column: by cell from the CSC (Z = C_b^T Q) and by gene
  * from the companion (rows cut into segments of bmx_dev_get "pca_sparse_row_segment" entries, a row's segments added in
  * ascending order by a second kernel).  The iteration around it -- Chebyshev filter, Cholesky QR 2, Rayleigh-Ritz,
- * residual, starting block -- is bmx_pca_t's, with its kernels for the dense n_rows_pca x 64 blocks.  No floating-point
+ * residual, starting block -- is the one bmx_pca_t runs, on the dense n_rows_pca x 64 blocks.  No floating-point
  * atomics: the same calls give the same bits, however the batches were cut into blocks.
  * What only the device sees of the pattern is flagged at upload and reported by the fit: "a row index is outside [0,
  * number of genes)", "the row indices of a column should be strictly ascending".  Such entries are skipped by every
@@ -436,8 +438,8 @@ int32_t bmx_pca_sparse_begin_batch(bmx_pca_sparse_t* h, int64_t n, double weight
 int32_t bmx_pca_sparse_add_block(bmx_pca_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
                                  const double* data, int64_t nnz);
 /* As bmx_pca_fit_tol / bmx_pca_fit over the first n_rows_pca rows: the same meaning, limits (d <= 120, a block of 64 or
- * 128 vectors, "rank below the subspace width") and messages; centers [n_rows_pca], rotation [n_rows_pca x d]
- * column-major, sdev [d]. */
+ * 128 vectors, "rank below the subspace width"), messages and fitted state after a failure; centers [n_rows_pca],
+ * rotation [n_rows_pca x d] column-major, sdev [d]. */
 int32_t bmx_pca_sparse_fit_tol(bmx_pca_sparse_t* h, int32_t d, double tol, int32_t max_iters, double* centers,
                                double* rotation, double* sdev, int32_t* iters_used, double* residual);
 int32_t bmx_pca_sparse_fit(bmx_pca_sparse_t* h, int32_t d, int32_t iters, double* centers, double* rotation,

@@ -373,6 +373,17 @@ def reference(name):
     return ex, allowances(ex)
 
 
+@functools.lru_cache(maxsize=None)
+def contract_case():
+    """The input of test_gpu_pca.py::test_fit_contract_of_both_handles: 130 genes, batches of 257 and 300 cells of seeded
+    normal noise -- a flat spectrum, so that one application of the operator is nowhere near TOL."""
+    rng = np.random.default_rng(20260)
+    out = [rng.standard_normal((130, n)) for n in (257, 300)]
+    for m in out:
+        m.setflags(write=False)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- stand-alone projection
 PROJECT_SHAPES = [   # (G, n, d, cos_norm): bx.project stages 64 genes x d and 16 cells a workgroup; d <= 256
     (1, 1, 1, False), (63, 15, 15, True), (64, 16, 16, False), (65, 17, 17, True), (200, 500, 120, True),

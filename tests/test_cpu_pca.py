@@ -139,3 +139,17 @@ def test_case_table_covers_what_it_claims():
         if c.zero is not None:
             assert 0 < c.zero[1] < c.sizes[c.zero[0]] - 1
     assert 20 <= len(cases) <= 30
+
+
+def test_contract_case_needs_more_than_one_step():
+    """The input of test_gpu_pca.py::test_fit_contract_of_both_handles cannot be fitted to TOL by one application of the
+    operator: the host PCA shows a flat spectrum (no gap for a single step to exploit), and one power step of the float64
+    restatement leaves a residual many orders above TOL from any of several start blocks."""
+    from batchelor_amd import multiBatchPCA_host
+    B = ref.contract_case()
+    s = multiBatchPCA_host(*B, d=64)["d"]
+    resid = [ref.fixed_count_f64(B, None, False, 5, 1, seed=seed)["residual"] for seed in range(4)]
+    print(f"contract case: (s_6 / s_1)^2 = {(s[5] / s[0]) ** 2:.3g}, (s_64 / s_1)^2 = {(s[63] / s[0]) ** 2:.3g}; residual "
+          f"after one application from 4 start blocks: {min(resid):.3g} .. {max(resid):.3g}")
+    assert (s[63] / s[0]) ** 2 > 0.05
+    assert min(resid) > 1e6 * ref.TOL

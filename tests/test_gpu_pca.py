@@ -12,9 +12,11 @@ import functools
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 import batchelor_amd as bx
 from batchelor_amd import _lib
+from batchelor_amd.inputs import canonical_csc
 from tests import pca_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -132,5 +134,55 @@ def test_error_paths_that_need_the_device():
         pca.add_block(B[1][:, 100:])
         out = pca.fit(d=10, iters=1)           # and the handle is still good once the batch is complete
         assert out["rotation"].shape == (130, 10) and pca.project(1).shape == (513, 10)
+    finally:
+        pca.close()
+
+
+def _contract_handle(kind):
+    """ref.contract_case() resident in a DevicePCA, or as CSC of the same matrices in a DeviceSparsePCA."""
+    B = ref.contract_case()
+    pca = bx.DevicePCA(B[0].shape[0]) if kind == "dense" else bx.DeviceSparsePCA(B[0].shape[0])
+    for m in B:
+        pca.add_batch(m if kind == "dense" else canonical_csc(sp.csc_matrix(m))[0])
+    return pca
+
+
+@pytest.mark.parametrize("kind", ["dense", "sparse"])
+def test_fit_contract_of_both_handles(kind):
+    """What DevicePCA and DeviceSparsePCA share since they run one iteration: the refusals and their messages; a
+    refused fit leaves the handle unfitted whatever an earlier fit had left, and a repeat of the earlier fit gives its
+    bits again; a fit that misses its tolerance has written its results, the wrapper knows its d, and project() works."""
+    B = ref.contract_case()
+    pca = _contract_handle(kind)
+    try:
+        for kwargs, text in (({"d": 0}, "the device PCA takes 1 <= d <= 120"),
+                             ({"d": 121}, "the device PCA takes 1 <= d <= 120"),
+                             ({"d": 131}, "the device PCA takes 1 <= d <= 120"),   # (checked before d > 130 genes,
+                             # which test_error_paths_that_need_the_device reaches at 64 genes)
+                             ({"d": 5, "max_iters": 0}, "the PCA needs at least one iteration"),
+                             ({"d": 5, "tol": 0.0}, "the PCA tolerance must be positive")):
+            with pytest.raises(_lib.BatchelorMI355XError) as info:
+                pca.fit(**kwargs)
+            print(f"{kind}: fit({kwargs}) refused with: {info.value}")
+            assert text in str(info.value), (kwargs, str(info.value))
+        first = pca.fit(d=5, iters=2)
+        first["pcs"] = [pca.project(b) for b in range(len(B))]
+        with pytest.raises(_lib.BatchelorMI355XError, match="the device PCA takes 1 <= d <= 120"):
+            pca.fit(d=121, iters=2)
+        with pytest.raises(_lib.BatchelorMI355XError, match="has not been run"):
+            pca.project(0)
+        again = pca.fit(d=5, iters=2)
+        again["pcs"] = [pca.project(b) for b in range(len(B))]
+        same = {k: bool(np.array_equal(first[k], again[k])) for k in ("centers", "rotation", "d")}
+        same["pcs"] = all(np.array_equal(p, q) for p, q in zip(first["pcs"], again["pcs"]))
+        print(f"{kind}: the good fit repeated after a refused one, bitwise equal to the first: {same}")
+        assert all(same.values()), same
+        # one application cannot reach 1e-9 on this input (tests/test_cpu_pca.py::test_contract_case_needs_more_than_one_step)
+        with pytest.raises(_lib.BatchelorMI355XError, match="did not reach the tolerance"):
+            pca.fit(d=5, tol=ref.TOL, max_iters=1)
+        print(f"{kind}: after max_iters=1: iters_used {pca.iters_used}, residual {pca.residual:.3g}, wrapper d {pca.d}")
+        assert pca.iters_used == 1 and np.isfinite(pca.residual) and pca.residual > ref.TOL and pca.d == 5
+        pcs = pca.project(0)
+        assert pcs.shape == (257, 5) and np.all(np.isfinite(pcs))
     finally:
         pca.close()
