@@ -11,6 +11,7 @@ from .multi_batch_pca import (DevicePCA, DevicePCAGenes, DeviceSparsePCA, cosine
                               multiBatchPCA_host, project, sparse_row_segment)
 from .fast_mnn import fastMNN  # noqa: F401
 from .mnn_correct import mnnCorrect  # noqa: F401
+from .kmeans import KmeansParam, KmeansResult, kmeans  # noqa: F401
 from .cluster_mnn import ClusterMnnResult, clusterMNN  # noqa: F401
 from .linear_correct import LinearCorrectResult, regressBatches, rescaleBatches  # noqa: F401
 from .delta_variance import MnnDeltaVarianceResult, mnnDeltaVariance  # noqa: F401

@@ -6,12 +6,18 @@ the centroids' correction vectors, all on the device behind the bmx_cluster_* en
 batches are uploaded once and stay in HBM between the two passes.  The full-rank PCA of the centroids (`.full_rank_pca`,
 :171-181) runs on the host: its input is genes x (number of clusters).
 
-Out of scope (a clear error): clustering itself (BlusterParam, cluster.d), more than 257 clusters in total (the merge
-engine takes at most 256 columns), SingleCellExperiment inputs.
+With `clusters=KmeansParam(...)` every batch is clustered here first (.format_clusters, :199-221): the `subset_row` rows
+of the raw batch, its own PCA to `cluster_d` components (the single-batch DevicePCA, or a host SVD where the blocked
+iteration cannot take the shape), then kmeans() on the device (csrc/kmeans.hip).  The labels then go the way labels
+given by the caller go.  A batch is uploaded once for that PCA and once more for bmx_cluster_*.
+
+Out of scope (a clear error): bluster methods other than k-means (NNGraphParam and the rest), more than 257 clusters in
+total (the merge engine takes at most 256 columns), SingleCellExperiment inputs.
 """
 from __future__ import annotations
 
 import ctypes
+import warnings
 from dataclasses import dataclass
 from typing import Any, List, Optional
 
@@ -20,6 +26,8 @@ import numpy as np
 from . import _lib
 from ._handle import ResidentHandle
 from .inputs import check_restrict_length, check_same_dim, divide_into_batches, restrict_list, subset_index, unpack_batches
+from .kmeans import MAX_CENTERS, KmeansParam, kmeans
+from .multi_batch_pca import DevicePCA, device_pca_takes
 from .reduced_mnn import reducedMNN
 
 MAX_DIMS = 256          # columns the merge engine takes (csrc/engine.hip)
@@ -37,7 +45,9 @@ class ClusterMnnResult:
     merge_info: Any            # of the centroid-level reducedMNN; pairs index the rows of cluster_info
     sigma: np.ndarray          # per batch: the bandwidth of the smoothing
     cluster_info: dict         # columns "cluster", "batch", "meta", one row per centroid
-    stats: Optional[dict] = None   # "stage_ms": upload, centroids, projection, nearest_median, smoothing; "merge": per merge sizes
+    # "stage_ms": upload, centroids, projection, nearest_median, smoothing; "merge": per merge sizes; "clustering": None for
+    # labels given by the caller, else per batch what clustered it (path of the PCA, d, K, iter, converged, stage_ms)
+    stats: Optional[dict] = None
 
 
 def _format_clusters(ncells, clusters):
@@ -53,6 +63,64 @@ def _format_clusters(ncells, clusters):
             raise ValueError("corresponding entries of '...' and 'clusters' should have the same number of cells")
         out.append(c)
     return out
+
+
+def _check_clustering(param, ncells, cluster_d):
+    """The argument errors of clusters=KmeansParam that need no device; returns every batch's number of centres."""
+    if cluster_d is not None and (isinstance(cluster_d, (bool, np.bool_)) or not isinstance(cluster_d, (int, np.integer))
+                                  or cluster_d < 1):
+        raise ValueError("'cluster_d' must be a positive integer or None")
+    for name in ("iter_max", "nstart"):
+        v = getattr(param, name)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"'{name}' of a KmeansParam must be a positive integer")
+    ks = []
+    for b, n in enumerate(ncells):
+        k = param.n_centers(n)
+        if k < 1 or k > min(n, MAX_CENTERS):
+            raise ValueError(f"batch {b + 1} of {n} cells cannot be split into {k} clusters: kmeans takes 1 <= centers <= "
+                             f"min(cells, {MAX_CENTERS})")
+        ks.append(k)
+    return ks
+
+
+def _batch_pcs(m, d, device):
+    """runPCA(t(m), rank=d) of one batch (genes x cells), centred and not scaled: cells x d and the path taken."""
+    if device_pca_takes(m.shape[0], m.shape[1], d):
+        pca = DevicePCA(m.shape[0], device)
+        try:
+            pca.add_batch(m, weight=1.0, cos_norm=False)
+            pca.fit(d=d)
+            return pca.project(0), "device-pca"
+        finally:
+            pca.close()
+    centred = m.T - m.mean(axis=1)
+    u, s, _ = np.linalg.svd(centred, full_matrices=False)
+    return u[:, :d] * s[:d], "host-svd"
+
+
+def _cluster_batches(mats, sub, param, ks, cluster_d, device):
+    """.format_clusters, the BlusterParam branch (R/clusterMNN.R:204-220): every batch's labels from kmeans() on its own
+    PCs (or on its rows with cluster_d=None), the restriction ignored as in the reference."""
+    labels, info = [], []
+    for m, k in zip(mats, ks):
+        cur = np.asarray(m, dtype=np.float64)
+        if sub is not None:
+            cur = cur[sub - 1]
+        d, path = cluster_d, "none"
+        if d is not None:
+            if d > min(cur.shape):
+                warnings.warn(f"'cluster_d' = {d} exceeds min(genes, cells) = {min(cur.shape)} of a batch: clamped",
+                              stacklevel=4)
+                d = int(min(cur.shape))
+            obs, path = _batch_pcs(cur, int(d), device)
+        else:
+            obs = np.ascontiguousarray(cur.T)
+        res = kmeans(obs, k, iter_max=param.iter_max, nstart=param.nstart, seed=param.seed, device=device)
+        labels.append(res.cluster)
+        info.append({"pca": path, "d": d, "centers": k, "iter": res.iter, "converged": res.converged,
+                     "tot_withinss": res.tot_withinss, "start": res.stats["start"], "stage_ms": res.stats["stage_ms"]})
+    return labels, info
 
 
 def _levels(labels, restrict, which):
@@ -172,18 +240,29 @@ class _ClusterHandle(ResidentHandle):
 
 
 def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
-                 names, device):
+                 names, device, cluster_d=50):
     """The body of clusterMNN() from .format_clusters on (R/clusterMNN.R:134-164), for a list of batches."""
     if len(mats) < 2:
         raise ValueError("at least two batches must be specified")
     G = check_same_dim(mats, byrow=False)
     ncells = [m.shape[1] for m in mats]
     check_restrict_length(restrict, len(mats))
-    clusters = _format_clusters(ncells, clusters)
+    ks = None
+    if isinstance(clusters, KmeansParam):
+        ks = _check_clustering(clusters, ncells, cluster_d)
+        if sum(ks) - 1 > MAX_DIMS:   # (refused below for any labels: here before a batch is clustered)
+            raise ValueError(f"clusterMNN works in sum(number of clusters) - 1 = {sum(ks) - 1} dimensions; the merge engine "
+                             f"takes at most {MAX_DIMS}")
+    else:
+        clusters = _format_clusters(ncells, clusters)
     restrict = restrict_list(restrict, ncells) or [None] * len(mats)
     sub = subset_index(subset_row, G)
     if sub is not None and sub.size == 0:
         raise ValueError("'subset_row' selects no genes")
+    clustering = None
+    if ks is not None:
+        _lib.require_gpu()
+        clusters, clustering = _cluster_batches(mats, sub, clusters, ks, cluster_d, device)
     lev = [_levels(c, r, b + 1) for b, (c, r) in enumerate(zip(clusters, restrict))]
     total = sum(lv.size for lv, _ in lev)
     if total - 1 > MAX_DIMS:
@@ -215,21 +294,25 @@ def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, mi
     batch = np.concatenate([np.repeat(cbatch[e - 1:e], m.shape[1]) for e, m in zip(ends, mats)])
     return ClusterMnnResult(corrected=np.concatenate(parts, axis=0), batch=batch, cluster=_concat_labels(clusters),
                             rotation=pca["rotation"], centers=pca["centers"], merge_info=merged.merge_info,
-                            sigma=np.asarray(sigma), cluster_info=info, stats={"stage_ms": stage_ms, "merge": merged.stats})
+                            sigma=np.asarray(sigma), cluster_info=info,
+                            stats={"stage_ms": stage_ms, "merge": merged.stats, "clustering": clustering})
 
 
-def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, merge_order=None, auto_merge=False,
-               min_batch_skip=0.0, subset_row=None, correct_all=False, device=0) -> ClusterMnnResult:
-    """clusterMNN(..., batch=, restrict=, clusters=, cos.norm=, merge.order=, auto.merge=, min.batch.skip=, subset.row=,
-    correct.all=) (R/clusterMNN.R:101-169).  Each batch is genes x cells; `clusters` is a list with one vector of labels
-    (integers or strings) per batch, or of length 1 for a single object that `batch=` splits."""
+def clusterMNN(*batches, batch=None, restrict=None, clusters, cluster_d=50, cos_norm=True, merge_order=None,
+               auto_merge=False, min_batch_skip=0.0, subset_row=None, correct_all=False, device=0) -> ClusterMnnResult:
+    """clusterMNN(..., batch=, restrict=, clusters=, cluster.d=, cos.norm=, merge.order=, auto.merge=, min.batch.skip=,
+    subset.row=, correct.all=) (R/clusterMNN.R:101-169).  Each batch is genes x cells; `clusters` is a list with one vector
+    of labels (integers or strings) per batch, or of length 1 for a single object that `batch=` splits -- or a KmeansParam:
+    every batch (of a single object: every piece `batch=` splits off) is then clustered by kmeans() on the first
+    `cluster_d` PCs of its `subset_row` rows (cluster_d=None: on those rows themselves), every batch from the param's
+    seed; `restrict` plays no part in that, as in the reference."""
     batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least two batches must be specified")
     mats: List[np.ndarray] = [np.asarray(b) for b in batches]
     if len(mats) > 1:
         return _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row,
-                            correct_all, None, device)
+                            correct_all, None, device, cluster_d)
     # one object: divideIntoBatches(byrow=FALSE) and split(clusters[[1]], batch) (:121-132)
     x = mats[0]
     if batch is None:
@@ -238,17 +321,19 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cos_norm=True, mer
         raise ValueError("'length(batch)' and 'ncol(x)' are not the same")
     if restrict is not None and len(restrict) != 1:
         raise ValueError("'restrictions' must of length equal to the number of batches")
+    also = ()
     if isinstance(clusters, (list, tuple)):
         if len(clusters) != 1:
             raise ValueError("'clusters' must be a list of length 1 when '...' contains one element")
         call = np.asarray(clusters[0])
         if call.ndim != 1 or call.shape[0] != x.shape[1]:
             raise ValueError("corresponding entries of '...' and 'clusters' should have the same number of cells")
-    else:
+        also = (call,)
+    elif not isinstance(clusters, KmeansParam):
         raise ValueError("'clusters' must be either a list or a BlusterParam object")
-    div = divide_into_batches(x, batch, None if restrict is None else restrict[0], also=(call,))
-    out = _cluster_mnn(div.parts, div.restricted, div.also[0], cos_norm, merge_order, auto_merge, min_batch_skip, subset_row,
-                       correct_all, [str(lv) for lv in div.levels], device)
+    div = divide_into_batches(x, batch, None if restrict is None else restrict[0], also=also)
+    out = _cluster_mnn(div.parts, div.restricted, div.also[0] if also else clusters, cos_norm, merge_order, auto_merge,
+                       min_batch_skip, subset_row, correct_all, [str(lv) for lv in div.levels], device, cluster_d)
     reorder = div.reorder
     out.corrected = out.corrected[reorder - 1]  # output[, divided$reorder] (:166-168)
     out.batch = out.batch[reorder - 1]

@@ -269,6 +269,13 @@ class DeviceSparsePCA(_ResidentPCA):
         return out.value
 
 
+def device_pca_takes(n_rows, n_cells, d):
+    """Whether the blocked subspace iteration takes a PCA of this shape: at least as many rows as its block of 64 / 128
+    vectors, more cells than that (over all batches), d <= 120."""
+    width = 64 if d <= 56 else 128
+    return d <= 120 and n_rows >= width and n_cells > width
+
+
 def _split_rows(subset_row, G):
     """(0-based subset rows in the caller's order, 0-based rows outside it ascending); (None, empty) without a subset."""
     idx = subset_index(subset_row, G)
@@ -332,7 +339,6 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
         left = left[:0]
     ncells = [(m if sparse else np.asarray(m)).shape[1] for m in batches]
     w = _weight_vector(ncells, weights)
-    width = 64 if d <= 56 else 128
 
     def host(reason):
         return _host_route(densify(batches, "multiBatchPCA") if sparse else batches, reason, d, weights, cos_norm, l2,
@@ -340,7 +346,7 @@ def multiBatchPCA(*batches, d=50, weights=None, cos_norm=False, tol=1e-9, max_it
 
     if l2 is not None:
         return host("per-cell norms given (round-1 signature)")
-    if d > 120 or G < width or sum(ncells) <= width:
+    if not device_pca_takes(G, sum(ncells), d):
         return host("fewer genes / cells than the device block, or d > 120")
     # what differs between the two device routes: the handle and how it is filled, and where the leftover rows come from
     if sparse:

@@ -491,6 +491,36 @@ int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rot
 int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * kmeans(): R's kmeans(x, centers = <matrix>, algorithm = "Lloyd") (what bluster::KmeansParam stands for in
+ * clusterMNN(clusters = <BlusterParam>), R/clusterMNN.R:199-221).  The observations (n x d, the d values of an observation
+ * contiguous: d x n column-major) are uploaded once, whole or in blocks of observations through the pinned staging ring,
+ * and stay in HBM for every run (start) and every iteration.  The assignment takes the products x . c on the FP64 matrix
+ * cores and compares |c|^2 - 2 x.c, the lowest index winning on equal values; the centre update adds every cluster's
+ * members in ascending order without floating-point atomics: the same calls give the same bits.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_kmeans bmx_kmeans_t;
+#define BMX_KMEANS_MAX_CENTERS 1024
+int32_t bmx_kmeans_create(int32_t device, int32_t n_dims, bmx_kmeans_t** out);
+void bmx_kmeans_destroy(bmx_kmeans_t* h);
+/* Announce the n >= 1 observations (once per handle), then hand them over in order: x_block [n_block][n_dims]. */
+int32_t bmx_kmeans_begin(bmx_kmeans_t* h, int64_t n);
+int32_t bmx_kmeans_add_block(bmx_kmeans_t* h, const double* x_block, int64_t n_block);
+/* Lloyd from centers [n_centers][n_dims] (every centre contiguous), 1 <= n_centers <= min(n, 1024), iter_max >= 1.  Labels
+ * start as "none"; every iteration assigns each observation to its nearest centre; no label changed: the run ends with
+ * *converged_out = 1; otherwise every centre becomes the mean of its members, *iter_out counts the assignments, and after
+ * iter_max of them the run ends behind the update with *converged_out = 0.  cluster_out [n]: 1-based labels; centers_out
+ * [n_centers][n_dims]: the means of those labels; size_out [n_centers]; withinss_out [n_centers] = sum (x - c)^2 taken
+ * directly; *tot_withinss_out their sum in ascending order.  BMX_ERR_ARG: "initial centers are not distinct" (two equal
+ * rows of `centers`), "empty cluster: try a better set of initial centers" (an update met a cluster without members; the
+ * outputs are then undefined).  The handle stays usable after either. */
+int32_t bmx_kmeans_run(bmx_kmeans_t* h, const double* centers, int32_t n_centers, int32_t iter_max, int32_t* cluster_out,
+                       double* centers_out, int32_t* size_out, double* withinss_out, double* tot_withinss_out,
+                       int32_t* iter_out, int32_t* converged_out);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), then HIP-event
+ * time of the assignments, the centre updates and withinss, out[4] = host wall time of the downloads. */
+int32_t bmx_kmeans_stage_ms(const bmx_kmeans_t* h, double* out5);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * rescaleBatches() (R/rescaleBatches.R:103-150) and regressBatches() (R/regressBatches.R:93-158): the linear
  * corrections.  The batches (genes x cells, column-major) are uploaded once, whole or in column blocks through the
  * pinned staging ring, and stay in HBM between the per-gene statistics and the pass that writes the result; results
