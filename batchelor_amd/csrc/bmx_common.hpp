@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/batchelor_mi355x.h"
+#include "host_basics.hpp"
 
 namespace bmx {
 
@@ -45,33 +46,9 @@ void guarded_stream_sync(hipStream_t stream, double budget_s);
 #define BMX_KS1 32
 #endif
 
-// Testing hooks (bmx_dev_set in the C ABI): process-wide knobs that tests and developer scripts set by an explicit call.
-// Nothing in the ENVIRONMENT of the host process changes what the library computes or which tier / form runs
-// (BMX_DEBUG=1 only prints, BMX_HOST_THREADS only sizes the staging thread pool).
-struct DevKnobs {
-    int knn_tier = 0;         // 1 / 2: that candidate tier only, 3: exact FP64 scan only
-    int sample = -1;          // rows of the threshold sample of a candidate pass (-1: automatic)
-    int split_c = 0;          // reference ranges of the tail query blocks (0: automatic)
-    int force_c = 0;          // reference ranges of EVERY query block (0: off)
-    int no_margin = 0;        // fp16 tier: lists cut at their KS-th best only (round 2's rule)
-    int asv_fast = 0;         // adjust_shift_variance: the tiled form whatever the size
-    int asv_cap = -1;         // tiled form: kept addends per chain of the literal re-run (-1: default, 0: no re-run)
-    int asv_modes = 0;        // tiled form: record which way each of the first n cells of a call went (bmx_dev_get_bytes)
-    int asv_sync = 0;         // tiled form: 1 = the workgroups start each round of tiles together (measured slower twice: rounds 4 and 6)
-    int tau_replay = 0;       // developer experiment: 1 record every search's final thresholds, 2 start the full passes from them
-    int lk_seed = 1;          // k beyond the tiers' lists: partitions after the first searched within the first's kp-th distance (0: plainly)
-    int sample_split = -1;    // ranges of the threshold sample of a search with few query blocks (-1: automatic, 0: never, n: that many)
-    int exchange_always = 0;  // a single rank goes through its exchange transport too (an all-gather of one)
-    int refine_wave = 0;      // the exact re-rank takes a whole wave for every query (no half-wave form)
-    int asv_wide = 0;         // adjust_shift_variance: the literal wide form (asv_wide_pairs + asv_wide_cells) whatever the size
-    int asv_chunk = 0;        // wide form: at most this many cells a chunk (0: as many as 1 GiB of scratch holds)
-};
 DevKnobs& dev_knobs();
 bool debug_prints();   // BMX_DEBUG=1 in the environment (read once)
 bool debug_timings();  // BMX_DEBUG=t or 1
-
-inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // Released device blocks are parked (a few, bounded) and handed out again: a merge engine rebuilds its node buffers at
 // every merge, and hipMalloc / hipFree cost hundreds of microseconds each (hipFree also waits for the device).
@@ -441,34 +418,9 @@ struct KnnWorkspace {
     }
 };
 
-// split-bf16 candidate pass (knn_bf16.hip)
-struct Bf16Launch {
-    const uint16_t* pq;
-    const uint16_t* pr;
-    int nqb, first_begin, range_len, nranges, r_limit, out_chunk0, out_nchunks;
-    uint32_t* tau_g;        // per-query threshold shared by all ranges (orderable image); sample pass writes it
-    int sample;             // non-zero: threshold-estimation pass, writes tau_g[q] only
-    int32_t* cand;
-    float* cand_v;          // approximate values of the candidates
-    float* tau;
-    int n_full = 0;         // the first n_full query blocks sweep [first_begin, r_limit) as ONE range; the others split it
-    // fp16 tier: with margin[q] = twice the pass's error bound for query q (its own units) a list is cut at
-    // (k-th best value + margin) instead of at its KS-th best -- what lies beyond cannot be among the k nearest
-    const float* margin = nullptr;
-    int k = 0;
-    const uint32_t* tau_seed = nullptr;  // fp16 tier, sample pass of a seeded search: tau_g = min(sampled, tau_seed)
-};
-int bf16_pick_ns(int d);         // MFMA k-steps (16 bf16 each) for 3 d + 3 columns; 0 = unsupported
-int bf16_ncons(int NS, int KS);  // consumer waves (32 queries each) per workgroup
-void bf16_prep(hipStream_t stream, const double* X, const int32_t* rows, int n, int n_pad, int d, int NS,
-               const double* mean, int is_query, uint16_t* P, double* n2, unsigned long long* maxbits,
-               unsigned long long* slots);  // slots: 64 x 16 words of scratch for the reference-norm maximum
-bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const Bf16Launch& L);
-int f16_rows_per_slot(int NS, int KS);  // reference rows a ring slot of the fp16 tier holds (ranges are multiples of it)
-
 // For rows q in [q_begin, q_end) of the query list: the k nearest rows of the reference list (exact, FP64 Euclidean,
 // ties by lowest position).  X/Q are row-major [*, d]; ref_rows / q_rows (0-based, may be null = identity) select
-// nr / nq rows.  idx_out [nq][k] receives 0-based POSITIONS in the reference list; dist_out [nq][k] Euclidean
+// the rows.  idx_out [nq][k] receives 0-based POSITIONS in the reference list; dist_out [nq][k] Euclidean
 // distances (may be null).  Only rows [q_begin, q_end) of the outputs are written.
 // seed_d2 (nullable, [nq] f32): per query an upper bound of the squared distance beyond which the caller has no use
 // for neighbours.  The search then starts from that threshold instead of a sampled one and a row may come back with
@@ -479,7 +431,7 @@ int f16_rows_per_slot(int NS, int KS);  // reference rows a ring slot of the fp1
 // centre (nullable, [d] device): a point near the middle of the reference rows (the prepared images are taken relative to
 // it: any vector is valid, a good one keeps the error bound tight); null: the mean of a strided sample is computed here.
 void knn_device(hipStream_t stream, KnnWorkspace& ws, const double* X, const int32_t* ref_rows, int nr,
-                const double* Q, const int32_t* q_rows, int nq, int d, int k, int32_t* idx_out, double* dist_out,
+                const double* Q, const int32_t* q_rows, int d, int k, int32_t* idx_out, double* dist_out,
                 int q_begin, int q_end, const float* seed_d2 = nullptr, const double* centre = nullptr,
                 double* kth_out = nullptr);
 

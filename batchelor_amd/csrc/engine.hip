@@ -454,7 +454,7 @@ void Engine::knn(const double* X, const int32_t* ref_rows, int nr, const double*
     queued_work_s_ += 2e-10 * (double)nq * (double)nr * (double)d_ / 50.0;
     knn_ws_.wd_budget_s = wd_base_s_ > 0.0 ? wd_base_s_ + queued_work_s_ : 0.0;
     try {
-        knn_device(stream_, knn_ws_, X, ref_rows, nr, Q, q_rows, nq, d_, k, idx, dist, (int)b, (int)e, seed_d2, centre, kth);
+        knn_device(stream_, knn_ws_, X, ref_rows, nr, Q, q_rows, d_, k, idx, dist, (int)b, (int)e, seed_d2, centre, kth);
     } catch (const WatchdogTimeout&) {  // (the search's own waits go through knn_ws_.sync, not through wait())
         mark_dead();
         throw;

@@ -19,8 +19,7 @@
 //     A consumer that is busy merging a candidate list therefore delays nobody until the ring runs dry;
 //   * the consumer loop is software-pipelined: under the dependent MFMA chain of tile t the wave refills its
 //     fragment registers with tile t + 1 and filters tile t - 1; appends and list merges of tile t - 1 follow.
-#include "bmx_common.hpp"
-#include "knn_select.hpp"
+#include "knn_internal.hpp"
 
 #include <cmath>
 
@@ -601,7 +600,7 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
 }
 
 template <int NS, int KS>
-void launch(hipStream_t stream, KnnWorkspace& ws, const Bf16Launch& L) {
+void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
     constexpr RingShape SH = ring_shape(NS, KS);
     constexpr int NCONS = SH.ncons, NPROD = SH.nprod, PLN = SH.pln;
     constexpr size_t lds = (size_t)ring_slots(NS, KS, NCONS, PLN) * NS * 1024 +
@@ -679,7 +678,7 @@ void bf16_prep(hipStream_t stream, const double* X, const int32_t* rows, int n, 
     }
 }
 
-bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const Bf16Launch& L) {
+bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L) {
 #define BMX_CASE(N)                        \
     case N:                                \
         if (KS == 24)                      \

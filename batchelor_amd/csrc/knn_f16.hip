@@ -28,8 +28,7 @@
 //     re-reads once per slot, drops to the cut.  They also write the final lists out (the consumers help).
 // Hand-over everywhere through LDS words and counters, no barrier in the loop.  Shared thresholds across reference
 // ranges and the register-only sample pass follow knn_bf16.hip.
-#include "bmx_common.hpp"
-#include "knn_select.hpp"
+#include "knn_internal.hpp"
 
 #include <cmath>
 #include <string>
@@ -1148,7 +1147,7 @@ __global__ __launch_bounds__((NCONS + NPROD + serv_waves(NS)) * 64) void knn_top
             }
         }
         // (a seeded search: the tighter of the sampled threshold and the seed's, prep wrote the latter's image)
-        // A sample split into ranges (few query blocks, see knn.hip): every range's threshold is valid by itself -- k of ITS
+        // A sample split into ranges (few query blocks, see knn_plan.hpp): every range's threshold is valid by itself -- k of ITS
         // references lie at or below it -- so the tightest of them is; prep has written the seed (or +inf) there.
         // Round 6: the ranges also leave their lists (cand_v is free in a sample pass: [query][range][2 x KS / 2] values, all
         // of distinct references), and sample_merge_kernel takes the k-th smallest of their UNION -- what the unsplit sample
@@ -1195,7 +1194,7 @@ __global__ __launch_bounds__((NCONS + NPROD + serv_waves(NS)) * 64) void knn_top
 }
 
 template <int NS, int KS>
-void launch(hipStream_t stream, KnnWorkspace& ws, const Bf16Launch& L) {
+void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
     constexpr int LCAP = list_cap(NS, KS);
     constexpr int TP = tile_pairs_for(NS, KS);
     constexpr size_t lds =
@@ -1311,7 +1310,7 @@ void f16_prep_all(hipStream_t stream, const double* X, const int32_t* rrows, int
     BMX_LAUNCH_CHECK();
 }
 
-bool f16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const Bf16Launch& L) {
+bool f16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L) {
 #define BMX_CASE(N)                       \
     case N:                               \
         if (KS == BMX_KS1)                \

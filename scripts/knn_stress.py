@@ -17,7 +17,7 @@ for case in range(cases):
     nx = int(rng.choice([64, 70, 130, 500, 2100, 4095, 4100, 9000, 20000, 33000, 70000]))
     nq = int(rng.choice([1, 31, 257, 900, 2500, 6000]))
     d = int(rng.integers(2, 126)) if rng.random() < 0.85 else int(rng.integers(126, 220))  # (beyond 125: the FP64 scan)
-    # (beyond 36: the partitioned search of knn.hip; beyond ~900: its big merge)
+    # (beyond 36: the partitioned search of knn_large_k.hip; beyond ~900: its big merge)
     k = int(min(rng.choice([1, 5, 20, 21, 36, 37, 50, 64, 65, 100, 150, 300, 700, 1200, 2500]), nx))
     dup = int(rng.choice([1, 1, 1, 2, 3]))  # every reference cell that many times: ties at the k-th place, decided by position
     force_c = str(rng.choice(["", "1", "2", "3", "5", "7"]))

@@ -1,5 +1,5 @@
 """Developer helper (GPU box): what a search costs beyond 125 columns, where no candidate tier takes the rows and every query goes
-through the FP64 scan (knn.hip: knn_exact_dist / knn_exact_select).   python scripts/wide_rows_probe.py [nx] [nq] [d ...]"""
+through the FP64 scan (knn_exact.hip: knn_exact_dist / knn_exact_select).   python scripts/wide_rows_probe.py [nx] [nq] [d ...]"""
 import os
 import sys
 import time

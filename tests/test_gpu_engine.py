@@ -207,7 +207,7 @@ def test_optimistic_run_starts_over_when_a_search_cannot_be_completed_on_the_dev
 
 
 def test_large_k_with_restriction_and_three_batches(oracle, bx):
-    # k = 50 (beyond the candidate tiers' lists: the partitioned search of knn.hip) through the whole engine, with a restrict
+    # k = 50 (beyond the candidate tiers' lists: the partitioned search of knn_large_k.hip) through the whole engine, with a restrict
     # vector on two of three batches (the searches then run over row LISTS) and prop.k on top
     B = synth_batches(41, [5000, 4200, 3600], 50)
     keep = [np.arange(1, 4001), None, np.arange(300, 3500)]
@@ -217,7 +217,7 @@ def test_large_k_with_restriction_and_three_batches(oracle, bx):
 
 @pytest.mark.parametrize("outliers,retries", [(True, 0), (False, 1)])
 def test_large_k_queries_the_merge_cannot_certify(oracle, bx, outliers, retries):
-    """k = 100: the searches are partitioned (knn.hip, large_k_search: reference rows g with the same g % 7).  Six cells of the
+    """k = 100: the searches are partitioned (knn_large_k.hip, large_k_search: reference rows g with the same g % 7).  Six cells of the
     first batch each have 40 exact copies in the second, all in its first partition: the merge of the partitions' lists cannot
     certify a query that has them among its 100 nearest.  With the six far from everything else only they themselves do: in the
     engine's optimistic run (no host read-back inside a search) those queries take the FP64 scan on the device -- one such query
@@ -243,7 +243,7 @@ def test_large_k_queries_the_merge_cannot_certify(oracle, bx, outliers, retries)
 
 @pytest.mark.parametrize("d,kw", [(140, {}), (131, {"k": 70}), (200, {"prop_k": 0.1})])
 def test_rows_beyond_125_columns(oracle, bx, d, kw):
-    """No candidate tier takes rows of more than 125 columns: every search of the run is the FP64 scan (knn.hip: knn_exact_dist in
+    """No candidate tier takes rows of more than 125 columns: every search of the run is the FP64 scan (knn_exact.hip: knn_exact_dist in
     LDS tiles, knn_exact_select in two sweeps / by bisection) -- same result as the oracle's, pairs bit for bit."""
     B = synth_batches(41, [1500, 2000, 900], d)
     assert_same_result(bx.reducedMNN(*B, **kw), oracle.reduced_mnn(*B, **kw))

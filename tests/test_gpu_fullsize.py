@@ -99,7 +99,7 @@ def test_full_size_engine_properties(data):
 @pytest.mark.parametrize("k", [50, 100])
 def test_full_size_knn_beyond_the_tiers_lists(oracle, data, k):
     """k > 36 at BASELINE config 2's size (`prop.k` = 0.001 of 100 000 cells is k = 100, R/MNN_tree.R:140-146): the partitioned
-    search of knn.hip (large_k_search) on the matrix cores instead of the FP64 scan -- 600 sampled queries against the
+    search of knn_large_k.hip (large_k_search) on the matrix cores instead of the FP64 scan -- 600 sampled queries against the
     oracle's brute force over the FULL reference, indices and distances bitwise."""
     from batchelor_amd import neighbors as nb
     L, R = data
@@ -113,7 +113,7 @@ def test_full_size_knn_beyond_the_tiers_lists(oracle, data, k):
 
 def test_full_size_knn_k_5000(oracle, data):
     """k = 5 000 = prop.k 0.05 of BASELINE config 2's 100 000 cells (R/MNN_tree.R:140-146), all 100 000 queries: the partitioned
-    search with the big merge (knn.hip: lk_merge_big) instead of seconds of FP64 scan; 200 sampled rows against the oracle's brute
+    search with the big merge (knn_large_k.hip: lk_merge_big) instead of seconds of FP64 scan; 200 sampled rows against the oracle's brute
     force over the full reference, indices and distances bitwise.  The time is printed (< 1 s was the mark)."""
     import time
     import torch

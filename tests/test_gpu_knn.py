@@ -63,7 +63,7 @@ def test_query_knn_small_and_edge_shapes(oracle, nb):
 def test_query_knn_beyond_the_tiers_lists(oracle, nb, nx, nq, d, k):
     """k > 36 (`prop.k`, R/MNN_tree.R:140-146; k = 50 is an everyday setting): the reference is dealt into ceil(k / 16) strided
     partitions, each searched at k = 36 on the matrix cores, the candidates merged exactly with a certificate that no
-    partition's list ends inside the first k (knn.hip: large_k_search).  Same bar as everywhere: indices equal, distances
+    partition's list ends inside the first k (knn_large_k.hip: large_k_search).  Same bar as everywhere: indices equal, distances
     bitwise.  (The last shape is too small for partitions of 144 cells: it takes the FP64 scan, as k > 36 did before.)"""
     X, Q = synth_batches(1, [nx, nq], d)
     idx, dist = nb.query_knn(X, Q, k)
@@ -77,7 +77,7 @@ def test_query_knn_beyond_the_tiers_lists(oracle, nb, nx, nq, d, k):
 @pytest.mark.parametrize("nx,nq,d,k", [(40000, 600, 50, 1000), (60000, 400, 20, 2500), (100000, 300, 50, 5000)])
 def test_query_knn_k_beyond_900(oracle, nb, nx, nq, d, k):
     """`prop.k` = 0.05 of 100 000 cells is k = 5 000 (R/MNN_tree.R:140-146): more candidates a query (P x 36, P = ceil(k / 14))
-    than the rank-counting merges take -- knn.hip: lk_merge_big, the k-th smallest by bisection on the distances' bit patterns,
+    than the rank-counting merges take -- knn_large_k.hip: lk_merge_big, the k-th smallest by bisection on the distances' bit patterns,
     only the selected sorted.  Same bar: indices equal, distances bitwise, none of it through the FP64 scan."""
     X, Q = synth_batches(3, [nx, nq], d)
     idx, dist = nb.query_knn(X, Q, k)
@@ -100,7 +100,7 @@ def test_query_knn_k_beyond_900_with_exact_duplicates(oracle, nb):
                                            (700, 30, 200, 700, 2), (8192, 20, 129, 8192, 1)])
 def test_full_scan_selection_beyond_64_neighbours(oracle, nb, nx, nq, d, k, dup):
     """d > 127: every query takes the FP64 scan; k > 64: its selection is the bisection on the distances' bit patterns
-    (knn.hip: knn_exact_select_big).  Each reference cell `dup` times: the k-th place falls among equal distances and is
+    (knn_exact.hip: knn_exact_select_big).  Each reference cell `dup` times: the k-th place falls among equal distances and is
     decided by position, as the reference's search order decides it."""
     X0, Q = synth_batches(11, [nx // dup, nq], d)
     X = np.concatenate([X0] * dup)
@@ -112,7 +112,7 @@ def test_full_scan_selection_beyond_64_neighbours(oracle, nb, nx, nq, d, k, dup)
 
 @pytest.mark.parametrize("k", [100, 300, 1000])
 def test_large_k_partitions_seeded_by_the_first(oracle, nb, dev, k):
-    """knn.hip, large_k_search: the partitions (reference rows g with the same g % P) after the first are searched within the
+    """knn_large_k.hip, large_k_search: the partitions (reference rows g with the same g % P) after the first are searched within the
     first's 36th distance.  Same answers with and without; and the case the seed is worthless for: 40 exact copies of a query,
     all in the first partition -- its 36th distance is 0, the other partitions' lists come back empty, fewer than k candidates in
     all: the certificate must send those queries to the exact scan."""
@@ -245,3 +245,46 @@ def test_rank_cut_without_the_margin_and_near_ties(oracle, nb, dev):
     idx, dist = nb.query_knn(X, Q, 20)
     oi, od = oracle.query_knn(X, Q, 20)
     assert np.array_equal(idx, oi) and np.array_equal(dist, od)
+
+
+@pytest.mark.parametrize("k", [5, 20])
+@pytest.mark.parametrize("d", [3, 8, 16, 26, 50, 56, 72, 104, 124])
+def test_refine_forms_agree(oracle, nb, dev, d, k):
+    # The FP64 re-rank has two forms (half a wave per query, a whole wave per query), each instantiated per row length:
+    # d = 3 (odd) takes the lane-per-row gather, the others the quad chain with 2, 2, 4, 7, 7, 10, 13 and 16 pieces a lane.
+    # 3 000 references are one range (fewer than 4 096), so without the hook every query takes the half-wave form and with
+    # it every query the whole-wave form.
+    nq = 500
+    X, Q = synth_batches(1, [3000, nq], d)
+    oi, od = oracle.query_knn(X, Q, k)
+    for wave in (0, 1):
+        dev("refine_wave", wave)
+        idx, dist = nb.query_knn(X, Q, k)
+        assert np.array_equal(idx, oi)
+        assert np.array_equal(dist, od)
+        assert nb.last_knn_exact_fallbacks() <= nq // 100  # (the re-rank, not the exact scan, produced the rows)
+
+
+def test_refine_forms_agree_in_one_search(nb, dev):
+    # Both forms in ONE search: 66 000 queries are 258 query blocks; the first 256 sweep the 4 200 references as one range
+    # (half-wave re-rank), the last two are split into C = 2 ranges (whole-wave re-rank from query 65 536 on, over two lists).
+    # BMX_DEBUG=1 printed for this search:
+    #   [bmx] knn tier 1: nq=66000 nr=4200 d=8 NS=1 KS=32 S=1152 C=2 chunk=2176 full-range blocks=256 of 258
+    nq, k = 66000, 5
+    X, Q = synth_batches(1, [4200, nq], 8)
+    idx, dist = nb.query_knn(X, Q, k)
+    assert nb.last_knn_exact_fallbacks() <= nq // 100
+    dev("refine_wave", 1)
+    idx_w, dist_w = nb.query_knn(X, Q, k)
+    assert nb.last_knn_exact_fallbacks() <= nq // 100
+    assert np.array_equal(idx, idx_w)
+    assert np.array_equal(dist, dist_w)
+    # (the oracle takes too long at this size: the last 1 000 queries -- 536 of the half-wave form, 464 of the other --
+    # against the full FP64 scan)
+    nb.set_force_exact_knn(True)
+    try:
+        idx_x, dist_x = nb.query_knn(X, Q[-1000:], k)
+    finally:
+        nb.set_force_exact_knn(False)
+    assert np.array_equal(idx[-1000:], idx_x)
+    assert np.array_equal(dist[-1000:], dist_x)
