@@ -1,4 +1,5 @@
-"""The Python side of a library handle that keeps genes x cells batches in HBM (bmx_pca_t, bmx_cluster_t, bmx_linear_t)."""
+"""The Python side of a library handle that keeps genes x cells batches in HBM, dense (bmx_pca_t, bmx_cluster_t,
+bmx_linear_t, bmx_norm_t) or as CSC (bmx_pca_sparse_t, bmx_norm_sparse_t)."""
 from __future__ import annotations
 
 import ctypes
@@ -6,6 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .inputs import csc_blocks
 
 
 class ResidentHandle:
@@ -52,6 +54,19 @@ class ResidentHandle:
             xb = _lib.as_f(x[:, a:a + block])
             self._call("add_block", _lib.f64p(xb), ctypes.c_int64(xb.shape[1]))
         self.ncells.append(n)
+
+    def _upload_csc(self, c, per, *begin_args):
+        """c: canonical CSC (inputs.canonical_csc), announced with begin_batch(n, *begin_args, nnz); it goes over in
+        column blocks of `per` cells."""
+        n = int(c.shape[1])
+        self._call("begin_batch", ctypes.c_int64(n), *begin_args, ctypes.c_int64(int(c.nnz)))
+        self.ncells.append(n)
+        for block in csc_blocks(c, per):
+            self._add_csc_block(*block)
+
+    def _add_csc_block(self, m, indptr, indices, data):
+        self._call("add_block", ctypes.c_int64(int(m)), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
+                   _lib.f64p(data), ctypes.c_int64(int(data.size)))
 
     def stage_ms(self):
         st = np.zeros(len(self.STAGES), dtype=np.float64)

@@ -1,0 +1,66 @@
+// Device helpers of the kernels that read a batch kept as CSC (indptr absolute, rows ascending within a column): NormSparse
+// (multi_batch_norm.hip) and PcaSparse (pca_sparse.hip).  The store and the host's checks are in resident_batches.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace bmx {
+
+// Entry k (row r) of the column that begins at kb: a row that is not above the one stored before it sets bad_order, a row
+// outside [0, G) sets bad_row.  Whether the row is outside: the entry then addresses nothing and is left out.
+__device__ __forceinline__ bool csc_entry_flags(const int32_t* __restrict__ idx, int64_t k, int64_t kb, int32_t r, int G,
+                                                int& bad_row, int& bad_order) {
+    if (k > kb && idx[k - 1] >= r) bad_order = 1;
+    if (r >= 0 && r < G) return false;
+    bad_row = 1;
+    return true;
+}
+
+// the first position in [lo, hi) whose row is not below g (rows ascending; on rows in any order it still ends, somewhere
+// in [lo, hi])
+__device__ __forceinline__ int64_t first_row_at_least(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int g) {
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (idx[mid] < g) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A workgroup of 256 threads walks the cells [chunk * CELLS, min(n, (chunk + 1) * CELLS)) x the rows [g0, g1): thread t
+// first finds the tile's entries in the chunk's column t (lo / hi: the caller's shared arrays [CELLS]); after a barrier
+// the columns are taken one after the other, col_begin(c) at the start of cell c's column, then the threads stride over
+// the column's entries in the tile, entry(c, k, r) for position k with row r, and a barrier before the next column.  Rows
+// are unique within a canonical column, so no two threads meet at a row; on any pattern r stays inside [g0, g1).  (The
+// callbacks get the cell and not its number in the chunk: handed the number, sp_sort_kernel<true> came out 1.5 % slower.)
+template <int CELLS, class ColBegin, class Entry>
+__device__ __forceinline__ void csc_tile_walk(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int64_t n,
+                                              int64_t chunk, int g0, int g1, int64_t* lo, int64_t* hi, ColBegin&& col_begin,
+                                              Entry&& entry) {
+    const int64_t b = chunk * CELLS;
+    const int ncol = (int)((b + CELLS < n ? b + CELLS : n) - b);
+    if ((int)threadIdx.x < ncol) {
+        const int64_t kb = indptr[b + threadIdx.x], ke = indptr[b + threadIdx.x + 1];
+        const int64_t first = first_row_at_least(idx, kb, ke, g0);
+        lo[threadIdx.x] = first;
+        hi[threadIdx.x] = first_row_at_least(idx, first, ke, g1);
+    }
+    __syncthreads();
+    for (int j = 0; j < ncol; ++j) {
+        col_begin(b + j);
+        const int64_t ke = hi[j];
+        for (int64_t k = lo[j] + threadIdx.x; k < ke; k += 256) {
+            const int r = idx[k];
+            if (r >= g0 && r < g1) entry(b + j, k, r);
+        }
+        __syncthreads();
+    }
+}
+template <int CELLS, class Entry>
+__device__ __forceinline__ void csc_tile_walk(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int64_t n,
+                                              int64_t chunk, int g0, int g1, int64_t* lo, int64_t* hi, Entry&& entry) {
+    csc_tile_walk<CELLS>(indptr, idx, n, chunk, g0, g1, lo, hi, [](int64_t) {}, entry);
+}
+
+}  // namespace bmx

@@ -27,7 +27,7 @@
 //                           has one accumulator and takes its terms in cell order, as gene_partial_kernel's does; the
 //                           terms left out are x / w = +0, which change no bit of a sum of non-negative terms.
 //   sp_out_kernel           one wave a column over the stored entries only; zero_image_kernel: what a zero becomes
-// Every entry position comes from an indptr the host has checked (norm_check_sparse_block); a row index is compared
+// Every entry position comes from an indptr the host has checked (check_csc_block); a row index is compared
 // with its bounds before it addresses anything, and an entry that fails is skipped.
 #include <algorithm>
 #include <cmath>
@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "bmx_ops.hpp"
+#include "csc_device.hpp"
 #include "host_xfer.hpp"
 #include "resident_batches.hpp"
 
@@ -51,8 +52,8 @@ constexpr double DBL_LARGEST = 1.7976931348623157e308;
 // flags (device): a count that is negative or not finite, a size factor that is not positive, a pair without a finite
 // median ratio; [3]: the reference batch (0-based)
 enum { F_COUNT = 0, F_SF = 1, F_RATIO = 2, F_SMALLEST = 3, F_WORDS = 4 };
-// the sparse handle's further words: a row index outside [0, G), rows of a column that do not ascend strictly
-enum { F_ROW = 4, F_ORDER = 5, F_SPARSE_WORDS = 6 };
+// the sparse handle's further words: the pattern pair (CSC_F_ROW, CSC_F_ORDER)
+enum { F_PATTERN = 4, F_SPARSE_WORDS = F_PATTERN + CSC_F_WORDS };
 constexpr int GT = 4096;  // genes per tile of the sparse per-gene sums (32 KiB of accumulators in the LDS)
 
 __device__ __forceinline__ int invalid_count(double v) { return !(v >= 0.0 && v <= DBL_LARGEST); }
@@ -368,8 +369,7 @@ __global__ __launch_bounds__(256) void norm_out_kernel(const double* __restrict_
 
 // The library sizes of the cells [c0, c0 + m), one wave a cell: lane l adds the column's entries l, l + 64, ..., then
 // the lanes are added in a fixed order.  mult (nullable): every value times mult[row].  w null: the entries are checked
-// only.  An entry whose row is outside [0, G) raises F_ROW and is left out; a row that is not above the one stored
-// before it raises F_ORDER.
+// only.  The pattern flags (csc_entry_flags) go to flags + F_PATTERN; an entry whose row is outside [0, G) is left out.
 __global__ __launch_bounds__(256) void sp_colsum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
                                                         const double* __restrict__ val, int G, int64_t c0, int64_t m,
                                                         const double* __restrict__ mult, double* __restrict__ w,
@@ -384,37 +384,20 @@ __global__ __launch_bounds__(256) void sp_colsum_kernel(const int64_t* __restric
         const int32_t r = idx[k];
         double v = val[k];
         bad |= invalid_count(v);
-        if (k > kb && idx[k - 1] >= r) bad_order = 1;
-        if (r < 0 || r >= G) {
-            bad_row = 1;
-            continue;
-        }
+        if (csc_entry_flags(idx, k, kb, r, G, bad_row, bad_order)) continue;
         if (mult) v *= mult[r];
         s += v;
     }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
     if (bad) flags[F_COUNT] = 1;
-    if (bad_row) flags[F_ROW] = 1;
-    if (bad_order) flags[F_ORDER] = 1;
+    if (bad_row) flags[F_PATTERN + CSC_F_ROW] = 1;
+    if (bad_order) flags[F_PATTERN + CSC_F_ORDER] = 1;
     if (lane == 0 && w) w[c] = s;
 }
 
-// the first position in [lo, hi) whose row is not below g (rows ascending; on rows in any order it still ends, somewhere
-// in [lo, hi])
-__device__ __forceinline__ int64_t first_row_at_least(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int g) {
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (idx[mid] < g) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // part[ch][g] = sum over the cells [ch * NCH, min(n, (ch + 1) * NCH)), in order, of x[g, cell] / w[cell] for the genes g
-// of tile blockIdx.y, all G rows (part is [nchunks][G]).  Thread t first finds the tile's entries in the chunk's column t;
-// then the columns are taken one after the other, the threads striding over a column's entries in the tile, with a
-// barrier before the next column.  Rows are unique within a canonical column, so no two threads meet at an accumulator
-// (on a column that is not canonical they may, F_ORDER has been raised for it, and the addresses stay inside the tile).
+// of tile blockIdx.y, all G rows (part is [nchunks][G]), by csc_tile_walk: no two threads meet at an accumulator (on a
+// column that is not canonical they may, CSC_F_ORDER has been raised for it, and the addresses stay inside the tile).
 __global__ __launch_bounds__(256) void sp_gene_partial_kernel(const int64_t* __restrict__ indptr,
                                                               const int32_t* __restrict__ idx,
                                                               const double* __restrict__ val, int G,
@@ -424,25 +407,11 @@ __global__ __launch_bounds__(256) void sp_gene_partial_kernel(const int64_t* __r
     __shared__ int64_t lo[NCH], hi[NCH];
     const int ch = ch0 + blockIdx.x;
     const int g0 = blockIdx.y * GT, g1 = min(G, g0 + GT);
-    const int64_t b = (int64_t)ch * NCH;
-    const int ncol = (int)((b + NCH < n ? b + NCH : n) - b);
     for (int i = threadIdx.x; i < g1 - g0; i += 256) acc[i] = 0.0;
-    if ((int)threadIdx.x < ncol) {
-        const int64_t kb = indptr[b + threadIdx.x], ke = indptr[b + threadIdx.x + 1];
-        const int64_t first = first_row_at_least(idx, kb, ke, g0);
-        lo[threadIdx.x] = first;
-        hi[threadIdx.x] = first_row_at_least(idx, first, ke, g1);
-    }
-    __syncthreads();
-    for (int j = 0; j < ncol; ++j) {
-        const double wj = w[b + j];
-        const int64_t ke = hi[j];
-        for (int64_t k = lo[j] + threadIdx.x; k < ke; k += 256) {
-            const int r = idx[k];
-            if (r >= g0 && r < g1) acc[r - g0] += val[k] / wj;
-        }
-        __syncthreads();
-    }
+    double wc = 0.0;
+    csc_tile_walk<NCH>(
+        indptr, idx, n, ch, g0, g1, lo, hi, [&](int64_t c) { wc = w[c]; },
+        [&](int64_t, int64_t k, int r) { acc[r - g0] += val[k] / wc; });
     for (int i = threadIdx.x; i < g1 - g0; i += 256) part[(int64_t)ch * G + g0 + i] = acc[i];
 }
 
@@ -509,21 +478,6 @@ void norm_check_run(double min_mean, int log, double pseudo_count) {
     if (min_mean != min_mean) throw Error(BMX_ERR_ARG, "'min_mean' must be a number");
     if (log != 0 && log != 1) throw Error(BMX_ERR_ARG, "'log' is 0 or 1");
     if (!std::isfinite(pseudo_count)) throw Error(BMX_ERR_ARG, "'pseudo_count' must be finite");
-}
-
-// a block of m cells for a batch of n cells that holds `filled` so far, without a device (throws Error(BMX_ERR_ARG)):
-// indptr [m + 1] relative to the block (starts at 0, never decreases, ends at nnz); indices / data [nnz]
-void norm_check_sparse_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
-                             const double* data, int64_t nnz) {
-    if (!indptr) throw Error(BMX_ERR_ARG, "the block's 'indptr' is missing");
-    if (nnz < 0) throw Error(BMX_ERR_ARG, "the block's number of stored entries is negative");
-    if (nnz > 0 && (!indices || !data)) throw Error(BMX_ERR_ARG, "the block's 'indices' or 'data' is missing");
-    if (n < 1 || filled < 0 || m < 1 || m > n || filled > n - m)
-        throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
-    if (indptr[0] != 0) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not start at 0");
-    for (int64_t i = 0; i < m; ++i)
-        if (indptr[i + 1] < indptr[i]) throw Error(BMX_ERR_ARG, "the block's 'indptr' decreases");
-    if (indptr[m] != nnz) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not end at its number of stored entries");
 }
 
 // what both handles keep for a batch beside its counts
@@ -790,14 +744,7 @@ class Norm : ResidentBatches<NormBatch> {
 
 // ---- the same for sparse counts: a batch is kept as CSC (indptr int64, 0-based int32 rows, FP64 values), its cells
 // arrive in column blocks, and the values are written for the stored entries only.
-struct SparseNormBatch : BlockLedger, NormStats {
-    static constexpr bool dense_x = false;
-    DevBuf<int64_t> indptr;        // [n + 1] absolute positions
-    DevBuf<int32_t> indices;       // [nnz] 0-based rows
-    DevBuf<double> data;           // [nnz]
-    std::vector<int64_t> hindptr;  // indptr on the host: the output pass cuts its blocks by it
-    int64_t nnz = 0, nnz_filled = 0;
-};
+struct SparseNormBatch : CscBatch, NormStats {};
 
 class NormSparse : ResidentBatches<SparseNormBatch> {
   public:
@@ -824,13 +771,7 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
     // a batch of n cells with nnz stored entries in all; size_factors as for Norm::begin_batch
     void begin_batch(int64_t n, const double* size_factors, int64_t nnz) {
         norm_check_batch(n, size_factors);
-        if (nnz < 0) throw Error(BMX_ERR_ARG, "the batch's number of stored entries is negative");
-        begin(n, [&](SparseNormBatch& b) {
-            b.nnz = nnz;
-            b.indptr.reserve((size_t)n + 1);
-            b.indices.reserve((size_t)std::max<int64_t>(nnz, 1));
-            b.data.reserve((size_t)std::max<int64_t>(nnz, 1));
-            b.hindptr.assign((size_t)n + 1, 0);
+        begin_csc(n, nnz, [&](SparseNormBatch& b) {
             b.nchunks = cdiv(n, NCH);
             b.part.reserve((size_t)b.nchunks * G_);
             b.w.reserve((size_t)n);
@@ -847,30 +788,16 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
     // the next m cells of the batch begun last: indptr [m + 1] relative to the block, its nnz entries
     void add_block(int64_t m, const int64_t* indptr, const int32_t* indices, const double* data, int64_t nnz) {
         const double t0 = now_ms();
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        SparseNormBatch* bp = batches_.empty() ? nullptr : batches_.back().get();
-        check_block(bp, indptr, m, begin_entry_);
-        SparseNormBatch& b = *bp;
-        norm_check_sparse_block(b.n, b.filled, m, indptr, indices, data, nnz);
-        if (nnz > b.nnz - b.nnz_filled) throw Error(BMX_ERR_ARG, "the block holds more entries than the batch announced");
-        if (b.filled + m == b.n && b.nnz_filled + nnz != b.nnz)
-            throw Error(BMX_ERR_ARG, "the batch has received fewer entries than it announced");
-        int64_t* habs = b.hindptr.data() + b.filled;
-        for (int64_t i = 0; i <= m; ++i) habs[i] = b.nnz_filled + indptr[i];
-        upload_pageable(b.indptr.p + b.filled, habs, (size_t)(m + 1) * sizeof(int64_t), stream_);
-        upload_pageable(b.indices.p + b.nnz_filled, indices, (size_t)nnz * sizeof(int32_t), stream_);
-        upload_pageable(b.data.p + b.nnz_filled, data, (size_t)nnz * sizeof(double), stream_);
-        b.filled += m;
-        b.nnz_filled += nnz;
-        BMX_HIP(hipEventRecord(landed_, stream_));
-        BMX_HIP(hipStreamWaitEvent(kstream_, landed_, 0));
-        launch_sums(b, b.filled - m, m);
-        if (b.complete()) {
-            BMX_HIP(hipStreamSynchronize(stream_));
-            BMX_HIP(hipStreamSynchronize(kstream_));
-            timer_.collect(ms_);
-        }
+        add_csc(m, indptr, indices, data, nnz, [&](SparseNormBatch& b, int64_t c0) {
+            BMX_HIP(hipEventRecord(landed_, stream_));
+            BMX_HIP(hipStreamWaitEvent(kstream_, landed_, 0));
+            launch_sums(b, c0, m);
+            if (b.complete()) {
+                BMX_HIP(hipStreamSynchronize(stream_));
+                BMX_HIP(hipStreamSynchronize(kstream_));
+                timer_.collect(ms_);
+            }
+        });
         ms_[0] += now_ms() - t0;
     }
 
@@ -905,7 +832,24 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         else
             hipLaunchKernelGGL(zero_image_kernel<false>, dim3(1), dim3(64), 0, kstream_, pseudo, zero_.p);
         BMX_LAUNCH_CHECK();
-        blocked_output_sparse(log, pseudo, outs);
+        // a block: whole cells of a batch with at most OUT_BLOCK_BYTES of stored entries (one cell if it alone has more)
+        std::vector<OutBlock> blocks;
+        for (size_t bi = 0; bi < batches_.size(); ++bi)
+            for (OutBlock k : plan_csc_output_blocks(batches_[bi]->hindptr.data(), batches_[bi]->n,
+                                                     (int64_t)(OUT_BLOCK_BYTES / sizeof(double)))) {
+                k.bi = (int)bi;
+                blocks.push_back(k);
+            }
+        run_output_blocks(blocks, kstream_, stream_, timer_, 3, out_, outs, [&](const OutBlock& k, double* out) {
+            const SparseNormBatch& b = *batches_[(size_t)k.bi];
+            const dim3 grid((unsigned)cdiv(k.mb, 4));
+            if (log)
+                hipLaunchKernelGGL(sp_out_kernel<true>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
+                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, out);
+            else
+                hipLaunchKernelGGL(sp_out_kernel<false>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
+                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, out);
+        });
         ms_[4] += now_ms() - t0;
 
         int32_t flags[F_SPARSE_WORDS] = {0, 0, 0, 0, 0, 0};
@@ -915,9 +859,7 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         timer_.collect(ms_);
         if (smallest_out) *smallest_out = flags[F_SMALLEST] + 1;
         if (zero_out) *zero_out = zero;
-        if (flags[F_ROW]) throw Error(BMX_ERR_ARG, "sparse counts: a row index is outside [0, number of genes)");
-        if (flags[F_ORDER])
-            throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
+        throw_if_bad_pattern(flags + F_PATTERN);
         throw_if_flagged(flags);
     }
 
@@ -944,64 +886,6 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
         }
         b.sum_done = std::max(b.sum_done, complete);
         timer_.span(1, ea, mark());
-    }
-
-    // blocked_output over the stored entries: a block is a run of whole cells of a batch with at most OUT_BLOCK_BYTES of
-    // entries (one cell if that cell alone has more); its values go to outs[batch] at the position of its first entry
-    // through the download ring while the next block's kernel writes the other buffer.
-    void blocked_output_sparse(int log, double pseudo, double* const* outs) {
-        struct Blk {
-            int bi;
-            int64_t c0;
-            int mb;
-        };
-        const int64_t cap = (int64_t)(OUT_BLOCK_BYTES / sizeof(double));
-        std::vector<Blk> blocks;
-        int64_t largest = 1;
-        for (size_t bi = 0; bi < batches_.size(); ++bi) {
-            const std::vector<int64_t>& hp = batches_[bi]->hindptr;
-            const int64_t n = batches_[bi]->n;
-            for (int64_t c0 = 0; c0 < n;) {
-                // the last c1 <= c0 + 2^30 with hp[c1] - hp[c0] <= cap, but one cell at the least
-                const int64_t end = std::min(n, c0 + ((int64_t)1 << 30));
-                int64_t c1 = std::upper_bound(hp.begin() + c0, hp.begin() + end + 1, hp[(size_t)c0] + cap) - hp.begin() - 1;
-                c1 = std::max(c1, c0 + 1);
-                if (hp[(size_t)c1] > hp[(size_t)c0]) {  // (a block of empty cells has nothing to write)
-                    blocks.push_back({(int)bi, c0, (int)(c1 - c0)});
-                    largest = std::max(largest, hp[(size_t)c1] - hp[(size_t)c0]);
-                }
-                c0 = c1;
-            }
-        }
-        if (blocks.empty()) return;
-        double* dev[2] = {out_[0].reserve((size_t)largest), out_[1].reserve((size_t)largest)};
-        std::vector<int> done(blocks.size(), -1);
-        auto queue = [&](size_t i) {
-            const Blk& k = blocks[i];
-            const SparseNormBatch& b = *batches_[(size_t)k.bi];
-            const int ea = mark();
-            const dim3 grid((unsigned)cdiv(k.mb, 4));
-            if (log)
-                hipLaunchKernelGGL(sp_out_kernel<true>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
-                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, dev[i & 1]);
-            else
-                hipLaunchKernelGGL(sp_out_kernel<false>, grid, dim3(256), 0, kstream_, (const int64_t*)b.indptr.p,
-                                   (const double*)b.data.p, k.c0, k.mb, (const double*)b.sfo.p, pseudo, dev[i & 1]);
-            BMX_LAUNCH_CHECK();
-            done[i] = mark();
-            timer_.span(3, ea, done[i]);
-        };
-        queue(0);
-        for (size_t i = 0; i < blocks.size(); ++i) {
-            if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
-            const Blk& k = blocks[i];
-            const std::vector<int64_t>& hp = batches_[(size_t)k.bi]->hindptr;
-            const int64_t k0 = hp[(size_t)k.c0], k1 = hp[(size_t)(k.c0 + k.mb)];
-            BMX_HIP(hipStreamWaitEvent(stream_, timer_.event(done[i]), 0));
-            download_pageable(outs[k.bi] + k0, dev[i & 1], (size_t)(k1 - k0) * sizeof(double), stream_);
-        }
-        BMX_HIP(hipStreamSynchronize(kstream_));
-        BMX_HIP(hipStreamSynchronize(stream_));
     }
 
     hipStream_t kstream_ = nullptr;  // kernels (the store's stream_ takes the copies)
@@ -1081,7 +965,7 @@ void bmx_norm_sparse_destroy(bmx_norm_sparse_t* h) { delete h; }
 
 int32_t bmx_norm_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
                                     const int32_t* indices, const double* data, int64_t nnz) {
-    return bmx::guarded([&] { bmx::norm_check_sparse_block(n, filled, n_block, indptr, indices, data, nnz); });
+    return bmx::guarded([&] { bmx::check_csc_block(n, filled, n_block, indptr, indices, data, nnz); });
 }
 
 int32_t bmx_norm_sparse_begin_batch(bmx_norm_sparse_t* h, int64_t n, const double* size_factors, int64_t nnz) {

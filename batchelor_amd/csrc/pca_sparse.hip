@@ -35,22 +35,18 @@
 #include <vector>
 
 #include "bmx_ops.hpp"
+#include "csc_device.hpp"
 #include "host_xfer.hpp"
 #include "pca_iteration.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
 
-// (multi_batch_norm.hip) the checks of a CSC block without a device
-void norm_check_sparse_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
-                             const double* data, int64_t nnz);
-
 namespace {
 
 constexpr int SEG = PCA_SPARSE_ROW_SEGMENT;  // entries of a row one wave adds
 constexpr int CH = 128;                      // cells per chunk of the counting sort
 constexpr int GT = 4096;                     // rows per tile of the counting sort (16 KiB of counters in the LDS)
-enum { F_ROW = 0, F_ORDER = 1, F_WORDS = 2 };
 
 __device__ __forceinline__ int64_t wave_uniform(int64_t v) {  // v is the same in every lane: keep it in scalar registers
     const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
@@ -98,8 +94,7 @@ __device__ __forceinline__ double gather_rows64(const int32_t* __restrict__ idx,
 }
 
 // The cells [c0, c0 + m), one wave a cell: cut[c] = the position after the column's last entry below row Gp (its PCA
-// prefix), inv[c] = 1 / max(1e-8, l2 over the prefix) (inv null: not wanted).  A row outside [0, G) raises F_ROW, a row
-// that is not above the one stored before it F_ORDER.
+// prefix), inv[c] = 1 / max(1e-8, l2 over the prefix) (inv null: not wanted).  flags: the pattern pair (csc_entry_flags).
 __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
                                                          const double* __restrict__ val, int G, int Gp, int64_t c0,
                                                          int64_t m, int64_t* __restrict__ cut, double* __restrict__ inv,
@@ -112,11 +107,7 @@ __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restri
     int below = 0, bad_row = 0, bad_order = 0;
     for (int64_t k = kb + lane; k < ke; k += 64) {
         const int32_t r = idx[k];
-        if (k > kb && idx[k - 1] >= r) bad_order = 1;
-        if (r < 0 || r >= G) {
-            bad_row = 1;
-            continue;
-        }
+        if (csc_entry_flags(idx, k, kb, r, G, bad_row, bad_order)) continue;
         if (r < Gp) {
             const double v = val[k];
             ++below;
@@ -127,8 +118,8 @@ __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restri
         s += __shfl_xor(s, o);
         below += __shfl_xor(below, o);
     }
-    if (bad_row) flags[F_ROW] = 1;
-    if (bad_order) flags[F_ORDER] = 1;
+    if (bad_row) flags[CSC_F_ROW] = 1;
+    if (bad_order) flags[CSC_F_ORDER] = 1;
     if (lane == 0) {
         cut[c] = kb + below;
         if (inv) {
@@ -138,20 +129,8 @@ __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restri
     }
 }
 
-// the first position in [lo, hi) whose row is not below g (rows ascending; on rows in any order it still ends, somewhere
-// in [lo, hi])
-__device__ __forceinline__ int64_t first_row_at_least(const int32_t* __restrict__ idx, int64_t lo, int64_t hi, int g) {
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (idx[mid] < g) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// The counting sort's two walks, workgroup (chunk, row tile): the chunk's columns in ascending order, the threads
-// striding over a column's entries in the tile, a barrier before the next column.  Rows are unique within a canonical
-// column, so no two threads meet at a counter (where they do, F_ORDER has been raised and the fit will refuse).
+// The counting sort's two walks (csc_tile_walk), workgroup (chunk, row tile).  Rows are unique within a canonical
+// column, so no two threads meet at a counter (where they do, CSC_F_ORDER has been raised and the fit will refuse).
 //   PLACE = false:  cnt[chunk][g] = the chunk's entries of row g
 //   PLACE = true:   cnt[chunk][g] holds the row's entries in the chunks before; an entry goes to rowptr[g] + that count
 //                   (kept inside the row whatever the pattern), with its cell and its value times scale
@@ -165,33 +144,18 @@ __global__ __launch_bounds__(256) void sp_sort_kernel(const int64_t* __restrict_
     __shared__ int64_t lo[CH], hi[CH];
     const int64_t ch = blockIdx.x;
     const int g0 = blockIdx.y * GT, g1 = min(G, g0 + GT);
-    const int64_t b = ch * CH;
-    const int ncol = (int)((b + CH < n ? b + CH : n) - b);
     for (int i = threadIdx.x; i < g1 - g0; i += 256) acc[i] = PLACE ? cnt[ch * G + g0 + i] : 0;
-    if ((int)threadIdx.x < ncol) {
-        const int64_t kb = indptr[b + threadIdx.x], ke = indptr[b + threadIdx.x + 1];
-        const int64_t first = first_row_at_least(idx, kb, ke, g0);
-        lo[threadIdx.x] = first;
-        hi[threadIdx.x] = first_row_at_least(idx, first, ke, g1);
-    }
-    __syncthreads();
-    for (int j = 0; j < ncol; ++j) {
-        const int64_t ke = hi[j];
-        for (int64_t k = lo[j] + threadIdx.x; k < ke; k += 256) {
-            const int r = idx[k];
-            if (r < g0 || r >= g1) continue;
-            const int32_t p = acc[r - g0];
-            acc[r - g0] = p + 1;
-            if (PLACE) {
-                const int64_t at = rowptr[r] + p;
-                if (at < rowptr[r + 1]) {
-                    rcol[at] = (int32_t)(b + j);
-                    rval[at] = scale ? val[k] * scale[b + j] : val[k];
-                }
+    csc_tile_walk<CH>(indptr, idx, n, ch, g0, g1, lo, hi, [&](int64_t c, int64_t k, int r) {
+        const int32_t p = acc[r - g0];
+        acc[r - g0] = p + 1;
+        if (PLACE) {
+            const int64_t at = rowptr[r] + p;
+            if (at < rowptr[r + 1]) {
+                rcol[at] = (int32_t)c;
+                rval[at] = scale ? val[k] * scale[c] : val[k];
             }
         }
-        __syncthreads();
-    }
+    });
     if (!PLACE)
         for (int i = threadIdx.x; i < g1 - g0; i += 256) cnt[ch * G + g0 + i] = acc[i];
 }
@@ -339,19 +303,13 @@ __global__ __launch_bounds__(256) void mu_dot_partial(const double* __restrict__
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-struct SparsePcaBatch : BlockLedger {
-    static constexpr bool dense_x = false;
-    DevBuf<int64_t> indptr;   // [n + 1] absolute positions
-    DevBuf<int32_t> indices;  // [nnz] 0-based rows
-    DevBuf<double> data;      // [nnz]
-    DevBuf<int64_t> cut;      // [n] the end of the column's PCA prefix
-    DevBuf<double> inv;       // [n] 1 / max(1e-8, l2 over the prefix), empty without cosine normalisation
+struct SparsePcaBatch : CscBatch {
+    DevBuf<int64_t> cut;  // [n] the end of the column's PCA prefix
+    DevBuf<double> inv;   // [n] 1 / max(1e-8, l2 over the prefix), empty without cosine normalisation
     // the row-major companion, built after the last block
     DevBuf<int64_t> rowptr, segptr;  // [n_rows + 1]
     DevBuf<int32_t> rcol;            // [nnz] cells, ascending within a row
     DevBuf<double> rval;             // [nnz] scale_c x_gc
-    std::vector<int64_t> hindptr;    // the block's absolute indptr on its way to the device
-    int64_t nnz = 0, nnz_filled = 0;
     int64_t segs_pca = 0, segs_all = 0;  // segptr[n_rows_pca], segptr[n_rows]
     double weight = 1.0;
     bool cos_norm = false;
@@ -362,7 +320,7 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
     PcaSparse(int device, int n_rows, int n_rows_pca)
         : ResidentBatches(device, n_rows, "bmx_pca_sparse_begin_batch"), Gp_(n_rows_pca) {
         CacheScope scope(&cache_);
-        BMX_HIP(hipMemsetAsync(flags_.reserve(F_WORDS), 0, F_WORDS * sizeof(int32_t), stream_));
+        BMX_HIP(hipMemsetAsync(flags_.reserve(CSC_F_WORDS), 0, CSC_F_WORDS * sizeof(int32_t), stream_));
         BMX_HIP(hipStreamSynchronize(stream_));
     }
     ~PcaSparse() { retire(); }
@@ -370,14 +328,9 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
     // a batch of n cells with nnz stored entries in all; its columns arrive in one or more blocks (add_block), in order
     void begin_batch(int64_t n, double weight, bool cos_norm, int64_t nnz) {
         check_cell_count(n);
-        if (nnz < 0) throw Error(BMX_ERR_ARG, "the batch's number of stored entries is negative");
-        begin(n, [&](SparsePcaBatch& b) {
-            b.nnz = nnz;
+        begin_csc(n, nnz, [&](SparsePcaBatch& b) {
             b.weight = weight;
             b.cos_norm = cos_norm;
-            b.indptr.reserve((size_t)n + 1);
-            b.indices.reserve((size_t)std::max<int64_t>(nnz, 1));
-            b.data.reserve((size_t)std::max<int64_t>(nnz, 1));
             b.cut.reserve((size_t)n);
             if (cos_norm) b.inv.reserve((size_t)n);
         });
@@ -386,30 +339,14 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
 
     // the next m cells of the batch begun last: indptr [m + 1] relative to the block, its nnz entries
     void add_block(int64_t m, const int64_t* indptr, const int32_t* indices, const double* data, int64_t nnz) {
-        CacheScope scope(&cache_);
-        BMX_HIP(hipSetDevice(device_));
-        SparsePcaBatch* bp = batches_.empty() ? nullptr : batches_.back().get();
-        check_block(bp, indptr, m, begin_entry_);
-        SparsePcaBatch& b = *bp;
-        norm_check_sparse_block(b.n, b.filled, m, indptr, indices, data, nnz);
-        if (nnz > b.nnz - b.nnz_filled) throw Error(BMX_ERR_ARG, "the block holds more entries than the batch announced");
-        if (b.filled + m == b.n && b.nnz_filled + nnz != b.nnz)
-            throw Error(BMX_ERR_ARG, "the batch has received fewer entries than it announced");
-        b.hindptr.resize((size_t)m + 1);
-        for (int64_t i = 0; i <= m; ++i) b.hindptr[(size_t)i] = b.nnz_filled + indptr[i];
-        upload_pageable(b.indptr.p + b.filled, b.hindptr.data(), (size_t)(m + 1) * sizeof(int64_t), stream_);
-        if (nnz > 0) {
-            upload_pageable(b.indices.p + b.nnz_filled, indices, (size_t)nnz * sizeof(int32_t), stream_);
-            upload_pageable(b.data.p + b.nnz_filled, data, (size_t)nnz * sizeof(double), stream_);
-        }
-        hipLaunchKernelGGL(sp_prepare_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, (const int64_t*)b.indptr.p,
-                           (const int32_t*)b.indices.p, (const double*)b.data.p, G_, Gp_, b.filled, m, b.cut.p,
-                           b.cos_norm ? b.inv.p : nullptr, flags_.p);
-        BMX_LAUNCH_CHECK();
-        b.filled += m;
-        b.nnz_filled += nnz;
-        fitted_ = false;
-        if (b.complete()) build_rows(b);
+        add_csc(m, indptr, indices, data, nnz, [&](SparsePcaBatch& b, int64_t c0) {
+            hipLaunchKernelGGL(sp_prepare_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_,
+                               (const int64_t*)b.indptr.p, (const int32_t*)b.indices.p, (const double*)b.data.p, G_, Gp_, c0, m,
+                               b.cut.p, b.cos_norm ? b.inv.p : nullptr, flags_.p);
+            BMX_LAUNCH_CHECK();
+            fitted_ = false;
+            if (b.complete()) build_rows(b);
+        });
     }
 
     // Pca::fit over the first n_rows_pca rows: centres [n_rows_pca], rotation [n_rows_pca x d] column-major, sdev [d]
@@ -424,12 +361,10 @@ class PcaSparse : ResidentBatches<SparsePcaBatch> {
         for (auto& bp : batches_) ncells += bp->n;
         const int L = SubspaceIteration::width_for(d, Gp_, ncells, max_applies);
         {
-            int32_t flags[F_WORDS] = {0, 0};
+            int32_t flags[CSC_F_WORDS] = {0, 0};
             BMX_HIP(hipMemcpyAsync(flags, flags_.p, sizeof(flags), hipMemcpyDeviceToHost, stream_));
             BMX_HIP(hipStreamSynchronize(stream_));
-            if (flags[F_ROW]) throw Error(BMX_ERR_ARG, "sparse counts: a row index is outside [0, number of genes)");
-            if (flags[F_ORDER])
-                throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
+            throw_if_bad_pattern(flags);
         }
         const int G = Gp_;
         // ---- grand centre of ALL rows: weighted mean of the batch means (R/multiBatchPCA.R:268-281)
@@ -666,7 +601,7 @@ void bmx_pca_sparse_destroy(bmx_pca_sparse_t* h) { delete h; }
 
 int32_t bmx_pca_sparse_check_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr, const int32_t* indices,
                                    const double* data, int64_t nnz) {
-    return bmx::guarded([&] { bmx::norm_check_sparse_block(n, filled, n_block, indptr, indices, data, nnz); });
+    return bmx::guarded([&] { bmx::check_csc_block(n, filled, n_block, indptr, indices, data, nnz); });
 }
 
 int32_t bmx_pca_sparse_begin_batch(bmx_pca_sparse_t* h, int64_t n, double weight, int32_t cos_norm, int64_t nnz) {

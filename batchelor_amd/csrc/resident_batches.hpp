@@ -1,7 +1,8 @@
-// What the handles that keep genes x cells batches in HBM (Pca, Cluster, Linear, Norm, NormSparse, Delta) have in common:
-// the guard their C entry points go through, the argument checks of a batch, the bookkeeping of a batch that arrives in
-// column blocks, the event-pair stage timer, the store that owns the cache, the copy stream, the batches and the stage
-// times, and the blocked pass that writes every cell.  The checks and the bookkeeping make no HIP call.
+// What the handles that keep genes x cells batches in HBM (Pca, PcaSparse, Cluster, Linear, Norm, NormSparse, Delta) have
+// in common: the guard their C entry points go through, the argument checks of a batch, the bookkeeping of a batch that
+// arrives in column blocks -- dense, or CSC (NormSparse, PcaSparse) --, the event-pair stage timer, the store that owns
+// the cache, the copy stream, the batches and the stage times, and the blocked pass that writes every cell (or every
+// stored entry).  The checks, the bookkeeping and the cutting of output blocks make no HIP call.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -64,6 +65,66 @@ inline void check_block(const BlockLedger* open, const void* x_block, int64_t m,
     if (!x_block) throw Error(BMX_ERR_ARG, "the block is missing");
 }
 
+// ---- the same for a batch kept as CSC: n cells with nnz stored entries in all
+struct CscLedger : BlockLedger {
+    int64_t nnz = 0, nnz_filled = 0;  // entries announced, received so far
+};
+// a block of m cells for a batch of n cells that holds `filled` so far: indptr [m + 1] relative to the block (starts at
+// 0, never decreases, ends at nnz); indices / data [nnz]
+inline void check_csc_block(int64_t n, int64_t filled, int64_t m, const int64_t* indptr, const int32_t* indices,
+                            const double* data, int64_t nnz) {
+    if (!indptr) throw Error(BMX_ERR_ARG, "the block's 'indptr' is missing");
+    if (nnz < 0) throw Error(BMX_ERR_ARG, "the block's number of stored entries is negative");
+    if (nnz > 0 && (!indices || !data)) throw Error(BMX_ERR_ARG, "the block's 'indices' or 'data' is missing");
+    if (n < 1 || filled < 0 || m < 1 || m > n || filled > n - m)
+        throw Error(BMX_ERR_ARG, "the block does not fit into the batch announced");
+    if (indptr[0] != 0) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not start at 0");
+    for (int64_t i = 0; i < m; ++i)
+        if (indptr[i + 1] < indptr[i]) throw Error(BMX_ERR_ARG, "the block's 'indptr' decreases");
+    if (indptr[m] != nnz) throw Error(BMX_ERR_ARG, "the block's 'indptr' does not end at its number of stored entries");
+}
+inline void check_csc_begin(int64_t nnz) {
+    if (nnz < 0) throw Error(BMX_ERR_ARG, "the batch's number of stored entries is negative");
+}
+// the next m cells of `open` bring nnz entries (the block has passed check_block and check_csc_block)
+inline void check_csc_entries(const CscLedger& open, int64_t m, int64_t nnz) {
+    if (nnz > open.nnz - open.nnz_filled) throw Error(BMX_ERR_ARG, "the block holds more entries than the batch announced");
+    if (open.filled + m == open.n && open.nnz_filled + nnz != open.nnz)
+        throw Error(BMX_ERR_ARG, "the batch has received fewer entries than it announced");
+}
+// what the kernels that read every stored entry report (csc_device.hpp: csc_entry_flags), a pair of adjacent device words:
+// a row index outside [0, G), rows of a column that do not ascend strictly
+enum { CSC_F_ROW = 0, CSC_F_ORDER = 1, CSC_F_WORDS = 2 };
+inline void throw_if_bad_pattern(const int32_t* pair) {
+    if (pair[CSC_F_ROW]) throw Error(BMX_ERR_ARG, "sparse counts: a row index is outside [0, number of genes)");
+    if (pair[CSC_F_ORDER])
+        throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
+}
+
+// ---- a block of a pass that writes every cell or stored entry: the cells [c0, c0 + mb) of batch bi, `count` elements
+// that go to outs[bi] + at
+struct OutBlock {
+    int bi;
+    int64_t c0;
+    int mb;
+    int64_t at, count;
+};
+// The blocks of a CSC batch of n cells, hindptr [n + 1] its absolute indptr: runs of whole cells in order, each up to the
+// last cell boundary within cap_elements stored entries and max_cells cells, one cell at the least; a run without entries
+// has nothing to write and is left out.  (bi is 0: the caller names the batch.)
+inline std::vector<OutBlock> plan_csc_output_blocks(const int64_t* hindptr, int64_t n, int64_t cap_elements,
+                                                    int64_t max_cells = (int64_t)1 << 30) {
+    std::vector<OutBlock> blocks;
+    for (int64_t c0 = 0; c0 < n;) {
+        const int64_t end = std::min(n, c0 + max_cells);
+        int64_t c1 = std::upper_bound(hindptr + c0, hindptr + end + 1, hindptr[c0] + cap_elements) - hindptr - 1;
+        c1 = std::max(c1, c0 + 1);
+        if (hindptr[c1] > hindptr[c0]) blocks.push_back({0, c0, (int)(c1 - c0), hindptr[c0], hindptr[c1] - hindptr[c0]});
+        c0 = c1;
+    }
+    return blocks;
+}
+
 // ---- device time by stage, from pairs of events
 class SpanTimer {
   public:
@@ -103,11 +164,17 @@ class SpanTimer {
 };
 
 // ---- the store.  Batch: a struct derived from ResidentBatch with the handle's own per-batch buffers -- or, for a handle
-// that keeps its cells in another form (the sparse counts of multiBatchNorm), one derived from BlockLedger alone that
-// says `dense_x = false`: begin() then reserves nothing itself and add() is not for it.
+// that keeps its cells as CSC, from CscBatch: begin_csc() / add_csc() are then what begin() / add() are for the others.
 struct ResidentBatch : BlockLedger {
     static constexpr bool dense_x = true;
     DevBuf<double> x;  // [n][G] (= genes x cells column-major)
+};
+struct CscBatch : CscLedger {
+    static constexpr bool dense_x = false;
+    DevBuf<int64_t> indptr;        // [n + 1] absolute positions
+    DevBuf<int32_t> indices;       // [nnz] 0-based rows
+    DevBuf<double> data;           // [nnz]
+    std::vector<int64_t> hindptr;  // indptr on the host: a pass over the stored entries cuts its blocks by it
 };
 
 template <class Batch>
@@ -173,6 +240,39 @@ class ResidentBatches {
         b->filled += m;
         queued(*b, p);
     }
+    // begin() for a CSC batch with nnz stored entries in all: the three arrays are reserved before fill(batch) runs
+    template <class F>
+    void begin_csc(int64_t n, int64_t nnz, F&& fill) {
+        check_csc_begin(nnz);
+        begin(n, [&](Batch& b) {
+            b.nnz = nnz;
+            b.indptr.reserve((size_t)n + 1);
+            b.indices.reserve((size_t)std::max<int64_t>(nnz, 1));
+            b.data.reserve((size_t)std::max<int64_t>(nnz, 1));
+            b.hindptr.assign((size_t)n + 1, 0);
+            fill(b);
+        });
+    }
+    // add() for a CSC batch: indptr [m + 1] relative to the block, its nnz entries (pageable).  indptr goes up rebased
+    // to absolute positions; queued(batch, first cell of the block) runs with filled / nnz_filled already advanced.
+    template <class F>
+    void add_csc(int64_t m, const int64_t* indptr, const int32_t* indices, const double* data, int64_t nnz, F&& queued) {
+        CacheScope scope(&cache_);
+        BMX_HIP(hipSetDevice(device_));
+        Batch* bp = batches_.empty() ? nullptr : batches_.back().get();
+        check_block(bp, indptr, m, begin_entry_);
+        Batch& b = *bp;
+        check_csc_block(b.n, b.filled, m, indptr, indices, data, nnz);
+        check_csc_entries(b, m, nnz);
+        int64_t* habs = b.hindptr.data() + b.filled;
+        for (int64_t i = 0; i <= m; ++i) habs[i] = b.nnz_filled + indptr[i];
+        upload_pageable(b.indptr.p + b.filled, habs, (size_t)(m + 1) * sizeof(int64_t), stream_);
+        upload_pageable(b.indices.p + b.nnz_filled, indices, (size_t)nnz * sizeof(int32_t), stream_);
+        upload_pageable(b.data.p + b.nnz_filled, data, (size_t)nnz * sizeof(double), stream_);
+        b.filled += m;
+        b.nnz_filled += nnz;
+        queued(b, b.filled - m);
+    }
 
     DevBlockCache cache_;  // first: see retire()
     int device_, G_;
@@ -183,29 +283,21 @@ class ResidentBatches {
     double ms_[5] = {0, 0, 0, 0, 0};  // what stage_ms reports (Pca reports none and leaves both alone)
 };
 
-// ---- a pass that writes every cell of every batch (Linear, Norm), in blocks of at most `per` cells through the two
-// device buffers of `buf`: launch(bi, batch, first cell, cells, device out) queues the kernel of a block on `kstream`;
-// the block then goes to outs[bi] through the download ring on `copy` while the next block's kernel runs into the other
-// buffer.  The kernels' event time goes to the timer's `stage`.  Both streams are idle when this returns.
-template <class Batch, class F>
-void blocked_output(const std::vector<std::unique_ptr<Batch>>& batches, int G, int64_t per, hipStream_t kstream,
-                    hipStream_t copy, SpanTimer& timer, int stage, DevBuf<double> (&buf)[2], double* const* outs,
-                    F&& launch) {
-    struct Blk {
-        int bi;
-        int64_t c0;
-        int mb;
-    };
-    std::vector<Blk> blocks;
-    for (size_t bi = 0; bi < batches.size(); ++bi)
-        for (int64_t c0 = 0; c0 < batches[bi]->n; c0 += per)
-            blocks.push_back({(int)bi, c0, (int)std::min(per, batches[bi]->n - c0)});
-    double* dev[2] = {buf[0].reserve((size_t)per * G), buf[1].reserve((size_t)per * G)};
+// ---- a pass that writes the blocks of a list (none: nothing happens) through the two device buffers of `buf`, sized
+// by the largest block: launch(block, device out) queues the kernel of a block on `kstream`; the block then goes to
+// outs[bi] + at through the download ring on `copy` while the next block's kernel runs into the other buffer.  The
+// kernels' event time goes to the timer's `stage`.  Both streams are idle when this returns.
+template <class F>
+void run_output_blocks(const std::vector<OutBlock>& blocks, hipStream_t kstream, hipStream_t copy, SpanTimer& timer,
+                       int stage, DevBuf<double> (&buf)[2], double* const* outs, F&& launch) {
+    if (blocks.empty()) return;
+    int64_t largest = 1;
+    for (const OutBlock& k : blocks) largest = std::max(largest, k.count);
+    double* dev[2] = {buf[0].reserve((size_t)largest), buf[1].reserve((size_t)largest)};
     std::vector<int> done(blocks.size(), -1);
     auto queue = [&](size_t i) {
-        const Blk& k = blocks[i];
         const int ea = timer.mark(kstream);
-        launch(k.bi, *batches[(size_t)k.bi], k.c0, k.mb, dev[i & 1]);
+        launch(blocks[i], dev[i & 1]);
         BMX_LAUNCH_CHECK();
         done[i] = timer.mark(kstream);
         timer.span(stage, ea, done[i]);
@@ -213,12 +305,29 @@ void blocked_output(const std::vector<std::unique_ptr<Batch>>& batches, int G, i
     queue(0);
     for (size_t i = 0; i < blocks.size(); ++i) {
         if (i + 1 < blocks.size()) queue(i + 1);  // (its buffer was emptied by the download of block i - 1)
-        const Blk& k = blocks[i];
+        const OutBlock& k = blocks[i];
         BMX_HIP(hipStreamWaitEvent(copy, timer.event(done[i]), 0));
-        download_pageable(outs[k.bi] + k.c0 * G, dev[i & 1], (size_t)k.mb * G * sizeof(double), copy);
+        download_pageable(outs[k.bi] + k.at, dev[i & 1], (size_t)k.count * sizeof(double), copy);
     }
     BMX_HIP(hipStreamSynchronize(kstream));
     BMX_HIP(hipStreamSynchronize(copy));
+}
+
+// every cell of every dense batch (Linear, Norm), in blocks of at most `per` cells: launch(bi, batch, first cell, cells,
+// device out)
+template <class Batch, class F>
+void blocked_output(const std::vector<std::unique_ptr<Batch>>& batches, int G, int64_t per, hipStream_t kstream,
+                    hipStream_t copy, SpanTimer& timer, int stage, DevBuf<double> (&buf)[2], double* const* outs,
+                    F&& launch) {
+    std::vector<OutBlock> blocks;
+    for (size_t bi = 0; bi < batches.size(); ++bi)
+        for (int64_t c0 = 0; c0 < batches[bi]->n; c0 += per) {
+            const int64_t mb = std::min(per, batches[bi]->n - c0);
+            blocks.push_back({(int)bi, c0, (int)mb, c0 * G, mb * G});
+        }
+    run_output_blocks(blocks, kstream, copy, timer, stage, buf, outs, [&](const OutBlock& k, double* out) {
+        launch(k.bi, *batches[(size_t)k.bi], k.c0, k.mb, out);
+    });
 }
 
 }  // namespace bmx

@@ -75,6 +75,11 @@ def csc_blocks(c, width):
         yield b - a, c.indptr[a:b + 1].astype(np.int64) - k0, c.indices[k0:k1], c.data[k0:k1]
 
 
+def csc_block_width(c, block_bytes):
+    """Cells per column block of `c` that hold about block_bytes of stored entries (12 bytes each) at its mean density."""
+    return max(1, int(block_bytes) * int(c.shape[1]) // max(1, 12 * int(c.nnz)))
+
+
 def check_unique_names(names):
     if names is not None and len(set(names)) != len(names):
         raise ValueError("names of batches should be unique")  # R/fastMNN.R:422

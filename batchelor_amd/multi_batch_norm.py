@@ -34,7 +34,9 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import canonical_csc, check_same_dim, csc_blocks, divide_into_batches, subset_index, unpack_batches
+from .inputs import (all_sparse, canonical_csc, check_same_dim, check_same_rows, csc_block_width, divide_into_batches,
+                     subset_index, unpack_batches)
+from .inputs import csc_blocks  # noqa: F401  (the helper's old import path)
 from .linear_correct import _as_matrices, _check_batch, _check_names
 
 BLOCK_BYTES = 1 << 28   # a batch above this size goes to the device in column blocks of about this many bytes
@@ -109,17 +111,11 @@ class _SparseNormHandle(ResidentHandle):
     def add_batch(self, c, size_factors=None, block_bytes=None):
         """c: canonical CSC, genes x cells.  The blocks are whole chunks of cells, as many as hold about block_bytes of
         stored entries (12 bytes each) at the batch's mean density."""
-        bb = BLOCK_BYTES if block_bytes is None else block_bytes
-        n, nnz = int(c.shape[1]), int(c.nnz)
-        per = max(1, int(bb) * n // max(1, 12 * nnz))
+        per = csc_block_width(c, BLOCK_BYTES if block_bytes is None else block_bytes)
         per = max(CHUNK, per // CHUNK * CHUNK)
         sf = None if size_factors is None else np.ascontiguousarray(size_factors, dtype=np.float64)
-        self._call("begin_batch", ctypes.c_int64(n), None if sf is None else _lib.f64p(sf), ctypes.c_int64(nnz))
-        for m, indptr, indices, data in csc_blocks(c, per):
-            self._call("add_block", ctypes.c_int64(m), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
-                       _lib.f64p(data), ctypes.c_int64(data.size))
-        self.ncells.append(n)
-        self.nnz.append(nnz)
+        self._upload_csc(c, per, None if sf is None else _lib.f64p(sf))
+        self.nnz.append(int(c.nnz))
 
     def run(self, min_mean, log, pseudo_count):
         N, B = sum(self.ncells), len(self.ncells)
@@ -133,25 +129,6 @@ class _SparseNormHandle(ResidentHandle):
                    ctypes.c_double(float(pseudo_count)), ptrs, _lib.f64p(sf), _lib.f64p(ave), _lib.f64p(ratios),
                    ctypes.byref(smallest), ctypes.byref(zero))
         return outs, float(zero.value), sf, ave, ratios, int(smallest.value)
-
-
-def _sparse_batches(batches):
-    """The batches as CSC if they are scipy.sparse objects (None if none is); a call that mixes them with anything else
-    is refused."""
-    raw = unpack_batches(batches)
-    flags = [sp.issparse(b) for b in raw]
-    if not any(flags):
-        return None
-    if not all(flags):
-        raise TypeError("multiBatchNorm takes batches that are all sparse or all dense, not a mixture")
-    return [b.tocsc() for b in raw]
-
-
-def _same_rows(mats):
-    for m in mats:
-        if m.shape[0] != mats[0].shape[0]:
-            raise ValueError("number of rows is not the same across batches")
-    return mats[0].shape[0]
 
 
 def _check_size_factors(sf, n):
@@ -172,13 +149,11 @@ def multiBatchNorm(*batches, batch=None, size_factors=None, norm_args=None, min_
     place of sizeFactors(); None: library sizes over `subset_row`.  `norm_args`: `log` (default True) and `pseudo_count`
     (default 1).  `names` plays the role of the argument names of `...`.  With one object and preserve_single the result
     is one matrix and one vector in the caller's cell order, otherwise lists with one entry per batch."""
-    mats = _sparse_batches(batches)
-    sparse = mats is not None
-    if not sparse:
-        mats = _as_matrices(batches, "multiBatchNorm")
+    sparse = all_sparse(unpack_batches(batches), "multiBatchNorm")
+    mats = [b.tocsc() for b in unpack_batches(batches)] if sparse else _as_matrices(batches, "multiBatchNorm")
     if len(mats) == 0:
         raise ValueError("at least one matrix of counts must be supplied")  # R/multiBatchNorm.R:118
-    G = _same_rows(mats) if sparse else check_same_dim(mats, byrow=False)
+    G = check_same_rows(mats) if sparse else check_same_dim(mats, byrow=False)
     norm_args = dict(norm_args or {})
     for key in norm_args:
         if key not in NORM_ARGS:

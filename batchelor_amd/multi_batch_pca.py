@@ -17,7 +17,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import all_sparse, canonical_csc, check_same_dim, check_same_rows, csc_blocks, subset_index, unpack_batches
+from .inputs import all_sparse, canonical_csc, check_same_dim, check_same_rows, csc_block_width, subset_index, unpack_batches
 
 # Sparse batches that the device path cannot take (multiBatchPCA's docstring) are made dense for the host path; beyond
 # this many bytes of dense float64 over all batches the call is refused instead.
@@ -241,18 +241,12 @@ class DeviceSparsePCA(_ResidentPCA):
         as hold about BLOCK_BYTES of stored entries, 12 bytes each); the results do not depend on it."""
         if c.ndim != 2 or c.shape[0] != self.G:
             raise ValueError("number of rows is not the same across batches")
-        n, nnz = int(c.shape[1]), int(c.nnz)
-        per = max(1, self.BLOCK_BYTES * n // max(1, 12 * nnz)) if block_cells is None else max(1, int(block_cells))
-        self._call("begin_batch", ctypes.c_int64(n), ctypes.c_double(float(weight)), 1 if cos_norm else 0,
-                   ctypes.c_int64(nnz))
-        self.ncells.append(n)
-        for m, indptr, indices, data in csc_blocks(c, per):
-            self.add_block(m, indptr, indices, data)
+        per = csc_block_width(c, self.BLOCK_BYTES) if block_cells is None else max(1, int(block_cells))
+        self._upload_csc(c, per, ctypes.c_double(float(weight)), 1 if cos_norm else 0)
 
     def add_block(self, m, indptr, indices, data):
         """The next m cells of the batch begun last: indptr [m + 1] int64 relative to the block, int32 rows, float64."""
-        self._call("add_block", ctypes.c_int64(int(m)), indptr.ctypes.data_as(_lib.c_i64p), _lib.i32p(indices),
-                   _lib.f64p(data), ctypes.c_int64(int(data.size)))
+        self._add_csc_block(m, indptr, indices, data)
 
     def genes(self):
         """(centers [n_rows - n_rows_pca], rotation [n_rows - n_rows_pca x d]) of the rows outside the subset."""

@@ -1,5 +1,6 @@
-"""The argument checks and the block bookkeeping of csrc/resident_batches.hpp on the host, under AddressSanitizer and
-UndefinedBehaviorSanitizer: tests/host/resident_batches_host.cpp is a stand-alone program that makes no HIP call."""
+"""The argument checks, the block bookkeeping (dense and CSC) and the cutting of output blocks of
+csrc/resident_batches.hpp on the host, under AddressSanitizer and UndefinedBehaviorSanitizer:
+tests/host/resident_batches_host.cpp is a stand-alone program that makes no HIP call."""
 import os
 import shutil
 import subprocess
@@ -17,6 +18,7 @@ def test_host_program_under_sanitizers(tmp_path):
                     "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
                     "-I" + os.path.join(ROOT, "batchelor_amd", "csrc"),
                     os.path.join(ROOT, "tests", "host", "resident_batches_host.cpp"), "-o", exe], check=True)
-    run = subprocess.run([exe], capture_output=True, text=True)
+    run = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "csc_output_blocks_parent.json")], capture_output=True,
+                         text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "host checks ok" in run.stdout

@@ -211,6 +211,23 @@ def test_determinism(monkeypatch):
     assert_same_result(run("g7", True), dense_result("g7", True))
 
 
+def test_an_upload_block_without_entries_gives_the_bits_of_a_whole_upload(monkeypatch):
+    """7 genes x 600 cells whose cells 256-511 hold no entry (size factors given): BLOCK_BYTES = 1 uploads the cells in
+    blocks of 256, 256 and 88, the middle one without a stored entry; the default uploads them in one block."""
+    A, B, C = (np.array(x) for x in dense("g7"))
+    C[:, 256:512] = 0
+    X = [sp.csc_matrix(x) for x in (A, B, C)]
+    assert X[2].shape == (7, 600) and X[2].indptr[256] == X[2].indptr[512] and X[2].indptr[256] > 0 and X[2].nnz > X[2].indptr[512]
+    sfs = list(given_factors("g7"))
+    whole = bx.multiBatchNorm(*X, size_factors=sfs)
+    monkeypatch.setattr(mbn, "BLOCK_BYTES", 1)
+    blocked = bx.multiBatchNorm(*X, size_factors=sfs)
+    assert_same_result(blocked, whole)
+    for a, b in zip(blocked.logcounts, whole.logcounts):
+        assert sp.issparse(a) and same_bits(a.data, b.data) and np.array_equal(a.indptr, b.indptr)
+    assert_same_result(whole, bx.multiBatchNorm(A, B, C, size_factors=sfs))
+
+
 def test_structure():
     A, B, C = (np.array(x) for x in dense("g7"))
     # cells without a stored entry in the middle of a batch and at its end (size factors given)

@@ -191,6 +191,39 @@ def test_misuse_of_the_handle():
         bx.multiBatchPCA(B[0], B[1][:60], d=5)
 
 
+def _with_an_empty_block(n_rows, n_pca, block_cells, more_cells):
+    """A batch of 10 cells whose cells 4-7 hold no entry, uploaded whole or in blocks of block_cells, then (more_cells > 0)
+    a second batch; fit with a fixed count, the projections and the rows outside the PCA's."""
+    rng = np.random.default_rng(4)
+    a = rng.poisson(1.0, (n_rows, 10)).astype(np.float64)
+    a[:, 4:8] = 0
+    mats = [sp.csc_matrix(a)] + ([sp.csc_matrix(rng.poisson(0.7, (n_rows, more_cells)).astype(np.float64))] if more_cells else [])
+    assert np.array_equal(np.diff(mats[0].indptr)[4:8], [0, 0, 0, 0]) and np.all(np.diff(mats[0].indptr)[:4] > 0)
+    pca = bx.DeviceSparsePCA(n_rows, n_pca)
+    try:
+        pca.add_batch(canonical_csc(mats[0])[0], block_cells=block_cells)
+        for m in mats[1:]:
+            pca.add_batch(canonical_csc(m)[0])
+        out = pca.fit(d=5, iters=2)
+        return [out["centers"], out["rotation"], out["d"], *pca.genes()] + [pca.project(b) for b in range(len(mats))]
+    finally:
+        pca.close()
+
+
+def test_an_upload_block_without_entries_gives_the_bits_of_a_whole_upload():
+    """block_cells = 4 cuts the 10 cells into 4 + 4 (no stored entry) + 2.  At 70 rows of which 40 are the PCA's, and 10
+    cells, both uploads are taken and the fit refuses either alike: the iteration's block needs 64 PCA rows and more than
+    64 cells.  The smallest shape it takes -- 94 rows of which 64 are the PCA's, a second batch of 60 cells -- gives the
+    same bits from either upload."""
+    for block_cells in (None, 4):
+        with pytest.raises(_lib.BatchelorMI355XError, match="rank below the subspace width"):
+            _with_an_empty_block(70, 40, block_cells, 0)
+    whole, blocked = (_with_an_empty_block(94, 64, block_cells, 60) for block_cells in (None, 4))
+    same = [bool(np.array_equal(p, q)) for p, q in zip(whole, blocked)]
+    print(f"centers, rotation, d, centers and rotation of the other rows, projections: bitwise equal {same}")
+    assert len(whole) == 7 and all(np.all(np.isfinite(p)) for p in whole) and all(same), same
+
+
 # ------------------------------------------------------------------------------------- fastMNN end to end
 def _aligned_rel(got, want, rot_got, rot_want):
     """max |got - want| / max |want| after giving every column of `got` the sign of its rotation column in `want`."""
