@@ -16,3 +16,6 @@ from .cluster_mnn import ClusterMnnResult, clusterMNN  # noqa: F401
 from .linear_correct import LinearCorrectResult, regressBatches, rescaleBatches  # noqa: F401
 from .delta_variance import MnnDeltaVarianceResult, mnnDeltaVariance  # noqa: F401
 from .multi_batch_norm import MultiBatchNormResult, multiBatchNorm  # noqa: F401
+from .model_gene_var import GeneVarTable, combineVar, getTopHVGs, modelGeneVar  # noqa: F401
+from .batch_correct import (ClassicMnnParam, FastMnnParam, NoCorrectParam, NoCorrectResult, QuickCorrectResult,  # noqa: F401
+                            RegressParam, RescaleParam, batchCorrect, intersectRows, noCorrect, quickCorrect)

@@ -1,5 +1,5 @@
 // Device helpers of the kernels that read a batch kept as CSC (indptr absolute, rows ascending within a column): NormSparse
-// (multi_batch_norm.hip) and PcaSparse (pca_sparse.hip).  The store and the host's checks are in resident_batches.hpp.
+// (multi_batch_norm.hip), PcaSparse (pca_sparse.hip) and GeneVarSparse (gene_var.hip, over one block at a time).  The store and the host's checks are in resident_batches.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

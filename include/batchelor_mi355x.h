@@ -118,7 +118,8 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * phase), "asv_ticks_literal" / "asv_ticks_chains" (the re-run cells' selection + re-evaluation + sort, their chains and walks),
  * "asv_literal_addends" (addends the re-run cells kept), "asv_chain_tiles" (tiles with a re-run cell).  Waits for the device.
  * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
- * owns, pairs of a step it walks). */
+ * owns, pairs of a step it walks), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
+ * genes a workgroup of the sparse one owns). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
  * call went -- 0 the histogram quantile (a well-conditioned cell), 1 re-run in the reference's order of operations, 2
@@ -674,6 +675,62 @@ int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_gene
  * time of out[1] the cell norms, out[2] the two pair passes (the gather), out[3] the pair preparation and the reductions
  * over chunks; out[4] = host wall time of bmx_delta_run. */
 int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-batch, per-gene mean and variance: what scran::modelGeneVar() takes from its input before any trend, and what
+ * quickCorrect() (R/quickCorrect.R:66-120) ranks its genes by.  For every batch b and gene g over the batch's n_b cells:
+ *   mean[g, b]  = (1 / n_b) * sum over c of x[g, c]
+ *   total[g, b] = (1 / (n_b - 1)) * sum over c of (x[g, c] - mean[g, b])^2      (NaN for a batch of one cell)
+ * Values are FP64, genes x cells column-major, and must be finite.  A batch STREAMS through two block buffers: it is
+ * announced with its cells and sent in column blocks, each reduced behind the copy of the next, so a batch need not
+ * fit in HBM.  The cells of a batch are cut into chunks of 256 at fixed positions WITHIN THE BATCH (bmx_dev_get
+ * "genevar_chunk"); a block that does not end its batch must hold whole chunks.  Per chunk and gene the kernels take
+ * the sum in cell order, the chunk mean, then the sum of squared deviations from it in cell order (two sweeps, never
+ * E[x^2] - E[x]^2); the chunks are merged in ascending order by the pairwise update of Chan, Golub and LeVeque,
+ *   delta = mB - mA;  n = nA + nB;  m = mA + (delta * nB) / n;  M2 = (M2A + M2B) + (((delta * delta) * nA) * nB) / n.
+ * No floating-point atomics, contraction off: the results are the same bits on every run, for every block width, and
+ * whichever batches were sent before.  Arguments are checked before any device work; what only the data can show is
+ * raised as device flags and reported by bmx_genevar_run with BMX_ERR_ARG: "values should be finite".
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_genevar bmx_genevar_t;
+int32_t bmx_genevar_create(int32_t device, int32_t n_genes, bmx_genevar_t** out);
+void bmx_genevar_destroy(bmx_genevar_t* h);
+/* The argument checks of bmx_genevar_create / _add_block / bmx_genevar_sparse_add_block on their own: they need no
+ * device.  A block of n_block cells for a batch of n cells of which `filled` have arrived; for the sparse block see
+ * bmx_genevar_sparse_add_block. */
+int32_t bmx_genevar_check_create(int32_t n_genes);
+int32_t bmx_genevar_check_block(int64_t n, int64_t filled, int64_t n_block);
+int32_t bmx_genevar_check_sparse_block(int64_t n, int64_t filled, int64_t n_block, const int64_t* indptr,
+                                       const int32_t* indices, const double* data, int64_t nnz);
+/* A batch of n cells (1 <= n < 2^31).  Its cells follow in one or more blocks (x_block: n_genes x n_block column-major,
+ * host, pageable is fine), in order; n_block is a multiple of 256 unless the block ends the batch. */
+int32_t bmx_genevar_begin_batch(bmx_genevar_t* h, int64_t n);
+int32_t bmx_genevar_add_block(bmx_genevar_t* h, const double* x_block, int64_t n_block);
+/* mean_out, total_out: n_genes x n_batches column-major (caller-allocated), batches in upload order. */
+int32_t bmx_genevar_run(bmx_genevar_t* h, double* mean_out, double* total_out);
+/* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), out[1] =
+ * HIP-event time of the kernels, out[2] = host wall time of bmx_genevar_run. */
+int32_t bmx_genevar_stage_ms(const bmx_genevar_t* h, double* out3);
+
+/* The same over batches given as canonical CSC: per block indptr [n_block + 1] (int64, relative to the block: starts at
+ * 0, never decreases, ends at nnz), 0-based int32 row indices strictly ascending within a column and FP64 values
+ * (explicit zeros are values like any other).  Only two blocks are on the device at a time.  A gene's sum takes the
+ * stored entries in cell order -- the dense handle's sum with its terms of +0 left out, so `mean` equals the dense
+ * handle's bit for bit but for the sign of a zero; the implicit zeros of a chunk enter M2 as (cells - stored) * m * m.
+ * What only the device sees of the pattern is flagged and reported by bmx_genevar_sparse_run: "a row index is outside
+ * [0, number of genes)", "the row indices of a column should be strictly ascending".  Such entries are skipped by every
+ * kernel, never used as an address.  The genes are tiled by bmx_dev_get "genevar_gene_tile". */
+typedef struct bmx_genevar_sparse bmx_genevar_sparse_t;
+int32_t bmx_genevar_sparse_create(int32_t device, int32_t n_genes, bmx_genevar_sparse_t** out);
+void bmx_genevar_sparse_destroy(bmx_genevar_sparse_t* h);
+/* A batch of n cells with nnz stored entries in all; its blocks follow in order (n_block as for bmx_genevar_add_block;
+ * indices and data may be NULL only when the block's nnz is 0). */
+int32_t bmx_genevar_sparse_begin_batch(bmx_genevar_sparse_t* h, int64_t n, int64_t nnz);
+int32_t bmx_genevar_sparse_add_block(bmx_genevar_sparse_t* h, int64_t n_block, const int64_t* indptr,
+                                     const int32_t* indices, const double* data, int64_t nnz);
+/* As bmx_genevar_run / bmx_genevar_stage_ms. */
+int32_t bmx_genevar_sparse_run(bmx_genevar_sparse_t* h, double* mean_out, double* total_out);
+int32_t bmx_genevar_sparse_stage_ms(const bmx_genevar_sparse_t* h, double* out3);
 
 #ifdef __cplusplus
 }
