@@ -156,6 +156,9 @@ void transpose_rm_to_cm(hipStream_t stream, const double* rm, int n, int d, doub
 
 // ---- upstream of the engine (prepca.hip): cosineNorm + PCA projection, x is genes x cells column-major ----------
 void cosine_l2_device(hipStream_t stream, const double* x, int G, int n, double* l2);
+// out[c] = l2 of cell c over the 0-based genes listed (genes0 null: over all G), c in [0, n); inverse: 1 / pmax(1e-8, l2)
+void cell_l2_device(hipStream_t stream, const double* x, int G, int64_t n, const int32_t* genes0, int n_genes, bool inverse,
+                    double* out);
 void apply_cosine_norm_device(hipStream_t stream, const double* x, int G, int n, const double* l2, double* out);
 // out [n x d] column-major = crossprod(x / pmax(1e-8, l2) - centers, u)   (u [G x d] column-major); cos_norm = 0 skips
 // the division.  One pass over x.  l2_out (nullable) receives the column norms; cu_scratch: d doubles.

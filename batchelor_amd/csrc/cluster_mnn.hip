@@ -2,9 +2,8 @@
 //   a. .compute_centroids (:231-244): the mean of every cluster's restricted cells, of cosineNorm(x) when asked for.
 //      The host sorts the restricted cells by cluster (a counting sort, ascending cell within a cluster) and cuts every
 //      cluster's list into chunks of CCH cells.  centroid_partial_kernel: one workgroup per (chunk, tile of 256 genes),
-//      lanes along the genes so that every cell's column is read coalesced, the chunk's cells added in list order;
-//      centroid_reduce_kernel adds a cluster's chunk sums in ascending chunk order and divides by the count.  No
-//      floating-point atomics anywhere: the result is the same bit for bit from run to run.  x is read once.
+//      lanes along the genes so that every cell's column is read coalesced; centroid_reduce_kernel adds a cluster's
+//      chunk sums and divides by the count.  The orders of both are those of ordered_sums.hpp.  x is read once.
 //   b. .propagate_to_cells (:262-282) + .smooth_gaussian_from_centroids (:286-312) for one batch:
 //      cur = crossprod(cosineNorm(x)[subset,], rotation) - centers %*% rotation through cosnorm_project_device (the
 //      rotation scattered to all genes, zero outside the subset, so that x is again read once);
@@ -23,6 +22,7 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -32,23 +32,6 @@ constexpr int CCH = 256;  // cells per chunk of the centroid pass
 constexpr int JT = 16;    // centroids (nearest_kernel) / columns (smooth_kernel) per LDS tile
 constexpr int DMAX = 256;  // columns cosnorm_project_device and the merge engine take
 constexpr int MSEL_T = 1024;
-
-// l2 over the subset's genes only (cosineNorm(x, mode="l2norm", subset.row=), R/clusterMNN.R:140): one wave per cell
-__global__ __launch_bounds__(256) void colnorm_subset_kernel(const double* __restrict__ x, int G, int n,
-                                                             const int32_t* __restrict__ sub0, int ns,
-                                                             double* __restrict__ l2) {
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (c >= n) return;
-    const double* col = x + (int64_t)c * G;
-    double s = 0.0;
-    for (int i = lane; i < ns; i += 64) {
-        const double v = col[sub0[i]];
-        s += v * v;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) l2[c] = sqrt(s);
-}
 
 // part[chunk][g] = sum over the chunk's cells, in list order, of x[g, cell] (/ pmax(1e-8, l2[cell]))
 __global__ __launch_bounds__(256) void centroid_partial_kernel(const double* __restrict__ x, int G,
@@ -60,33 +43,17 @@ __global__ __launch_bounds__(256) void centroid_partial_kernel(const double* __r
     if (g >= G) return;
     const int ch = blockIdx.x;
     const int b = chunk_begin[ch], e = chunk_begin[ch + 1];
+    struct Cell {
+        double v, L;
+    };
     double s = 0.0;
-    int i = b;
-    for (; i + 4 <= e; i += 4) {  // four loads in flight, added in list order
-        const int c0 = order[i], c1 = order[i + 1], c2 = order[i + 2], c3 = order[i + 3];
-        double v0 = x[(int64_t)c0 * G + g], v1 = x[(int64_t)c1 * G + g];
-        double v2 = x[(int64_t)c2 * G + g], v3 = x[(int64_t)c3 * G + g];
-        if (l2) {
-            const double L0 = l2[c0], L1 = l2[c1], L2 = l2[c2], L3 = l2[c3];
-            v0 = v0 / (L0 < 1e-8 ? 1e-8 : L0);
-            v1 = v1 / (L1 < 1e-8 ? 1e-8 : L1);
-            v2 = v2 / (L2 < 1e-8 ? 1e-8 : L2);
-            v3 = v3 / (L3 < 1e-8 ? 1e-8 : L3);
-        }
-        s += v0;
-        s += v1;
-        s += v2;
-        s += v3;
-    }
-    for (; i < e; ++i) {
-        const int c = order[i];
-        double v = x[(int64_t)c * G + g];
-        if (l2) {
-            const double L = l2[c];
-            v = v / (L < 1e-8 ? 1e-8 : L);
-        }
-        s += v;
-    }
+    ordered_walk4(
+        b, e,
+        [&](int i) {
+            const int c = order[i];
+            return Cell{x[(int64_t)c * G + g], l2 ? l2[c] : 1.0};
+        },
+        [&](const Cell& q) { s += l2 ? q.v / cos_clamp(q.L) : q.v; });
     part[(int64_t)ch * G + g] = s;
 }
 
@@ -99,9 +66,8 @@ __global__ __launch_bounds__(256) void centroid_reduce_kernel(const double* __re
     const int cl = blockIdx.y;
     if (g >= G || cl >= C) return;
     const int f = cluster_chunk0[cl], l = cluster_chunk0[cl + 1];
-    double s = part[(int64_t)f * G + g];
-    for (int ch = f + 1; ch < l; ++ch) s += part[(int64_t)ch * G + g];
-    out[(int64_t)cl * G + g] = s / (double)count[cl];
+    const auto at = [&](int ch) { return part[(int64_t)ch * G + g]; };
+    out[(int64_t)cl * G + g] = fold_ascending(at(f), f + 1, l, at) / (double)count[cl];
 }
 
 // cur[c, t] = acc[c, t] / pmax(1e-8, l2[c]) - cu[t], in place ([n x d] column-major)
@@ -112,10 +78,7 @@ __global__ void finish_projection_kernel(double* __restrict__ cur, int n, int d,
     const int t = (int)(e / n);
     const int c = (int)(e - (int64_t)t * n);
     double v = cur[e];
-    if (l2) {
-        const double L = l2[c];
-        v = v / (L < 1e-8 ? 1e-8 : L);
-    }
+    if (l2) v = v / cos_clamp(l2[c]);
     cur[e] = v - cu[t];
 }
 
@@ -391,13 +354,7 @@ class Cluster : ResidentBatches<ClusterBatch> {
         add(x_block, m, [&](ClusterBatch& b, double* p) {
             if (b.cos_norm) {
                 double* l2 = b.l2.p + (b.filled - m);
-                if (sub0_host_.empty()) {
-                    cosine_l2_device(stream_, p, G_, (int)m, l2);
-                } else {
-                    hipLaunchKernelGGL(colnorm_subset_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_,
-                                       (const double*)p, G_, (int)m, (const int32_t*)sub0_.p, (int)sub0_host_.size(), l2);
-                    BMX_LAUNCH_CHECK();
-                }
+                cell_l2_device(stream_, p, G_, m, sub0_host_.empty() ? nullptr : sub0_.p, (int)sub0_host_.size(), false, l2);
             }
             if (b.complete()) BMX_HIP(hipStreamSynchronize(stream_));
         });

@@ -6,12 +6,12 @@
 //   prep    one thread per pair: the two columns' addresses (a search of the batches' offset table) and scales.
 //   pass 1  a workgroup owns DELTA_GENE_TILE genes (lanes along the genes, 16-byte loads where G is even) and one chunk
 //           of DELTA_PAIR_CHUNK pairs of one step: the sums of s_l x_left and of s_r x_right in pair order.  Four pairs'
-//           loads are in flight; a left cell that repeats stays in registers.  mean_reduce_kernel adds the chunk sums in
-//           ascending order: mean (:197) and the mean delta.
+//           loads are in flight; a left cell that repeats stays in registers.  mean_reduce_kernel adds the chunk sums:
+//           mean (:197) and the mean delta.
 //   pass 2  the same walk: sum of (delta - mean delta)^2 (rowVars' two passes, :196); total_reduce_kernel adds the chunks
-//           in ascending order and divides by P - 1 (NaN below two pairs).
-// The chunk edges are fixed positions of a step's pair list and every sum has one order: no floating-point atomics, the
-// same bits on every run.  All FP64 vector arithmetic, contraction off.
+//           and divides by P - 1 (NaN below two pairs).
+// The chunk edges are fixed positions of a step's pair list; the orders of the sums are those of ordered_sums.hpp.  All
+// FP64 vector arithmetic, contraction off.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -21,6 +21,7 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -40,23 +41,6 @@ struct ChunkRef {
     int32_t len, step;
 };
 
-// l2 over the listed genes only (cosineNorm(x, mode="l2norm", subset.row=), :122): one wave per cell
-__global__ __launch_bounds__(256) void colnorm_genes_kernel(const double* __restrict__ x, int G, int n,
-                                                            const int32_t* __restrict__ genes0, int ng,
-                                                            double* __restrict__ l2) {
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (c >= n) return;
-    const double* col = x + (int64_t)c * G;
-    double s = 0.0;
-    for (int i = lane; i < ng; i += 64) {
-        const double v = col[genes0[i]];
-        s += v * v;
-    }
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) l2[c] = sqrt(s);
-}
-
 // bmean[b] = mean of l2 over batch b's cells: 256 strided sums, then a tree in a fixed order
 __global__ __launch_bounds__(256) void l2_mean_kernel(const double* __restrict__ l2, const int64_t* __restrict__ off,
                                                       double* __restrict__ bmean) {
@@ -65,13 +49,8 @@ __global__ __launch_bounds__(256) void l2_mean_kernel(const double* __restrict__
     const int64_t c0 = off[b], n = off[b + 1] - c0;
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) s += l2[c0 + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bmean[b] = sh[0] / (double)n;
+    const double sum = block_tree_sum<256>(s, sh);
+    if (threadIdx.x == 0) bmean[b] = sum / (double)n;
 }
 
 // scale[c] = 1 / pmax(1e-8, l2[c] / ml2), ml2 = mean over the batches of bmean (:123-125, R/cosineNorm.R:80)
@@ -82,9 +61,7 @@ __global__ __launch_bounds__(256) void scale_kernel(const double* __restrict__ l
     double m = 0.0;
     for (int b = 0; b < B; ++b) m += bmean[b];
     m /= (double)B;
-    double d = l2[c] / m;
-    d = d < 1e-8 ? 1e-8 : d;
-    scale[c] = 1.0 / d;
+    scale[c] = 1.0 / cos_clamp(l2[c] / m);
 }
 
 // left / right: 1-based columns of the batches side by side; off [B + 1] the batches' first columns, base [B] their
@@ -237,14 +214,11 @@ __global__ __launch_bounds__(256) void mean_reduce_kernel(const double* __restri
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int s = blockIdx.y;
     if (g >= G) return;
-    double sl = 0.0, sr = 0.0;
-#pragma unroll 8
-    for (int ch = chunk0[s]; ch < chunk0[s + 1]; ++ch) {
-        sl += part_l[(int64_t)ch * G + g];
-        sr += part_r[(int64_t)ch * G + g];
-    }
+    const double2 lr = fold_ascending<8>(make_double2(0.0, 0.0), chunk0[s], chunk0[s + 1], [&](int ch) {
+        return make_double2(part_l[(int64_t)ch * G + g], part_r[(int64_t)ch * G + g]);
+    });
     const double P = (double)npairs[s];
-    const double ml = sl / P, mr = sr / P;  // (no pairs: NaN, as rowMeans of no columns)
+    const double ml = lr.x / P, mr = lr.y / P;  // (no pairs: NaN, as rowMeans of no columns)
     mean[(int64_t)s * G + g] = (ml + mr) / 2.0;
     mdelta[(int64_t)s * G + g] = ml - mr;
 }
@@ -256,9 +230,7 @@ __global__ __launch_bounds__(256) void total_reduce_kernel(const double* __restr
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int s = blockIdx.y;
     if (g >= G) return;
-    double v = 0.0;
-#pragma unroll 8
-    for (int ch = chunk0[s]; ch < chunk0[s + 1]; ++ch) v += part[(int64_t)ch * G + g];
+    const double v = fold_ascending<8>(0.0, chunk0[s], chunk0[s + 1], [&](int ch) { return part[(int64_t)ch * G + g]; });
     const int64_t P = npairs[s];
     total[(int64_t)s * G + g] = P >= 2 ? v / (double)(P - 1) : __longlong_as_double(0x7ff8000000000000ll);
 }
@@ -416,13 +388,7 @@ class Delta : ResidentBatches<DeltaBatch> {
             const int e0 = timer_.mark(stream_);
             for (int b = 0; b < B; ++b) {
                 const DeltaBatch& bt = *batches_[(size_t)b];
-                if (!d_genes) {
-                    cosine_l2_device(stream_, bt.x.p, G, (int)bt.n, l2 + off[(size_t)b]);
-                } else {
-                    hipLaunchKernelGGL(colnorm_genes_kernel, dim3((unsigned)cdiv(bt.n, 4)), dim3(256), 0, stream_,
-                                       (const double*)bt.x.p, G, (int)bt.n, d_genes, a.n_norm_genes, l2 + off[(size_t)b]);
-                    BMX_LAUNCH_CHECK();
-                }
+                cell_l2_device(stream_, bt.x.p, G, bt.n, d_genes, a.n_norm_genes, false, l2 + off[(size_t)b]);
             }
             hipLaunchKernelGGL(l2_mean_kernel, dim3((unsigned)B), dim3(256), 0, stream_, (const double*)l2,
                                (const int64_t*)d_off, bmean);

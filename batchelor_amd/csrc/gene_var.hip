@@ -5,8 +5,9 @@
 //   per block, on the kernel stream, once the block has landed:
 //     gv_dense_kernel      lanes along the genes (16-byte loads, two genes a lane, where G is even), the block's cells cut
 //                          into chunks of NCH at fixed positions within the batch.  Per chunk and gene, two sweeps over the
-//                          chunk while it sits in the block buffer: the sum in cell order gives the chunk mean, then the
-//                          sum of (x - chunk mean)^2 in cell order.  Also the flag for a value that is not finite.
+//                          chunk while it sits in the block buffer: the sum gives the chunk mean, then the sum of
+//                          (x - chunk mean)^2, both in the cell order of ordered_sums.hpp.  Also the flag for a value
+//                          that is not finite.
 //     gv_csc_check_kernel  one wave a cell over its stored entries: the flags for a value that is not finite, a row
 //                          outside [0, G) and rows that do not ascend strictly within a column
 //     gv_csc_kernel        one workgroup per (chunk, tile of GT genes), sum / count / squares of the tile in the LDS:
@@ -16,8 +17,8 @@
 //     gv_merge_kernel      one thread a gene: the block's chunks, ascending, folded into the gene's running
 //                          (mean, M2) by genevar_merge (gene_var_host.hpp); the count is the same for every gene
 //   per batch: gv_final_kernel, total = M2 / (n - 1)
-// Never the one-pass E[x^2] - E[x]^2.  No floating-point atomics, one accumulator per sum, contraction off: the chunk
-// edges do not depend on the blocks (a block holds whole chunks), so every block width and every run give the same bits.
+// Never the one-pass E[x^2] - E[x]^2.  Contraction off; the chunk edges do not depend on the blocks (a block holds whole
+// chunks), and the sums keep the orders of ordered_sums.hpp, so every block width and every run give the same bits.
 // A block's entry positions come from an indptr the host has checked (check_csc_block); a row index is compared with its
 // bounds before it addresses anything, and an entry that fails is skipped.
 #include <algorithm>
@@ -29,6 +30,7 @@
 #include "csc_device.hpp"
 #include "gene_var_host.hpp"
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -59,78 +61,41 @@ __global__ __launch_bounds__(256) void gv_dense_kernel(const double* __restrict_
     if (V2) {
         const double2* x2 = reinterpret_cast<const double2*>(x);
         const int64_t G2 = G / 2;
+        const auto at = [&](int64_t i) { return x2[i * G2 + t]; };
         double s0 = 0.0, s1 = 0.0;
-        int64_t i = b;
-        for (; i + 4 <= e; i += 4) {  // four loads in flight, added in cell order
-            const double2 v0 = x2[i * G2 + t], v1 = x2[(i + 1) * G2 + t], v2 = x2[(i + 2) * G2 + t], v3 = x2[(i + 3) * G2 + t];
-            bad |= not_finite(v0.x) | not_finite(v0.y) | not_finite(v1.x) | not_finite(v1.y);
-            bad |= not_finite(v2.x) | not_finite(v2.y) | not_finite(v3.x) | not_finite(v3.y);
-            s0 += v0.x;
-            s1 += v0.y;
-            s0 += v1.x;
-            s1 += v1.y;
-            s0 += v2.x;
-            s1 += v2.y;
-            s0 += v3.x;
-            s1 += v3.y;
-        }
-        for (; i < e; ++i) {
-            const double2 v = x2[i * G2 + t];
-            bad |= not_finite(v.x) | not_finite(v.y);
-            s0 += v.x;
-            s1 += v.y;
-        }
+        ordered_walk4(
+            b, e,
+            [&](int64_t i) {
+                const double2 v = at(i);
+                bad |= not_finite(v.x) | not_finite(v.y);
+                return v;
+            },
+            [&](double2 v) {
+                s0 += v.x;
+                s1 += v.y;
+            });
         const double m0 = s0 / cnt, m1 = s1 / cnt;
         double q0 = 0.0, q1 = 0.0;
-        i = b;
-        for (; i + 4 <= e; i += 4) {
-            const double2 v0 = x2[i * G2 + t], v1 = x2[(i + 1) * G2 + t], v2 = x2[(i + 2) * G2 + t], v3 = x2[(i + 3) * G2 + t];
-            q0 += (v0.x - m0) * (v0.x - m0);
-            q1 += (v0.y - m1) * (v0.y - m1);
-            q0 += (v1.x - m0) * (v1.x - m0);
-            q1 += (v1.y - m1) * (v1.y - m1);
-            q0 += (v2.x - m0) * (v2.x - m0);
-            q1 += (v2.y - m1) * (v2.y - m1);
-            q0 += (v3.x - m0) * (v3.x - m0);
-            q1 += (v3.y - m1) * (v3.y - m1);
-        }
-        for (; i < e; ++i) {
-            const double2 v = x2[i * G2 + t];
+        ordered_walk4(b, e, at, [&](double2 v) {
             q0 += (v.x - m0) * (v.x - m0);
             q1 += (v.y - m1) * (v.y - m1);
-        }
+        });
         reinterpret_cast<double2*>(pmean)[ch * G2 + t] = make_double2(m0, m1);
         reinterpret_cast<double2*>(pm2)[ch * G2 + t] = make_double2(q0, q1);
     } else {
+        const auto at = [&](int64_t i) { return x[i * G + t]; };
         double s = 0.0;
-        int64_t i = b;
-        for (; i + 4 <= e; i += 4) {
-            const double v0 = x[i * G + t], v1 = x[(i + 1) * G + t], v2 = x[(i + 2) * G + t], v3 = x[(i + 3) * G + t];
-            bad |= not_finite(v0) | not_finite(v1) | not_finite(v2) | not_finite(v3);
-            s += v0;
-            s += v1;
-            s += v2;
-            s += v3;
-        }
-        for (; i < e; ++i) {
-            const double v = x[i * G + t];
-            bad |= not_finite(v);
-            s += v;
-        }
+        ordered_walk4(
+            b, e,
+            [&](int64_t i) {
+                const double v = at(i);
+                bad |= not_finite(v);
+                return v;
+            },
+            [&](double v) { s += v; });
         const double m0 = s / cnt;
         double q = 0.0;
-        i = b;
-        for (; i + 4 <= e; i += 4) {
-            const double v0 = x[i * G + t], v1 = x[(i + 1) * G + t], v2 = x[(i + 2) * G + t], v3 = x[(i + 3) * G + t];
-            q += (v0 - m0) * (v0 - m0);
-            q += (v1 - m0) * (v1 - m0);
-            q += (v2 - m0) * (v2 - m0);
-            q += (v3 - m0) * (v3 - m0);
-        }
-        for (; i < e; ++i) {
-            const double v = x[i * G + t];
-            q += (v - m0) * (v - m0);
-        }
+        ordered_walk4(b, e, at, [&](double v) { q += (v - m0) * (v - m0); });
         pmean[ch * G + t] = m0;
         pm2[ch * G + t] = q;
     }

@@ -14,9 +14,9 @@
 //      sort (rank_kernel: every observation's rank among the equal labels of its chunk and the chunk's label counts;
 //      chunk_scan_kernel: the chunks' offsets per label and `size`; cluster_scan_kernel: the clusters' starts, their
 //      pieces of PIECE = 256 members, the empty-cluster flag; scatter_kernel: the index list), so every cluster's
-//      members stand in ascending order.  update_partial_kernel adds a piece's members in that order (each wave a
-//      quarter, the quarters then in order), update_reduce_kernel a cluster's pieces in ascending order and divides by
-//      the size.  Two runs give the same bits.
+//      members stand in ascending order.  update_partial_kernel adds a piece's members (each wave a quarter, the
+//      quarters then in order), update_reduce_kernel a cluster's pieces, and divides by the size: the orders are those
+//      of ordered_sums.hpp.
 // withinss is taken directly as sum (x - c)^2 over the same pieces (wss_partial_kernel / wss_reduce_kernel).
 #include <algorithm>
 #include <cmath>
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -244,18 +245,9 @@ __global__ __launch_bounds__(256) void update_partial_kernel(const double* __res
     const int pe = min(start[j + 1], pb + PIECE);
     const int b = min(pe, pb + 64 * w), e = min(pe, pb + 64 * w + 64);
     double s = 0.0;
-    if (g < d) {
-        int i = b;
-        for (; i + 4 <= e; i += 4) {  // four loads in flight, added in list order
-            const int64_t m0 = order[i], m1 = order[i + 1], m2 = order[i + 2], m3 = order[i + 3];
-            const double v0 = x[m0 * d + g], v1 = x[m1 * d + g], v2 = x[m2 * d + g], v3 = x[m3 * d + g];
-            s += v0;
-            s += v1;
-            s += v2;
-            s += v3;
-        }
-        for (; i < e; ++i) s += x[(int64_t)order[i] * d + g];
-    }
+    if (g < d)
+        ordered_walk4(
+            b, e, [&](int i) { return x[(int64_t)order[i] * d + g]; }, [&](double v) { s += v; });
     sh[w][lane] = s;
     __syncthreads();
     if (w == 0 && g < d) part[(int64_t)p * d + g] = ((sh[0][lane] + sh[1][lane]) + sh[2][lane]) + sh[3][lane];
@@ -271,9 +263,8 @@ __global__ __launch_bounds__(256) void update_reduce_kernel(const double* __rest
     if (g >= d || j >= K) return;
     const int f = piece0[j], l = piece0[j + 1];
     if (f == l) return;
-    double s = part[(int64_t)f * d + g];
-    for (int p = f + 1; p < l; ++p) s += part[(int64_t)p * d + g];
-    centres[(int64_t)j * d + g] = s / (double)size[j];
+    const auto at = [&](int p) { return part[(int64_t)p * d + g]; };
+    centres[(int64_t)j * d + g] = fold_ascending(at(f), f + 1, l, at) / (double)size[j];
 }
 
 // wpart[p] = sum over piece p's members and all dimensions of (x - c)^2: every lane its dimensions g = lane, lane + 64, ...
@@ -310,9 +301,7 @@ __global__ __launch_bounds__(256) void wss_reduce_kernel(const double* __restric
                                                          const int32_t* __restrict__ piece0, double* __restrict__ withinss) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= K) return;
-    double s = 0.0;
-    for (int p = piece0[j]; p < piece0[j + 1]; ++p) s += wpart[p];
-    withinss[j] = s;
+    withinss[j] = fold_ascending(0.0, piece0[j], piece0[j + 1], [&](int p) { return wpart[p]; });
 }
 
 }  // namespace

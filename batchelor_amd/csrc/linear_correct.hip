@@ -2,10 +2,10 @@
 // passes over genes x cells FP64 matrices in R's layout, uploaded once (whole or in column blocks) and kept in HBM.
 //   pass 1  per-gene sums over a batch's restricted cells.  The restricted cells, ascending, are cut into chunks of LCH at
 //           fixed positions of that list; sum_partial_kernel adds a chunk's cells in list order (one workgroup per chunk
-//           and tile of 256 genes, lanes along the genes), mean_kernel adds the chunk sums in ascending chunk order.  A
-//           chunk is summed by the first add_block call after which all its cells are resident, on a second stream behind
-//           the upload of the next block: the chunk edges do not depend on the blocks, so every blocking of the upload
-//           and every run gives the same bits.  No floating-point atomics.
+//           and tile of 256 genes, lanes along the genes), mean_kernel adds the chunk sums in ascending order: the rules
+//           of ordered_sums.hpp (sum_partial_kernel keeps its own copy of the walk: the helper cost its pow forms 3 %).
+//           A chunk is summed by the first add_block call after which all its cells are resident, on a second stream
+//           behind the upload of the next block.
 //             rescaleBatches          sums of log.base^x - pseudo.count (.unlog, :140-143)
 //             regressBatches, default sums of x: the coefficient of a batch's indicator column is its mean
 //             regressBatches, design  coef = X[:, R] %*% W (W = pinv(D[R, ])^T from the host's QR), chunks of GCH cells,
@@ -26,6 +26,7 @@
 
 #include "bmx_ops.hpp"
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -66,6 +67,7 @@ __global__ __launch_bounds__(256) void sum_partial_kernel(const double* __restri
     const int64_t e = b + LCH < m ? b + LCH : m;
     double s = 0.0;
     int64_t i = b;
+    // (its own loop, not ordered_walk4: on the helper the pow forms came out 3 % slower, MEASUREMENTS.md)
     for (; i + 4 <= e; i += 4) {  // four loads in flight, added in list order
         const int64_t c0 = order ? order[i] : i, c1 = order ? order[i + 1] : i + 1;
         const int64_t c2 = order ? order[i + 2] : i + 2, c3 = order ? order[i + 3] : i + 3;
@@ -97,9 +99,8 @@ __global__ __launch_bounds__(256) void mean_kernel(const double* __restrict__ pa
                                                    double* __restrict__ mean) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= G) return;
-    double s = part[g];
-    for (int ch = 1; ch < nchunks; ++ch) s += part[(int64_t)ch * G + g];
-    mean[g] = s / m;
+    const auto at = [&](int ch) { return part[(int64_t)ch * G + g]; };
+    mean[g] = fold_ascending(at(0), 1, nchunks, at) / m;
 }
 
 // avg [B][G] -> ref [G] = pmin over the batches (NaN if any is), scale [B][G] = ref / avg, 0 where that is not finite
@@ -183,9 +184,8 @@ __global__ __launch_bounds__(256) void coef_reduce_kernel(const double* __restri
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int j = blockIdx.y;
     if (g >= G) return;
-    double s = part[(int64_t)j * G + g];
-    for (int ch = 1; ch < nchunks; ++ch) s += part[((int64_t)ch * p16 + j) * G + g];
-    coef[(int64_t)j * G + g] = s;
+    const auto at = [&](int ch) { return part[((int64_t)ch * p16 + j) * G + g]; };
+    coef[(int64_t)j * G + g] = fold_ascending(at(0), 1, nchunks, at);
 }
 
 // out[g, c] = x[g, c] - sum_j coef[g, drop[j]] * dd[c][j]: the dropped columns in tiles of PT, ascending; dd [mb][pd16]
@@ -248,13 +248,12 @@ void linear_check_regress(const double* design, int p, const double* w, const in
         if (keep[i] < 1 || keep[i] > p) throw Error(BMX_ERR_ARG, "'keep' indices out of range");
 }
 
-struct LinearBatch : ResidentBatch {
+struct LinearBatch : ResidentBatch, ChunkProgress {
     DevBuf<double> u;        // [n][G] unlogged values, when they are kept
     DevBuf<double> part;     // [nchunks][G]
     DevBuf<int32_t> order;   // restricted cells (0-based) ascending, empty without restriction
     std::vector<int32_t> order_host;
     int64_t m = 0;  // restricted cells
-    int nchunks = 0, sum_done = 0;
     int sum_kind = 0;  // what part / the mean slot hold: 0 nothing, 1 plain, 2 unlogged
     double sum_base = 0.0, sum_pseudo = 0.0;
     bool has_u = false;
@@ -505,7 +504,7 @@ class Linear : ResidentBatches<LinearBatch> {
         if (!b.order_host.empty())
             have = std::lower_bound(b.order_host.begin(), b.order_host.end(), (int32_t)std::min<int64_t>(b.filled, 0x7fffffff)) -
                    b.order_host.begin();
-        const int complete = have == b.m ? b.nchunks : (int)(have / LCH);
+        const int complete = b.chunks_complete(have, b.m, LCH);
         if (complete <= b.sum_done) return;
         const int G = G_;
         const dim3 grid((unsigned)(complete - b.sum_done), (unsigned)cdiv(G, 256));

@@ -5,17 +5,16 @@
 //             colsum_kernel        one wave a cell: its sum over S (the library size) in a fixed lane order, and the
 //                                  device flag for a negative or non-finite count
 //             gene_partial_kernel  lanes along the genes of S, cells cut into chunks of NCH at fixed positions:
-//                                  part[chunk][g] = sum of x[g, c] / w[c] in cell order, w = the library sizes (or the
-//                                  size factors given).  A chunk is summed once all its cells are resident: the chunk
-//                                  edges do not depend on the blocks, so every blocking of the upload gives the same bits.
+//                                  part[chunk][g] = sum of x[g, c] / w[c], w = the library sizes (or the size factors
+//                                  given).  A chunk is summed once all its cells are resident.
 //   stats   finalize_kernel  mean(w) in a fixed order, sf = w / mean(w), the flag for a size factor that is not positive
-//           ave_kernel       ave[g] = (chunk sums, ascending) * (mean(w) / n)  [= (1/n) sum x / sf]
+//           ave_kernel       ave[g] = (chunk sums) * (mean(w) / n)  [= (1/n) sum x / sf]
 //   ratios  ratio_kernel     one workgroup per unordered pair: both sums, the keep rule, both medians by an exact radix
 //                            selection on the bit patterns of the (non-negative) ratios; smallest_kernel: the diagonal,
 //                            the reference batch and the rescaling; sfout_kernel: sf / rescaling
 //   output  norm_out_kernel  log2(x / sf_out + pseudo) (or x / sf_out), in blocks through two device buffers that
 //                            download behind the kernels (blocked_output)
-// No floating-point atomics, FP64 vector arithmetic, contraction off: the same input gives the same bits on every run.
+// The orders of the sums are those of ordered_sums.hpp.  FP64 vector arithmetic, contraction off.
 //
 // Sparse counts (NormSparse, bmx_norm_sparse_*): a batch stays in HBM as CSC -- indptr [n + 1] int64 absolute, indices
 // int32, data FP64 -- filled in column blocks through the same staging ring.  The reductions and the output pass have
@@ -38,6 +37,7 @@
 #include "bmx_ops.hpp"
 #include "csc_device.hpp"
 #include "host_xfer.hpp"
+#include "ordered_sums.hpp"
 #include "resident_batches.hpp"
 
 namespace bmx {
@@ -139,38 +139,25 @@ __global__ __launch_bounds__(256) void gene_partial_kernel(const double* __restr
         const double2* x2 = reinterpret_cast<const double2*>(x);
         const int64_t G2 = G / 2;
         double s0 = 0.0, s1 = 0.0;
-        int64_t i = b;
-        for (; i + 4 <= e; i += 4) {  // four loads in flight, added in cell order
-            const double2 v0 = x2[i * G2 + t], v1 = x2[(i + 1) * G2 + t], v2 = x2[(i + 2) * G2 + t], v3 = x2[(i + 3) * G2 + t];
-            const double w0 = w[i], w1 = w[i + 1], w2 = w[i + 2], w3 = w[i + 3];
-            s0 += v0.x / w0;
-            s1 += v0.y / w0;
-            s0 += v1.x / w1;
-            s1 += v1.y / w1;
-            s0 += v2.x / w2;
-            s1 += v2.y / w2;
-            s0 += v3.x / w3;
-            s1 += v3.y / w3;
-        }
-        for (; i < e; ++i) {
-            const double2 v = x2[i * G2 + t];
-            const double wi = w[i];
-            s0 += v.x / wi;
-            s1 += v.y / wi;
-        }
+        struct Term {
+            double2 v;
+            double w;
+        };
+        ordered_walk4(
+            b, e, [&](int64_t i) { return Term{x2[i * G2 + t], w[i]}; },
+            [&](const Term& q) {
+                s0 += q.v.x / q.w;
+                s1 += q.v.y / q.w;
+            });
         reinterpret_cast<double2*>(part)[(int64_t)ch * (nS / 2) + t] = make_double2(s0, s1);
     } else {
         const int64_t r = rows ? rows[t] : t;
         double s = 0.0;
-        int64_t i = b;
-        for (; i + 4 <= e; i += 4) {
-            const double v0 = x[i * G + r], v1 = x[(i + 1) * G + r], v2 = x[(i + 2) * G + r], v3 = x[(i + 3) * G + r];
-            s += v0 / w[i];
-            s += v1 / w[i + 1];
-            s += v2 / w[i + 2];
-            s += v3 / w[i + 3];
-        }
-        for (; i < e; ++i) s += x[i * G + r] / w[i];
+        struct Term {
+            double v, w;
+        };
+        ordered_walk4(
+            b, e, [&](int64_t i) { return Term{x[i * G + r], w[i]}; }, [&](const Term& q) { s += q.v / q.w; });
         part[(int64_t)ch * nS + t] = s;
     }
 }
@@ -180,15 +167,7 @@ template <int T>
 __device__ double block_sum(const double* __restrict__ a, int64_t n, double* red) {
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += T) s += a[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = T / 2; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
+    return block_tree_sum<T>(s, red);
 }
 
 // one workgroup a batch: sf = w / mean(w), scale[0] = mean(w) / n
@@ -211,9 +190,8 @@ __global__ __launch_bounds__(256) void ave_kernel(const double* __restrict__ par
                                                   const double* __restrict__ scale, double* __restrict__ ave) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= nS) return;
-    double s = part[g];
-    for (int ch = 1; ch < nchunks; ++ch) s += part[(int64_t)ch * nS + g];
-    ave[g] = s * scale[0];
+    const auto at = [&](int ch) { return part[(int64_t)ch * nS + g]; };
+    ave[g] = fold_ascending(at(0), 1, nchunks, at) * scale[0];
 }
 
 // .rescale_size_factors' filter (R/multiBatchNorm.R:253-254), in R's order of evaluation
@@ -423,9 +401,8 @@ __global__ __launch_bounds__(256) void ave_rows_kernel(const double* __restrict_
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= nS) return;
     const int r = rows[g];
-    double s = part[r];
-    for (int ch = 1; ch < nchunks; ++ch) s += part[(int64_t)ch * G + r];
-    ave[g] = s * scale[0];
+    const auto at = [&](int ch) { return part[(int64_t)ch * G + r]; };
+    ave[g] = fold_ascending(at(0), 1, nchunks, at) * scale[0];
 }
 
 // out[k - k0] = log2(val[k] / sfo[c] + pseudo) (LOG) or val[k] / sfo[c] for the stored entries k of the cells c in
@@ -481,13 +458,12 @@ void norm_check_run(double min_mean, int log, double pseudo_count) {
 }
 
 // what both handles keep for a batch beside its counts
-struct NormStats {
+struct NormStats : ChunkProgress {
     DevBuf<double> w;     // [n] library sizes, or the size factors given
     DevBuf<double> sf;    // [n] w / mean(w)
     DevBuf<double> sfo;   // [n] sf / rescaling
     DevBuf<double> part;  // [nchunks][nS] (sparse counts: [nchunks][G])
     bool given = false;
-    int nchunks = 0, sum_done = 0;
 };
 struct NormBatch : ResidentBatch, NormStats {};
 
@@ -717,7 +693,7 @@ class Norm : ResidentBatches<NormBatch> {
             hipLaunchKernelGGL(colsum_kernel<0>, cgrid, dim3(256), 0, kstream_, (const double*)b.x.p, G, c0, m,
                                (const double*)nullptr, w, flags_.p);
         BMX_LAUNCH_CHECK();
-        const int complete = b.complete() ? b.nchunks : (int)(b.filled / NCH);
+        const int complete = b.chunks_complete(b.filled, b.n, NCH);
         if (complete > b.sum_done) {
             const unsigned nch = (unsigned)(complete - b.sum_done);
             if (!subset_ && G % 2 == 0)
@@ -876,7 +852,7 @@ class NormSparse : ResidentBatches<SparseNormBatch> {
                            (const int32_t*)b.indices.p, (const double*)b.data.p, G_, c0, m,
                            (const double*)(subset_ ? mult_.p : nullptr), b.given ? nullptr : b.w.p, flags_.p);
         BMX_LAUNCH_CHECK();
-        const int complete = b.complete() ? b.nchunks : (int)(b.filled / NCH);
+        const int complete = b.chunks_complete(b.filled, b.n, NCH);
         for (int ch = b.sum_done; ch < complete; ch += 65535) {  // (a grid dimension holds at most 65 535 workgroups)
             const unsigned nch = (unsigned)std::min(65535, complete - ch);
             hipLaunchKernelGGL(sp_gene_partial_kernel, dim3(nch, (unsigned)cdiv(G_, GT)), dim3(256), 0, kstream_,

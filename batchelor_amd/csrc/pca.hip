@@ -64,9 +64,7 @@ class Pca : ResidentBatches<PcaBatch> {
     void add_block(const double* x_block, int64_t m) {
         add(x_block, m, [&](PcaBatch& b, double* p) {
             if (!b.cos_norm) return;
-            hipLaunchKernelGGL(inv_l2_kernel, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, stream_, p, m, G_,
-                               b.inv.p + (b.filled - m));
-            BMX_LAUNCH_CHECK();
+            cell_l2_device(stream_, p, G_, m, nullptr, 0, true, b.inv.p + (b.filled - m));
         });
     }
     void add_batch(const double* x, int64_t n, double weight, bool cos_norm) {

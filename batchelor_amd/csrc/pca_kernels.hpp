@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bmx_ops.hpp"
+#include "ordered_sums.hpp"
 
 namespace bmx {
 namespace {
@@ -195,8 +196,7 @@ __global__ void reduce_parts(const double* __restrict__ part, int nsplit, int64_
                              double* __restrict__ Y, int w, int64_t ldy) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= len) return;
-    double s = 0.0;
-    for (int p = 0; p < nsplit; ++p) s += part[(int64_t)p * len + e];
+    const double s = fold_ascending(0.0, 0, nsplit, [&](int p) { return part[(int64_t)p * len + e]; });
     const int64_t o = (e / w) * ldy + e % w;
     Y[o] = (beta == 0.0 ? 0.0 : beta * Y[o]) + alpha * s;
 }
@@ -212,21 +212,6 @@ __global__ __launch_bounds__(256) void colsum64_partial(const double* __restrict
     sm[q][j] = s;
     __syncthreads();
     if (q == 0) part[(int64_t)blockIdx.x * 64 + j] = (sm[0][j] + sm[1][j]) + (sm[2][j] + sm[3][j]);
-}
-
-// per-cell 1 / max(1e-8, l2) (R/cosineNorm.R:63-82); one wave per cell
-__global__ __launch_bounds__(256) void inv_l2_kernel(const double* __restrict__ X, int64_t n, int G, double* __restrict__ inv) {
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (c >= n) return;
-    const double* col = X + c * G;
-    double s = 0.0;
-    for (int g = lane; g < G; g += 64) s += col[g] * col[g];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) {
-        const double l2 = sqrt(s);
-        inv[c] = 1.0 / (l2 < 1e-8 ? 1e-8 : l2);
-    }
 }
 
 // gene sums over the cells of a chunk: part[chunk][g] = sum_c rs[c] X[c][g]

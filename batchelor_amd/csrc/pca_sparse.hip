@@ -122,10 +122,7 @@ __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restri
     if (bad_order) flags[CSC_F_ORDER] = 1;
     if (lane == 0) {
         cut[c] = kb + below;
-        if (inv) {
-            const double l2 = sqrt(s);
-            inv[c] = 1.0 / (l2 < 1e-8 ? 1e-8 : l2);
-        }
+        if (inv) inv[c] = 1.0 / cos_clamp(sqrt(s));
     }
 }
 

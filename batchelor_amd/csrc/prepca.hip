@@ -4,6 +4,7 @@
 // fused into ONE pass over the genes x cells matrix:   out[c, j] = (sum_g x[g,c] u[g,j]) / L_c - sum_g centers[g] u[g,j]
 // with L_c = max(1e-8, l2[c]) (or 1 without cosine normalisation).  x is read exactly once; FP64 throughout.
 #include "bmx_ops.hpp"
+#include "ordered_sums.hpp"
 
 namespace bmx {
 namespace {
@@ -11,25 +12,36 @@ namespace {
 constexpr int CB = 16;  // cells per workgroup
 constexpr int GT = 64;  // genes per staged tile
 
-__global__ __launch_bounds__(256) void colnorm_kernel(const double* __restrict__ x, int G, int n,
-                                                      double* __restrict__ l2) {
-    // one wave per cell (column): the column is contiguous
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+// The l2 norm of every cell, one wave per cell (a column is contiguous): over the ng genes listed in genes0 (0-based;
+// cosineNorm(x, mode="l2norm", subset.row=)) or, genes0 null, over all G.  out[c] = l2, or with `inverse` 1 / pmax(1e-8, l2).
+__global__ __launch_bounds__(256) void cell_l2_kernel(const double* __restrict__ x, int G, int64_t n,
+                                                      const int32_t* __restrict__ genes0, int ng, bool inverse,
+                                                      double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (c >= n) return;
-    const double* col = x + (int64_t)c * G;
+    const double* col = x + c * G;
     double s = 0.0;
-    for (int g = lane; g < G; g += 64) s += col[g] * col[g];
+    if (genes0) {
+        for (int i = lane; i < ng; i += 64) {
+            const double v = col[genes0[i]];
+            s += v * v;
+        }
+    } else {
+        for (int g = lane; g < G; g += 64) s += col[g] * col[g];
+    }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) l2[c] = sqrt(s);
+    if (lane == 0) {
+        const double l2 = sqrt(s);
+        out[c] = inverse ? 1.0 / cos_clamp(l2) : l2;
+    }
 }
 
 __global__ void apply_cosnorm_kernel(const double* __restrict__ x, int G, int n, const double* __restrict__ l2,
                                      double* __restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (int64_t)G * n) return;
-    const double L = l2[e / G];
-    out[e] = x[e] / (L < 1e-8 ? 1e-8 : L);  // pmax(1e-8, l2)
+    out[e] = x[e] / cos_clamp(l2[e / G]);
 }
 
 __global__ __launch_bounds__(256) void cosnorm_project_kernel(const double* __restrict__ x, int G, int n,
@@ -74,7 +86,7 @@ __global__ __launch_bounds__(256) void cosnorm_project_kernel(const double* __re
     s2 = __shfl(s2, (tid & 63) & ~15);  // the jg == 0 lane of this cell's 16-lane group
     if (c >= n) return;
     const double l2 = sqrt(s2);
-    const double L = cos_norm ? (l2 < 1e-8 ? 1e-8 : l2) : 1.0;
+    const double L = cos_norm ? cos_clamp(l2) : 1.0;
 #pragma unroll
     for (int t = 0; t < JMAX; ++t) {
         const int j = jg + 16 * t;
@@ -97,10 +109,16 @@ __global__ void center_dot_kernel(const double* __restrict__ centers, const doub
 
 }  // namespace
 
-void cosine_l2_device(hipStream_t stream, const double* x, int G, int n, double* l2) {
+void cell_l2_device(hipStream_t stream, const double* x, int G, int64_t n, const int32_t* genes0, int n_genes, bool inverse,
+                    double* out) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(colnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, x, G, n, l2);
+    hipLaunchKernelGGL(cell_l2_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, x, G, n, genes0, n_genes, inverse,
+                       out);
     BMX_LAUNCH_CHECK();
+}
+
+void cosine_l2_device(hipStream_t stream, const double* x, int G, int n, double* l2) {
+    cell_l2_device(stream, x, G, n, nullptr, 0, false, l2);
 }
 
 void apply_cosine_norm_device(hipStream_t stream, const double* x, int G, int n, const double* l2, double* out) {

@@ -102,6 +102,18 @@ inline void throw_if_bad_pattern(const int32_t* pair) {
         throw Error(BMX_ERR_ARG, "sparse counts: the row indices of a column should be strictly ascending");
 }
 
+// ---- the per-gene sums of a batch whose cells are cut into chunks of `width` at fixed positions: a chunk is summed by
+// the first block after which all its cells are resident, so the chunk edges never depend on the blocks
+struct ChunkProgress {
+    int nchunks = 0;   // chunks of the whole batch
+    int sum_done = 0;  // chunks summed so far
+    // the chunks that are complete with `have` of the batch's `total` cells resident: the whole ones, and with the last
+    // cell the short one at the end
+    int chunks_complete(int64_t have, int64_t total, int width) const {
+        return have == total ? nchunks : (int)(have / width);
+    }
+};
+
 // ---- a block of a pass that writes every cell or stored entry: the cells [c0, c0 + mb) of batch bi, `count` elements
 // that go to outs[bi] + at
 struct OutBlock {

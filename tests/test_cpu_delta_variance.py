@@ -113,9 +113,10 @@ def case(name):
         else:
             left, right = cross_pairs(C + 1, SIZES, 52, avoid=(zero,))
         return Case(B, [(left, right)], cos_norm=True)
-    if name.startswith("subset"):                                    # subset[-all][-cos]
+    if name.startswith("subset"):                                    # subset[-all][-cos][:number of genes]
         G = 2 * T + 1
-        sub = np.random.default_rng(61).permutation(G)[:T + 44] + 1  # shuffled
+        n_sub = int(name.split(":")[1]) if ":" in name else T + 44
+        sub = np.random.default_rng(61).permutation(G)[:n_sub] + 1   # shuffled
         return Case(make_batches(G, SIZES, 62), [cross_pairs(C + 1, SIZES, 63)], subset_row=sub,
                     compute_all="-all" in name, cos_norm="-cos" in name)
     if name == "offset":     # the second batch is the first plus 1e4 per gene, with unit noise

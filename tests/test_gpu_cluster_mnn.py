@@ -74,6 +74,32 @@ def test_centroids_against_numpy(handle, G, cos_norm, restricted):
     assert err < 1e-5
 
 
+@pytest.mark.parametrize("G,subset", [(1, None), (2, None), (255, 1), (256, 63), (257, 64), (258, 65)])
+@pytest.mark.parametrize("restricted", [False, True])
+def test_centroids_at_the_edges_of_the_chunk_walk(handle, G, subset, restricted):
+    """Clusters of 1, 3, 4, 5, 255, 256, 257 and 513 cells (chunks of 256), restricted lists of 4k + 1, 4k + 2 and 4k + 3
+    cells, gene counts on either side of the 256-gene tile; the cosine norms over all genes or over a list of 1, 63, 64
+    and 65 (a wave takes 64 at a time)."""
+    sizes = np.array([1, 3, 4, 5, 255, 256, 257, 513])
+    rng = np.random.default_rng(G + restricted)
+    lab = rng.permutation(np.repeat(np.arange(sizes.size), sizes))
+    x = rng.normal(size=(G, lab.size)) + 2.0
+    sub = None if subset is None else (np.sort(rng.choice(G, size=subset, replace=False)) + 1).astype(np.int32)
+    restrict = None
+    if restricted:
+        keep = [1, 2, 3, 5, 6, 7, 255, 257]
+        restrict = np.sort(np.concatenate([rng.choice(np.flatnonzero(lab == c), size=m, replace=False)
+                                           for c, m in enumerate(keep)]) + 1).astype(np.int32)
+    h = handle(G, sub, 0)
+    h.add_batch(x, lab.astype(np.int32), sizes.size, restrict, True)
+    got = h.centroids(0)
+    h.close()
+    want, levels = ref.compute_centroids(x / np.maximum(ref.cosine_l2(x, sub), 1e-8), lab, restrict)
+    err = rel(got, want)
+    print(f"centroids at the edges G={G} norm genes={subset} restricted={restricted}: max rel err {err:.3e}")
+    assert err < 1e-5
+
+
 def test_centroids_blocked_upload_equals_whole(handle):
     rng = np.random.default_rng(11)
     G, n = 300, 5000

@@ -134,6 +134,27 @@ def test_invariants_of_an_unconverged_run(bx, n, d, K):
     assert set(out.stats["stage_ms"]) == {"upload", "assign", "update", "withinss", "download"}
 
 
+@pytest.mark.parametrize("d", [1, 65])
+def test_clusters_at_the_edges_of_a_wave_and_of_a_piece(bx, d):
+    """Well separated clusters of 1, 63, 64 and 65 members (a wave of the update adds 64), of one piece of 256 and of a
+    piece plus one member: the labels are the planted ones and the centres their means."""
+    sizes = np.array([1, 63, 64, 65, 256, 257])
+    K = sizes.size
+    rng = np.random.default_rng(40 + d)
+    planted = np.zeros((K, d))
+    planted[:, 0] = 100.0 * np.arange(K)
+    lab = rng.permutation(np.repeat(np.arange(K), sizes))
+    x = planted[lab] + rng.normal(size=(lab.size, d))
+    out = quiet(bx.kmeans, x, planted + 0.5, iter_max=2)
+    assert np.array_equal(out.cluster.astype(np.int64) - 1, lab) and np.array_equal(out.size, sizes)
+    means = np.stack([np.bincount(lab, weights=x[:, k], minlength=K) for k in range(d)], axis=1) / sizes[:, None]
+    diff = x - means[lab]
+    wss = np.bincount(lab, weights=np.einsum("ik,ik->i", diff, diff), minlength=K)
+    print(f"sizes {sizes.tolist()} d={d}: centres {rel(out.centers, means):.3g}, withinss {rel(out.withinss, wss):.3g}")
+    assert rel(out.centers, means) <= 1e-12
+    assert rel(out.withinss, wss) <= 1e-12
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # reproducibility, starts, blocks
 # ---------------------------------------------------------------------------------------------------------------------

@@ -64,6 +64,26 @@ def test_rescale(G, restricted, log_base, pseudo):
     assert set(got.stats["stage_ms"]) == set(lc.STAGES)
 
 
+EDGE_SIZES = (1, 3, 4, 5, 255, 256, 257, 513)      # chunks of 1, 3, 4, 5, 255, 256 and 257 cells, and two chunks plus one
+EDGE_RESTRICTED = (1, 2, 3, 5, 6, 7, 255, 257)     # restricted lists of 4k + 1, 4k + 2 and 4k + 3 cells
+
+
+@pytest.mark.parametrize("G", [1, 2, 255, 256, 257, 258])   # a single lane of a second tile of 256 genes at 257
+@pytest.mark.parametrize("restricted", [False, True])
+def test_edges_of_the_chunk_walk(G, restricted):
+    rng = np.random.default_rng(130 + G)
+    B = [np.log2(rng.poisson(rng.uniform(2.0, 30.0, (G, 1)), (G, n)) + 1.0) for n in EDGE_SIZES]
+    r = [np.sort(rng.choice(n, m, replace=False)) + 1 for n, m in zip(EDGE_SIZES, EDGE_RESTRICTED)] if restricted else None
+    got = bx.rescaleBatches(*B, restrict=r)
+    want, avg, reference = ref.rescale_batches(B, 2.0, 1.0, None, r)
+    e = max(excess(got.corrected, want), excess(got.averages, avg), excess(got.reference, reference))
+    reg = bx.regressBatches(*B, restrict=r)
+    want, labels, coef = ref.regress(B, restrict=r)
+    e2 = max(excess(reg.corrected, want), excess(reg.coefficients, coef))
+    print(f"chunk edges G={G} restrict={restricted}: error / allowance: rescale {e:.3g}, regress {e2:.3g}")
+    assert e <= 1.0 and e2 <= 1.0
+
+
 def test_rescale_rows_of_zeros_stay_zero():
     B = make(500, SIZES[500], 150)
     got = bx.rescaleBatches(*B).corrected

@@ -15,11 +15,12 @@ from tests import pca_sparse_ref
 
 pytestmark = pytest.mark.gpu
 
-CELLS = (2, 255, 256, 257, 513)
+CELLS = (2, 3, 4, 5, 255, 256, 257, 513)   # the edges of the walk over a chunk of 256 cells, four at a time
 
 
 def gene_counts():
-    return (1, 63, 64, 65, mgv.gene_tile() + 1)
+    # odd counts take the scalar form, even ones two genes a lane; 257 and 258 put a single lane into a second tile
+    return (1, 2, 63, 64, 65, 255, 256, 257, 258, mgv.gene_tile() + 1)
 
 
 def bits(a):

@@ -23,6 +23,13 @@ SHAPES = {                       # genes, cells per batch
     "g255": (255, (3, 600)),
     "g257": (257, (65, 1, 64, 3, 600)),
     "g1000": (1000, (600, 65, 3)),
+    # the chunk walk's edges, in the scalar form (odd gene counts) and the two-gene form (even ones): chunks of 1, 3, 4, 5,
+    # 255, 256 and 257 cells and two chunks plus one; 257 and 258 genes put a single lane into a second tile
+    "g1-chunks": (1, (4, 5, 255)),
+    "g255-chunks": (255, (256, 257, 513)),
+    "g2-chunks": (2, (1, 3, 4, 5)),
+    "g256-chunks": (256, (255, 256, 257, 513)),
+    "g258-chunks": (258, (4, 257)),
 }
 
 
