@@ -1,10 +1,11 @@
 // Device-level building blocks that more than one file uses: the merge loop's (pairs.hip / correct.hip), the steps
-// upstream of the engine (prepca.hip) and the legacy natives (legacy.hip).  Unless a section says otherwise all pointers
+// upstream of the engine (prepca.hip) and the classic mnnCorrect natives (sgk.hip, asv.hip).  Unless a section says otherwise all pointers
 // are device pointers, all matrices row-major [cells x d] FP64, and all launches go to `stream`.  The handles that keep
 // batches resident (pca.hip, cluster_mnn.hip, linear_correct.hip, multi_batch_norm.hip, delta_variance.hip) hold their
 // own classes and C entry points and declare nothing here.
 #pragma once
 #include <functional>
+#include "asv_plan.hpp"
 #include "bmx_common.hpp"
 
 namespace bmx {
@@ -171,22 +172,14 @@ constexpr int PCA_SPARSE_ROW_SEGMENT = 256;  // stored entries of a gene row one
 constexpr int DELTA_PAIR_CHUNK = 128;  // pairs of one step a workgroup walks (fixed: the results do not depend on the grid)
 constexpr int GENEVAR_GENE_TILE = 2048;  // genes a workgroup of the CSC gene-variance kernel owns (gene_var.hip)
 
-// ---- legacy natives (legacy.hip) -------------------------------------------------------------------
+// ---- the classic mnnCorrect natives: smooth_gaussian_kernel (sgk.hip), adjust_shift_variance (asv.hip) -------------
 void smooth_gaussian_kernel_device(hipStream_t stream, const double* averaged, int g, int U, const int32_t* index,
                                    const double* mat, int gd, int n, double sigma2, double* out, double* ws_density);
-// What a call of these sizes runs and needs -- a pure function of its arguments (and of the testing hook "asv_fast"):
-// the caller reserves main_doubles + extra_doubles of scratch and hands the same plan to the launch.
-struct AsvPlan {
-    int exact = 1;   // 1: asv_exact_kernel (the reference's order of operations literally), 0: the tiled FP64-MFMA form
-    int wide = 0;    // 1 (with exact = 0): the literal wide form -- pair values in LDS-tiled passes, then the exact per-cell phase
-    int chunk = 0;   // wide form: cells whose pair values sit in scratch at once
-    int blocks = 1;  // workgroups
-    int npad = 1;    // exact form: nr1 rounded up to a power of two
-    int lcap = 0;    // tiled form: addends a chain of the literal re-run of a flagged cell may keep (0: no re-run)
-    size_t main_doubles = 0, extra_doubles = 0;
-};
+// What a call of these sizes runs and needs (AsvPlan, asv_plan.hpp) -- a pure function of its arguments and of the testing
+// hooks "asv_fast" / "asv_wide" / "asv_chunk" / "asv_cap", which this wrapper reads (plan_adjust_shift_variance is the
+// function itself): the caller reserves main_doubles + extra_doubles of scratch and hands the same plan to the launch.
 AsvPlan adjust_shift_variance_plan(int g, int n2, int nr1, int nr2, int vect_row_major);
-// counters of the tiled form on the current device: {cells re-run literally, flagged cells beyond lcap, all cells}
+// (asv_tile.hip) counters of the tiled form on the current device: {cells re-run literally, flagged cells beyond lcap, all cells}
 void asv_tally_read(unsigned long long out[3], bool reset);
 void asv_ticks_read(unsigned long long out[8]);  // diagnostics: 100 MHz ticks in the stream / at the round barrier / per-cell phase / -; literal cells: selection + re-evaluation, chains, kept addends, tiles
 void asv_modes_read(unsigned char* dst, size_t n);  // testing hook "asv_modes": the way each cell of the last call went

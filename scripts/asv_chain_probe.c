@@ -8,7 +8,7 @@
 
 #define LN2 0.6931471805599453
 
-/* may an addend lw be left out when the running sum is known to lie in [L, U]?  (see legacy.hip: asv_skippable) */
+/* may an addend lw be left out when the running sum is known to lie in [L, U]?  (see asv_tile.hip: asv_noop_below) */
 static int skippable(double lw, double L, double U) {
     if (lw < L - 701.0) return 1; /* exp(lw - acc) is 0 in the portable exp (cut at -700): log1p(0) = 0 */
     if (!((L > 0.0 && U > 0.0) || (L < 0.0 && U < 0.0))) return 0;

@@ -249,7 +249,7 @@ def test_full_size_config5_pairs_of_sampled_cells_match_oracle(oracle, full5, m)
 @pytest.mark.parametrize("sigma", [1.0, 0.1])
 def test_full_size_config5_with_variance_adjustment(oracle, full5, sigma):
     """BASELINE.json configs[4] as named, on one GPU: the full 16-batch tree WITH adjust_shift_variance on (6e11 cell pairs
-    per run; the tiled FP64-MFMA form of legacy.hip), at the bench's bandwidth and at mnnCorrect's default.  The oracle cannot
+    per run; the tiled FP64-MFMA form of asv_tile.hip), at the bench's bandwidth and at mnnCorrect's default.  The oracle cannot
     run the tree at this size, but it can run CELLS of it: the root merge's adjust_shift_variance call -- the largest of the
     run, two eight-batch subtrees -- is snapshotted and 192 sampled right cells go through the oracle on the same inputs
     (src/adjust_shift_variance.cpp:51: the loop treats every cell on its own).  Also: the run finishes, every coordinate is

@@ -110,7 +110,7 @@ def test_mnn_correct_restriction_identical(args):
 def test_mnn_correct_raw_output_var_adj():
     """cos.norm.out=FALSE with var.adj: the output genes keep their raw scale, adjust_shift_variance's weights are then
     concentrated on one or two cells and its quantile walk turns on the last bits of the smoothed correction vectors
-    (legacy.hip's header; tests/testthat/test-mnn-correct.R:141 upstream).  Measured on these inputs: last-bit noise in the
+    (asv.hip's header; tests/testthat/test-mnn-correct.R:141 upstream).  Measured on these inputs: last-bit noise in the
     restatement's own correction vectors moves 303 of the 600 cells, the device differs from it in 299 -- so only the pairs
     are held here; the same path without var.adj is held to 1e-5 in test_mnn_correct_matches_restatement."""
     B = _batches(2 * 7 + 10, [100, 200, 300], 10)

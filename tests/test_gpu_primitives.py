@@ -234,6 +234,56 @@ def test_adjust_shift_variance_tiled_form_edges(oracle, nat, dev, sigma):
     assert np.isnan(out[17]) and np.isnan(ref[17])                  # 0 / 0, as the reference (:160)
 
 
+def _asv_edges_data(g):
+    """The data of test_adjust_shift_variance_tiled_form_edges at g dimensions."""
+    rng = np.random.default_rng(100033)
+    d1 = rng.standard_normal((g, 1237)) / np.sqrt(1.0 + np.arange(g) / 5.0)[:, None]
+    d2 = rng.standard_normal((g, 1003)) / np.sqrt(1.0 + np.arange(g) / 5.0)[:, None] + 0.3
+    cv = rng.standard_normal((1003, g)) * 0.2
+    cv[17] = 0.0
+    r1 = np.concatenate([rng.permutation(1237)[:901], rng.integers(0, 1237, 40)])
+    r2 = np.concatenate([rng.permutation(1003)[:777], rng.integers(0, 1003, 60)])
+    return d1, d2, cv, r1, r2
+
+
+@pytest.mark.parametrize("g", [62, 63, 126, 127, 200, 256])
+@pytest.mark.parametrize("sigma", [1.0, 0.05])
+def test_adjust_shift_variance_tiled_form_every_stream_form(oracle, nat, dev, g, sigma):
+    """The three shapes of the tile kernel's stream (csrc/asv_tile.hip) at their boundaries, on the data and with the
+    criterion of test_adjust_shift_variance_tiled_form_edges: a streamed row of g + 2 columns in 8-dimension blocks held
+    in registers (62 dimensions: 8 blocks), with the cells' operands parked in the LDS (63: 9 blocks, 126: 16), and the
+    LDS-staged form (127, 200, 256 dimensions: its first, a middle and its last width)."""
+    dev("asv_fast", 1)
+    d1, d2, cv, r1, r2 = _asv_edges_data(g)
+    out = nat.adjust_shift_variance(d1, d2, cv, sigma, r1, r2)
+    ref = oracle.adjust_shift_variance(d1, d2, cv, sigma, r1, r2)
+    close = np.isclose(out, ref, rtol=1e-8, atol=1e-12, equal_nan=True)
+    print(f"g {g} sigma {sigma}: {close.mean():.6f} of 1003 cells equal to the oracle")
+    assert close.mean() >= 0.999, (g, sigma, close.mean())
+    assert np.isnan(out[17]) and np.isnan(ref[17])                  # 0 / 0, as the reference (:160)
+
+
+@pytest.mark.parametrize("cap", [64, 0])
+def test_adjust_shift_variance_staged_form_beyond_the_rerun(nat, dev, cap):
+    """The LDS-staged stream (200 dimensions) with a re-run of at most 64 addends per chain -- a flagged cell that keeps more
+    goes the histogram way -- and with no re-run at all: finite, reproducible, and the tallies say which way the cells went
+    (as test_adjust_shift_variance_tiled_form_beyond_the_rerun has it at 100 dimensions; no share is pinned here)."""
+    from batchelor_amd import _lib
+    dev("asv_fast", 1)
+    dev("asv_cap", cap)
+    rng = np.random.default_rng(100036)
+    a = rng.standard_normal((200, 1237)) / np.sqrt(1.0 + np.arange(200) / 5.0)[:, None]
+    b = rng.standard_normal((200, 1003)) / np.sqrt(1.0 + np.arange(200) / 5.0)[:, None] + 0.3
+    v = rng.standard_normal((1003, 200)) * 0.2
+    r1, r2 = np.arange(1237), np.arange(1003)
+    _lib.dev_get("asv_tally_reset")
+    out = nat.adjust_shift_variance(a, b, v, 0.3, r1, r2)
+    lit, back = _lib.dev_get("asv_literal_cells"), _lib.dev_get("asv_fallback_cells")
+    assert np.all(np.isfinite(out))
+    assert np.array_equal(out, nat.adjust_shift_variance(a, b, v, 0.3, r1, r2))
+    assert (lit == 0) if cap == 0 else (lit + back > 0)
+
+
 @pytest.mark.parametrize("sigma", [1.0, 0.05])
 def test_adjust_shift_variance_tiled_form_tiny_and_empty(oracle, nat, dev, sigma):
     # the tiled form's smallest inputs: an empty restrict2 (prob2 keeps its starting value 0, :76), one and three reference

@@ -1,4 +1,4 @@
-"""CPU check of the lemma the tiled adjust_shift_variance's literal re-run rests on (batchelor_amd/csrc/legacy.hip, in front of
+"""CPU check of the lemma the tiled adjust_shift_variance's literal re-run rests on (batchelor_amd/csrc/asv_tile.hip, in front of
 asv_noop_below): an addend far enough below a logspace_add chain's running value is an exact no-op, so
 the chain over the addends that are NOT provably no-ops -- bounds taken from the largest addend so far, the count, and, once
 the cell's own weight 1 has gone by, the largest other weight -- has the bits of the full chain
