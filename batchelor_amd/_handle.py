@@ -1,5 +1,5 @@
 """The Python side of a library handle that keeps genes x cells batches in HBM, dense (bmx_pca_t, bmx_cluster_t,
-bmx_linear_t, bmx_norm_t) or as CSC (bmx_pca_sparse_t, bmx_norm_sparse_t), or that streams them through block buffers
+bmx_linear_t, bmx_norm_t, bmx_delta_t) or as CSC (bmx_pca_sparse_t, bmx_norm_sparse_t, bmx_delta_sparse_t), or that streams them through block buffers
 (bmx_genevar_t, bmx_genevar_sparse_t)."""
 from __future__ import annotations
 

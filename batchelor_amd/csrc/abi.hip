@@ -1,6 +1,6 @@
 // extern "C" boundary of libbatchelor_mi355x.so (declared in include/batchelor_mi355x.h): the engine, the one-shot
 // primitives, the legacy natives and mnnCorrect.  The entry points of the handles that keep batches resident (bmx_pca_*,
-// bmx_cluster_*, bmx_linear_*, bmx_norm_*, bmx_norm_sparse_*, bmx_delta_*) or stream them through block buffers
+// bmx_cluster_*, bmx_linear_*, bmx_norm_*, bmx_norm_sparse_*, bmx_delta_*, bmx_delta_sparse_*) or stream them through block buffers
 // (bmx_genevar_*, bmx_genevar_sparse_*) stand at the end of their classes' files.
 // Nothing throws across the boundary: exceptions become return codes + a thread-local message (guarded, defined here).
 #include <algorithm>
@@ -236,6 +236,8 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = (int64_t)t[n == "asv_ticks_literal" ? 4 : (n == "asv_ticks_chains" ? 5 : (n == "asv_literal_addends" ? 6 : 7))];
         } else if (n == "delta_gene_tile" || n == "delta_pair_chunk") {
             *value = n == "delta_gene_tile" ? bmx::DELTA_GENE_TILE : bmx::DELTA_PAIR_CHUNK;
+        } else if (n == "delta_sparse_gene_tile") {
+            *value = bmx::DELTA_SPARSE_GENE_TILE;
         } else if (n == "genevar_gene_tile" || n == "genevar_chunk") {
             *value = n == "genevar_gene_tile" ? bmx::GENEVAR_GENE_TILE : bmx::GENEVAR_CHUNK;
         } else if (n == "pca_sparse_row_segment") {

@@ -170,6 +170,7 @@ void cosnorm_project_device(hipStream_t stream, const double* x, int G, int n, c
 constexpr int DELTA_GENE_TILE = 256;   // genes a workgroup of the pair passes owns
 constexpr int PCA_SPARSE_ROW_SEGMENT = 256;  // stored entries of a gene row one wave of the sparse PCA's by-gene pass adds
 constexpr int DELTA_PAIR_CHUNK = 128;  // pairs of one step a workgroup walks (fixed: the results do not depend on the grid)
+constexpr int DELTA_SPARSE_GENE_TILE = 256;  // genes a one-wave workgroup of the CSC handle's pair passes owns
 constexpr int GENEVAR_GENE_TILE = 2048;  // genes a workgroup of the CSC gene-variance kernel owns (gene_var.hip)
 
 // ---- the classic mnnCorrect natives: smooth_gaussian_kernel (sgk.hip), adjust_shift_variance (asv.hip) -------------

@@ -1,5 +1,6 @@
 // Device helpers of the kernels that read a batch kept as CSC (indptr absolute, rows ascending within a column): NormSparse
-// (multi_batch_norm.hip), PcaSparse (pca_sparse.hip) and GeneVarSparse (gene_var.hip, over one block at a time).  The store and the host's checks are in resident_batches.hpp.
+// (multi_batch_norm.hip), PcaSparse (pca_sparse.hip), DeltaSparse (delta_variance.hip: two arbitrary columns per pair, one
+// wave a tile) and GeneVarSparse (gene_var.hip, over one block at a time).  The store and the host's checks are in resident_batches.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,24 @@ template <int CELLS, class Entry>
 __device__ __forceinline__ void csc_tile_walk(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int64_t n,
                                               int64_t chunk, int g0, int g1, int64_t* lo, int64_t* hi, Entry&& entry) {
     csc_tile_walk<CELLS>(indptr, idx, n, chunk, g0, g1, lo, hi, [](int64_t) {}, entry);
+}
+
+// A column whose address came out of memory (DeltaSparse's pair records): say that it is global memory, or the loads are
+// flat ones.
+typedef const __attribute__((address_space(1))) int32_t* csc_rows_ptr;
+typedef const __attribute__((address_space(1))) double* csc_vals_ptr;
+
+// ONE wave takes the n entries at idx / val -- a column's entries inside the rows [g0, g1) -- lane l the entries l,
+// l + 64, ...  The lane's first entry comes in as r0 / v0: the caller loads it, with other columns' loads in flight
+// (r0 < 0: the lane has none).  entry(r - g0, value); on any pattern r stays inside [g0, g1).
+template <class Entry>
+__device__ __forceinline__ void csc_wave_walk(csc_rows_ptr idx, csc_vals_ptr val, int n, int lane, int g0, int g1, int r0,
+                                              double v0, Entry&& entry) {
+    if (r0 >= g0 && r0 < g1) entry(r0 - g0, v0);
+    for (int k = lane + 64; k < n; k += 64) {
+        const int r = idx[k];
+        if (r >= g0 && r < g1) entry(r - g0, val[k]);
+    }
 }
 
 }  // namespace bmx

@@ -5,10 +5,14 @@ hot path is a gather -- every pair reads two whole gene vectors -- so the batche
 statistics of all steps come back in one download (csrc/delta_variance.hip, bmx_delta_*).  The host keeps what needs no
 device: the validation of the pairs, the subset.row / compute.all bookkeeping, the trend and the combination over steps.
 
+The batches are all dense or all scipy.sparse (any format, matrix or array: what multiBatchNorm returns for sparse counts
+goes straight in).  Sparse ones are made canonical CSC on the host and stay CSC in HBM (bmx_delta_sparse_*): the pair
+passes walk the stored entries only, as R/mnnDeltaVariance.R:185-201 does over SVT_SparseMatrix blocks.
+
 scran::fitTrendVar is third-party code outside the reference and is not re-implemented: `trend_fit` takes its place.
 
-Out of scope (a clear error): sparse and SingleCellExperiment inputs; batches that do not fit in free HBM (restrict the
-genes with `subset_row`: there is no streaming by gene block).
+Out of scope (a clear error): SingleCellExperiment inputs; a mixture of sparse and dense batches; batches that do not
+fit in free HBM, dense or as CSC (restrict the genes with `subset_row`: there is no streaming by gene block).
 """
 from __future__ import annotations
 
@@ -17,13 +21,16 @@ from dataclasses import dataclass
 from typing import Callable, List, NamedTuple, Optional
 
 import numpy as np
+import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import check_same_dim, check_unique_names, subset_index
+from .inputs import (all_sparse, canonical_csc, check_same_dim, check_same_rows, check_unique_names, csc_block_width,
+                     subset_index, unpack_batches)
 from .linear_correct import _as_matrices, _rows  # (_as_matrices: inputs.unpack_batches + the sparse / SCE refusals)
 
 BLOCK_BYTES = 1 << 28  # a batch above this size goes to the device in column blocks of about this many bytes
+SPARSE_BLOCK_CELLS = None  # cells per uploaded block of a CSC batch; None: about BLOCK_BYTES of stored entries
 STAGES = ("upload", "norms", "pair_passes", "reductions", "run_wall")
 FIELDS = ("mean", "total", "trend", "adjusted")
 
@@ -31,6 +38,11 @@ FIELDS = ("mean", "total", "trend", "adjusted")
 def gene_tile():
     """Genes a workgroup of the pair passes owns (bmx_dev_get "delta_gene_tile"; needs no device)."""
     return _lib.dev_get("delta_gene_tile")
+
+
+def sparse_gene_tile():
+    """Genes a workgroup of the CSC handle's pair passes owns (bmx_dev_get "delta_sparse_gene_tile"; needs no device)."""
+    return _lib.dev_get("delta_sparse_gene_tile")
 
 
 def pair_chunk():
@@ -181,19 +193,35 @@ class _DeltaHandle(ResidentHandle):
         mean = np.empty((self.G, S), dtype=np.float64, order="F")
         total = np.empty((self.G, S), dtype=np.float64, order="F")
         ng = 0 if norm_genes0 is None else int(norm_genes0.size)
-        _lib.check(_lib.lib().bmx_delta_run(self._h, ctypes.c_int32(int(bool(cos_norm))),
-                                            None if norm_genes0 is None else _lib.i32p(norm_genes0), ctypes.c_int32(ng),
-                                            ctypes.c_int32(S), lp, rp, counts.ctypes.data_as(_lib.c_i64p),
-                                            _lib.f64p(mean), _lib.f64p(total)))
+        self._call("run", ctypes.c_int32(int(bool(cos_norm))), None if norm_genes0 is None else _lib.i32p(norm_genes0),
+                   ctypes.c_int32(ng), ctypes.c_int32(S), lp, rp, counts.ctypes.data_as(_lib.c_i64p), _lib.f64p(mean),
+                   _lib.f64p(total))
         return mean, total
 
 
+class _DeltaSparseHandle(_DeltaHandle):
+    """bmx_delta_sparse_t: the same over canonical CSC batches (inputs.canonical_csc), kept CSC in HBM."""
+    PREFIX = "bmx_delta_sparse"
+
+    def add_batch(self, c, block_cells=None):
+        if block_cells is None:
+            block_cells = SPARSE_BLOCK_CELLS
+        self._upload_csc(c, csc_block_width(c, BLOCK_BYTES) if block_cells is None else max(1, int(block_cells)))
+
+
+def csc_batches(mats, rows=None):
+    """scipy.sparse batches as canonical CSC; `rows` (1-based, in any order) are taken from each on the host and the result
+    is made canonical again."""
+    out = [canonical_csc(m)[0] for m in mats]
+    return out if rows is None else [canonical_csc(c[np.asarray(rows, dtype=np.int64) - 1])[0] for c in out]
+
+
 def device_statistics(mats, steps, cos_norm=False, norm_genes0=None, device=0):
-    """The device's part of a call: `mats` genes x cells matrices with the same rows, `steps` what check_pairs() returns.
-    Returns mean and total, [genes x steps] each, as the kernels leave them (a step with one pair still has its mean), and
-    the stage times."""
+    """The device's part of a call: `mats` genes x cells matrices with the same rows -- all numpy arrays, or all canonical
+    CSC (csc_batches) --, `steps` what check_pairs() returns.  Returns mean and total, [genes x steps] each, as the kernels
+    leave them (a step with one pair still has its mean), and the stage times."""
     _lib.require_gpu()
-    h = _DeltaHandle(mats[0].shape[0], device)
+    h = (_DeltaSparseHandle if sp.issparse(mats[0]) else _DeltaHandle)(mats[0].shape[0], device)
     try:
         for m in mats:
             h.add_batch(m)
@@ -207,7 +235,8 @@ def mnnDeltaVariance(*batches, pairs=None, cos_norm=False, subset_row=None, comp
                      trend_fit: Optional[Callable] = None, names=None, device=0) -> MnnDeltaVarianceResult:
     """mnnDeltaVariance(..., pairs=, cos.norm=, subset.row=, compute.all=) (R/mnnDeltaVariance.R:95-201).
 
-    Each batch is genes x cells of (uncorrected) log-expression values.  `pairs` is one (left, right) pair of equal-length
+    Each batch is genes x cells of (uncorrected) log-expression values; the batches are all dense or all scipy.sparse
+    (implicit zeros are zeros: sparse logcounts as multiBatchNorm returns them).  `pairs` is one (left, right) pair of equal-length
     1-based index vectors or a list of them, one entry per merge step, over the cells of the batches side by side in the
     order given: what fastMNN(...).merge_info.pairs and mnnCorrect(...).merge_info.pairs hold.  Per step, `total` is the
     variance of x[, left] - x[, right] across the pairs and `mean` the mean of the two cells' means; the steps are
@@ -216,10 +245,11 @@ def mnnDeltaVariance(*batches, pairs=None, cos_norm=False, subset_row=None, comp
     `trend_fit` stands in for scran::fitTrendVar, which is not re-implemented: a callable (mean, total) -> callable(mean)
     -> trend, applied per step (on the `subset_row` genes when `compute_all` is set).  Without it `trend` and `adjusted`
     are None.  `names` plays the role of the argument names of `...`."""
-    mats = _as_matrices(batches, "mnnDeltaVariance")
+    sparse = all_sparse(unpack_batches(batches), "mnnDeltaVariance")
+    mats = list(unpack_batches(batches)) if sparse else _as_matrices(batches, "mnnDeltaVariance")
     if len(mats) == 0:
         raise ValueError("at least one batch must be specified")
-    G = check_same_dim(mats, byrow=False)
+    G = check_same_rows(mats) if sparse else check_same_dim(mats, byrow=False)
     if names is not None:
         names = [str(v) for v in names]
         if len(names) != len(mats):
@@ -229,7 +259,8 @@ def mnnDeltaVariance(*batches, pairs=None, cos_norm=False, subset_row=None, comp
     plan = plan_genes(subset_row, compute_all, G)
     if trend_fit is not None and not callable(trend_fit):
         raise ValueError("'trend_fit' must be callable")
-    mean, total, stage_ms = device_statistics(_rows(mats, plan.rows), steps, cos_norm, plan.norm_genes0, device)
+    mats = csc_batches(mats, plan.rows) if sparse else _rows(mats, plan.rows)
+    mean, total, stage_ms = device_statistics(mats, steps, cos_norm, plan.norm_genes0, device)
     npairs = np.asarray([l.size for l, _ in steps], dtype=np.int64)
     tables = [step_table(np.ascontiguousarray(mean[:, i]), np.ascontiguousarray(total[:, i]), int(npairs[i]), trend_fit,
                          plan.fit_rows0) for i in range(len(steps))]

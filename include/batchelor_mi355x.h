@@ -118,7 +118,7 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * phase), "asv_ticks_literal" / "asv_ticks_chains" (the re-run cells' selection + re-evaluation + sort, their chains and walks),
  * "asv_literal_addends" (addends the re-run cells kept), "asv_chain_tiles" (tiles with a re-run cell).  Waits for the device.
  * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
- * owns, pairs of a step it walks), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
+ * owns, pairs of a step it walks), "delta_sparse_gene_tile" (genes a workgroup of bmx_delta_sparse_run's owns), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
  * genes a workgroup of the sparse one owns). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
@@ -675,6 +675,30 @@ int32_t bmx_delta_run(bmx_delta_t* h, int32_t cos_norm, const int32_t* norm_gene
  * time of out[1] the cell norms, out[2] the two pair passes (the gather), out[3] the pair preparation and the reductions
  * over chunks; out[4] = host wall time of bmx_delta_run. */
 int32_t bmx_delta_stage_ms(const bmx_delta_t* h, double* out5);
+
+/* The same over batches kept in HBM as CSC, what R/mnnDeltaVariance.R:185-201 does over SVT_SparseMatrix blocks: per batch
+ * indptr [n + 1] (int64), 0-based int32 row indices strictly ascending within a column and FP64 values (explicit zeros
+ * are values like any other).  A batch is announced with its cells and its stored entries and filled in column blocks
+ * (per block: indptr [n_block + 1] relative to the block -- starts at 0, never decreases, ends at nnz; indices and data
+ * may be NULL only when nnz is 0).  Pairs, chunks, outputs and stage times are those of bmx_delta_t.  The sums of a chunk
+ * take the stored entries in pair order -- the dense handle's sums with their terms of +0 left out -- so without
+ * cos_norm `mean` equals the dense handle's bit for bit; a pair's two entries of a gene are combined before they are
+ * squared, and the pairs of a chunk where neither cell stores the gene enter `total` as (pairs - touched) * m * m, m the
+ * step's mean delta.  The same input gives the same bits on every run, for every block width, and for a step alone or
+ * among others.  Every stored entry is checked on the device behind its upload, and bmx_delta_sparse_run refuses with
+ * BMX_ERR_ARG before its pair passes start: "a row index is outside [0, number of genes)", "the row indices of a column
+ * should be strictly ascending", "values should be finite".  The genes are tiled by bmx_dev_get "delta_sparse_gene_tile"
+ * (no device needed).  A batch that does not fit in free HBM is refused as by bmx_delta_begin_batch. */
+typedef struct bmx_delta_sparse bmx_delta_sparse_t;
+int32_t bmx_delta_sparse_create(int32_t device, int32_t n_genes, bmx_delta_sparse_t** out);
+void bmx_delta_sparse_destroy(bmx_delta_sparse_t* h);
+int32_t bmx_delta_sparse_begin_batch(bmx_delta_sparse_t* h, int64_t n, int64_t nnz);
+int32_t bmx_delta_sparse_add_block(bmx_delta_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                   const double* data, int64_t nnz);
+int32_t bmx_delta_sparse_run(bmx_delta_sparse_t* h, int32_t cos_norm, const int32_t* norm_genes0, int32_t n_norm_genes,
+                             int32_t nsteps, const int32_t* const* left, const int32_t* const* right, const int64_t* npairs,
+                             double* mean, double* total);
+int32_t bmx_delta_sparse_stage_ms(const bmx_delta_sparse_t* h, double* out5);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Per-batch, per-gene mean and variance: what scran::modelGeneVar() takes from its input before any trend, and what

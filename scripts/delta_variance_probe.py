@@ -4,8 +4,15 @@ they must move (2 P G 8 per pass and step), what share of the HBM rate that is, 
 (--ref) the numpy restatement (tests/delta_variance_ref.py) on the same input, gene block by gene block as the reference
 walks its rowAutoGrid, on --threads host threads.
 
+--sparse DENSITY [DENSITY ...]: the same workload and pairs with every entry kept with that probability, through three
+paths that alternate after a warm-up of each, in this process: (a) the batches as scipy.sparse CSC through the sparse
+handle; (b) the same CSC batches densified on the host (`.toarray()`) and given to the dense handle -- the only route for
+such data before the sparse handle existed; (c) the dense handle on batches that are dense already.  Per path the
+host-to-host times and the HIP-event time of the pair passes; for (a) the bytes its passes must move, counted from the
+pairs' column lengths at 12 bytes per stored entry and pass.
+
     python scripts/delta_variance_probe.py [--cells 100000] [--batches 4] [--genes 2000] [--reps 4] [--cos-norm] [--ref]
-                                           [--threads 16]
+                                           [--threads 16] [--sparse 0.05 0.2]
 """
 import argparse
 import os
@@ -58,6 +65,71 @@ def restatement_by_gene_block(batches, pairs, threads, block=50):
     return mean, total
 
 
+def sparse_paths(batches, pairs, density, reps, seed=1):
+    """The three paths at one density; prints what the module docstring lists."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    t0 = time.perf_counter()
+    csc, nnz_col = [], []
+    for x in batches:
+        c = sp.csc_matrix(np.where(rng.random(x.shape) < density, x, 0.0))
+        csc.append(c)
+        nnz_col.append(np.diff(c.indptr))
+    kept = [c.toarray(order="F") for c in csc]                       # path (c)'s input: dense already
+    nnz_col = np.concatenate(nnz_col).astype(np.int64)
+    stored = int(nnz_col.sum())
+    print(f"--- density {density}: {stored} stored entries of {sum(x.size for x in batches)} "
+          f"({12.0 * stored / 1e9:.2f} GB as CSC, {8.0 * sum(x.size for x in batches) / 1e9:.2f} GB dense); made in "
+          f"{time.perf_counter() - t0:.0f} s", flush=True)
+    entries = sum(int(nnz_col[np.asarray(l) - 1].sum() + nnz_col[np.asarray(r) - 1].sum()) for l, r in pairs)
+    nbytes = 2 * 12.0 * entries                                      # two passes
+
+    def path_a():
+        return bx.mnnDeltaVariance(*csc, pairs=pairs)
+
+    def path_b():
+        return bx.mnnDeltaVariance(*[c.toarray(order="F") for c in csc], pairs=pairs)
+
+    def path_c():
+        return bx.mnnDeltaVariance(*kept, pairs=pairs)
+
+    paths = (("a: sparse handle", path_a), ("b: toarray() + dense handle", path_b), ("c: dense handle, dense input", path_c))
+    wall = {name: [] for name, _ in paths}
+    passes = {name: [] for name, _ in paths}
+    last = {}
+    for rep in range(reps + 1):                                      # round 0 warms every path up
+        for name, fn in paths:
+            t0 = time.perf_counter()
+            out = fn()
+            t = time.perf_counter() - t0
+            st = out.stats["stage_ms"]
+            print(f"round {rep} {name}: host to host {t * 1e3:.0f} ms; " + ", ".join(f"{k} {v:.2f}" for k, v in st.items()),
+                  flush=True)
+            if rep > 0:
+                wall[name].append(t)
+                passes[name].append(st["pair_passes"] * 1e-3)
+            last[name] = out
+    a, b, c = (name for name, _ in paths)
+    for name in (a, b, c):
+        w = np.asarray(wall[name]) * 1e3
+        print(f"{name}: host to host median {np.median(w):.0f} ms, fastest {w.min():.0f} ms, spread {w.max() - w.min():.0f} ms; "
+              f"pair passes fastest {min(passes[name]) * 1e3:.2f} ms", flush=True)
+    ka = min(passes[a])
+    print(f"(a) pair passes: {ka * 1e3:.2f} ms for {nbytes / 1e9:.3f} GB that must move ({entries} entries of the pairs' columns "
+          f"x 12 bytes x 2 passes) = {nbytes / ka / 1e12:.3f} TB/s = {nbytes / ka / COPY_BW:.1%} of the plain-copy figure",
+          flush=True)
+    print(f"kernel-level ratio (a) / (c), pair passes: {ka / min(passes[c]):.2f}", flush=True)
+    gain = np.median(wall[b]) - np.median(wall[a])
+    spread = max(wall[b]) - min(wall[b])
+    print(f"acceptance at this density: (a) is faster than (b) host to host by {gain * 1e3:.0f} ms (medians), the spread of (b) "
+          f"is {spread * 1e3:.0f} ms: {'met' if gain > spread else 'NOT met'}; slowest (a) {max(wall[a]) * 1e3:.0f} ms, fastest "
+          f"(b) {min(wall[b]) * 1e3:.0f} ms", flush=True)
+    sa, sc = last[a], last[c]
+    rel = max(float((np.abs(ta.total - tc.total) / tc.total).max()) for ta, tc in zip(sa.per_step, sc.per_step))
+    print(f"(a) against (c): means bitwise equal {all(np.array_equal(ta.mean, tc.mean) for ta, tc in zip(sa.per_step, sc.per_step))}, "
+          f"max rel diff of the totals {rel:.2e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", type=int, default=100000)
@@ -67,6 +139,7 @@ def main():
     ap.add_argument("--cos-norm", action="store_true")
     ap.add_argument("--ref", action="store_true")
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--sparse", type=float, nargs="+", default=[], metavar="DENSITY")
     a = ap.parse_args()
     G, n, B = a.genes, a.cells, a.batches
     _lib.require_gpu()
@@ -111,6 +184,11 @@ def main():
         print(f"restatement (numpy, {a.threads} threads over gene blocks): {t:.1f} s = {t / best_wall:.0f} x the device call "
               f"host to host, {t / best_kernel:.0f} x the pair passes; max abs diff of the means {dm:.2e}, max rel diff of the "
               f"totals {dt:.2e}", flush=True)
+
+    for density in a.sparse:
+        if a.cos_norm:
+            raise SystemExit("--sparse compares the pair statistics: run it without --cos-norm")
+        sparse_paths(batches, pairs, density, max(1, a.reps - 1))
 
 
 if __name__ == "__main__":
