@@ -1,5 +1,6 @@
 """The Python side of a library handle that keeps genes x cells batches in HBM, dense (bmx_pca_t, bmx_cluster_t,
-bmx_linear_t, bmx_norm_t, bmx_delta_t) or as CSC (bmx_pca_sparse_t, bmx_norm_sparse_t, bmx_delta_sparse_t), or that streams them through block buffers
+bmx_linear_t, bmx_norm_t, bmx_delta_t) or as CSC (bmx_pca_sparse_t, bmx_norm_sparse_t, bmx_delta_sparse_t,
+bmx_cluster_sparse_t), or that streams them through block buffers
 (bmx_genevar_t, bmx_genevar_sparse_t)."""
 from __future__ import annotations
 
@@ -56,11 +57,13 @@ class ResidentHandle:
             self._call("add_block", _lib.f64p(xb), ctypes.c_int64(xb.shape[1]))
         self.ncells.append(n)
 
-    def _upload_csc(self, c, per, *begin_args):
-        """c: canonical CSC (inputs.canonical_csc), announced with begin_batch(n, *begin_args, nnz); it goes over in
-        column blocks of `per` cells."""
+    def _upload_csc(self, c, per, *begin_args, nnz_first=False):
+        """c: canonical CSC (inputs.canonical_csc), announced with begin_batch(n, *begin_args, nnz) -- nnz_first:
+        begin_batch(n, nnz, *begin_args), as bmx_cluster_sparse_begin_batch takes it --; it goes over in column blocks of
+        `per` cells."""
         n = int(c.shape[1])
-        self._call("begin_batch", ctypes.c_int64(n), *begin_args, ctypes.c_int64(int(c.nnz)))
+        nnz = ctypes.c_int64(int(c.nnz))
+        self._call("begin_batch", ctypes.c_int64(n), *((nnz, *begin_args) if nnz_first else (*begin_args, nnz)))
         self.ncells.append(n)
         for block in csc_blocks(c, per):
             self._add_csc_block(*block)

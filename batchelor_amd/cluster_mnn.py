@@ -11,8 +11,16 @@ of the raw batch, its own PCA to `cluster_d` components (the single-batch Device
 iteration cannot take the shape), then kmeans() on the device (csrc/kmeans.hip).  The labels then go the way labels
 given by the caller go.  A batch is uploaded once for that PCA and once more for bmx_cluster_*.
 
+The batches are all dense or all scipy.sparse (any format, matrix or array: what multiBatchNorm returns for sparse counts
+goes straight in).  Sparse ones are made canonical CSC on the host and stay CSC in HBM (bmx_cluster_sparse_*): both
+streaming passes walk the stored entries only, and everything after them -- the centroids' PCA, the merge, the nearest
+centroid, the median, the smoothing -- is the dense call's, so the result is the dense call's: dense cells x d.  Under
+`clusters=KmeansParam(...)` a sparse batch's PCs come from a one-batch DeviceSparsePCA over its `subset_row` rows; where
+that handle cannot take the shape, and with cluster_d=None (kmeans takes dense observations), those rows are made dense
+on the host, which is refused above multi_batch_pca.DENSIFY_CAP_BYTES.
+
 Out of scope (a clear error): bluster methods other than k-means (NNGraphParam and the rest), more than 257 clusters in
-total (the merge engine takes at most 256 columns), SingleCellExperiment inputs.
+total (the merge engine takes at most 256 columns), SingleCellExperiment inputs, a mixture of sparse and dense batches.
 """
 from __future__ import annotations
 
@@ -22,16 +30,19 @@ from dataclasses import dataclass
 from typing import Any, List, Optional
 
 import numpy as np
+import scipy.sparse as sp
 
 from . import _lib
 from ._handle import ResidentHandle
-from .inputs import check_restrict_length, check_same_dim, divide_into_batches, restrict_list, subset_index, unpack_batches
+from .inputs import (all_sparse, canonical_csc, check_restrict_length, check_same_dim, check_same_rows, csc_block_width,
+                     divide_into_batches, restrict_list, subset_index, unpack_batches)
 from .kmeans import MAX_CENTERS, KmeansParam, kmeans
-from .multi_batch_pca import DevicePCA, device_pca_takes
+from .multi_batch_pca import DevicePCA, DeviceSparsePCA, _csc_rows, densify, device_pca_takes
 from .reduced_mnn import reducedMNN
 
 MAX_DIMS = 256          # columns the merge engine takes (csrc/engine.hip)
 BLOCK_BYTES = 1 << 28   # a batch above this size goes to the device in column blocks of about this many bytes
+SPARSE_BLOCK_CELLS = None  # cells per uploaded block of a CSC batch; None: about BLOCK_BYTES of stored entries
 
 
 @dataclass
@@ -46,7 +57,8 @@ class ClusterMnnResult:
     sigma: np.ndarray          # per batch: the bandwidth of the smoothing
     cluster_info: dict         # columns "cluster", "batch", "meta", one row per centroid
     # "stage_ms": upload, centroids, projection, nearest_median, smoothing; "merge": per merge sizes; "clustering": None for
-    # labels given by the caller, else per batch what clustered it (path of the PCA, d, K, iter, converged, stage_ms)
+    # labels given by the caller, else per batch what clustered it (path of the PCA, d, K, iter, converged, stage_ms);
+    # "pca" of a sparse batch: "device-sparse-pca", or "densified: " + the dense path its subset rows then took
     stats: Optional[dict] = None
 
 
@@ -99,21 +111,42 @@ def _batch_pcs(m, d, device):
     return u[:, :d] * s[:d], "host-svd"
 
 
+def _sparse_batch_pcs(c, d, device):
+    """_batch_pcs for canonical CSC: a one-batch DeviceSparsePCA whose PCA rows are all of c's; where it cannot take the
+    shape, c is made dense (refused above DENSIFY_CAP_BYTES) and goes the dense way."""
+    if device_pca_takes(c.shape[0], c.shape[1], d):
+        pca = DeviceSparsePCA(c.shape[0], None, device)
+        try:
+            pca.add_batch(c, weight=1.0, cos_norm=False)
+            pca.fit(d=d)
+            return pca.project(0), "device-sparse-pca"
+        finally:
+            pca.close()
+    obs, path = _batch_pcs(densify([c], "clusterMNN")[0], d, device)
+    return obs, "densified: " + path
+
+
 def _cluster_batches(mats, sub, param, ks, cluster_d, device):
     """.format_clusters, the BlusterParam branch (R/clusterMNN.R:204-220): every batch's labels from kmeans() on its own
     PCs (or on its rows with cluster_d=None), the restriction ignored as in the reference."""
     labels, info = [], []
     for m, k in zip(mats, ks):
-        cur = np.asarray(m, dtype=np.float64)
-        if sub is not None:
-            cur = cur[sub - 1]
+        sparse = sp.issparse(m)
+        if sparse:
+            cur = _csc_rows(m, None if sub is None else sub.astype(np.int64) - 1)
+        else:
+            cur = np.asarray(m, dtype=np.float64)
+            if sub is not None:
+                cur = cur[sub - 1]
         d, path = cluster_d, "none"
         if d is not None:
             if d > min(cur.shape):
                 warnings.warn(f"'cluster_d' = {d} exceeds min(genes, cells) = {min(cur.shape)} of a batch: clamped",
                               stacklevel=4)
                 d = int(min(cur.shape))
-            obs, path = _batch_pcs(cur, int(d), device)
+            obs, path = (_sparse_batch_pcs if sparse else _batch_pcs)(cur, int(d), device)
+        elif sparse:
+            obs, path = np.ascontiguousarray(densify([cur], "clusterMNN")[0].T), "densified: none"
         else:
             obs = np.ascontiguousarray(cur.T)
         res = kmeans(obs, k, iter_max=param.iter_max, nstart=param.nstart, seed=param.seed, device=device)
@@ -219,7 +252,7 @@ class _ClusterHandle(ResidentHandle):
 
     def centroids(self, b):
         out = np.empty((self.G, self.nclusters[b]), dtype=np.float64, order="F")
-        _lib.check(_lib.lib().bmx_cluster_centroids(self._h, ctypes.c_int32(b), _lib.f64p(out)))
+        self._call("centroids", ctypes.c_int32(b), _lib.f64p(out))
         return out
 
     def propagate(self, b, rotation, centers, centroid_pcs, corrected_pcs):
@@ -233,18 +266,36 @@ class _ClusterHandle(ResidentHandle):
             raise ValueError("the centroids' coordinates must be (number of clusters) x d")
         out = np.empty((self.ncells[b], d), dtype=np.float64, order="F")
         sigma = ctypes.c_double(0.0)
-        _lib.check(_lib.lib().bmx_cluster_propagate(self._h, ctypes.c_int32(b), _lib.f64p(rotation), ctypes.c_int32(d),
-                                                    _lib.f64p(centers), _lib.f64p(cp), _lib.f64p(cc), _lib.f64p(out),
-                                                    ctypes.byref(sigma)))
+        self._call("propagate", ctypes.c_int32(b), _lib.f64p(rotation), ctypes.c_int32(d), _lib.f64p(centers), _lib.f64p(cp),
+                   _lib.f64p(cc), _lib.f64p(out), ctypes.byref(sigma))
         return out, float(sigma.value)
+
+
+class _ClusterSparseHandle(_ClusterHandle):
+    """bmx_cluster_sparse_t: the same over canonical CSC batches (inputs.canonical_csc), kept CSC in HBM."""
+    PREFIX = "bmx_cluster_sparse"
+
+    def add_batch(self, c, ids, n_clusters, restrict, cos_norm, block_cells=None):
+        """c: canonical CSC, genes x cells.  block_cells: cells per uploaded block (None: SPARSE_BLOCK_CELLS, and without
+        that as many as hold about BLOCK_BYTES of stored entries); the results do not depend on it."""
+        if block_cells is None:
+            block_cells = SPARSE_BLOCK_CELLS
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        self._upload_csc(c, csc_block_width(c, BLOCK_BYTES) if block_cells is None else max(1, int(block_cells)),
+                         _lib.i32p(ids), ctypes.c_int32(int(n_clusters)), None if restrict is None else _lib.i32p(restrict),
+                         ctypes.c_int64(-1 if restrict is None else int(restrict.size)), ctypes.c_int32(int(bool(cos_norm))),
+                         nnz_first=True)
+        self.nclusters.append(int(n_clusters))
 
 
 def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row, correct_all,
                  names, device, cluster_d=50):
-    """The body of clusterMNN() from .format_clusters on (R/clusterMNN.R:134-164), for a list of batches."""
+    """The body of clusterMNN() from .format_clusters on (R/clusterMNN.R:134-164), for a list of batches: all numpy
+    arrays, or all scipy.sparse."""
     if len(mats) < 2:
         raise ValueError("at least two batches must be specified")
-    G = check_same_dim(mats, byrow=False)
+    sparse = sp.issparse(mats[0])
+    G = check_same_rows(mats) if sparse else check_same_dim(mats, byrow=False)
     ncells = [m.shape[1] for m in mats]
     check_restrict_length(restrict, len(mats))
     ks = None
@@ -269,7 +320,9 @@ def _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, mi
         raise ValueError(f"clusterMNN works in sum(number of clusters) - 1 = {total - 1} dimensions; the merge engine takes "
                          f"at most {MAX_DIMS}")
     _lib.require_gpu()
-    h = _ClusterHandle(G, sub, device)
+    if sparse:
+        mats = [canonical_csc(m)[0] for m in mats]
+    h = (_ClusterSparseHandle if sparse else _ClusterHandle)(G, sub, device)
     try:
         for m, (lv, ids), r in zip(mats, lev, restrict):
             h.add_batch(m, ids, lv.size, r, cos_norm)
@@ -305,11 +358,15 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cluster_d=50, cos_
     of labels (integers or strings) per batch, or of length 1 for a single object that `batch=` splits -- or a KmeansParam:
     every batch (of a single object: every piece `batch=` splits off) is then clustered by kmeans() on the first
     `cluster_d` PCs of its `subset_row` rows (cluster_d=None: on those rows themselves), every batch from the param's
-    seed; `restrict` plays no part in that, as in the reference."""
+    seed; `restrict` plays no part in that, as in the reference.
+
+    The batches are all dense or all scipy.sparse (implicit zeros are zeros); sparse ones stay CSC on the device and the
+    result is the dense call's (the module docstring)."""
     batches = unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least two batches must be specified")
-    mats: List[np.ndarray] = [np.asarray(b) for b in batches]
+    sparse = all_sparse(batches, "clusterMNN")
+    mats: List[Any] = list(batches) if sparse else [np.asarray(b) for b in batches]
     if len(mats) > 1:
         return _cluster_mnn(mats, restrict, clusters, cos_norm, merge_order, auto_merge, min_batch_skip, subset_row,
                             correct_all, None, device, cluster_d)
@@ -331,6 +388,8 @@ def clusterMNN(*batches, batch=None, restrict=None, clusters, cluster_d=50, cos_
         also = (call,)
     elif not isinstance(clusters, KmeansParam):
         raise ValueError("'clusters' must be either a list or a BlusterParam object")
+    if sparse:
+        x = canonical_csc(x)[0]  # (a format that takes a column mask)
     div = divide_into_batches(x, batch, None if restrict is None else restrict[0], also=also)
     out = _cluster_mnn(div.parts, div.restricted, div.also[0] if also else clusters, cos_norm, merge_order, auto_merge,
                        min_batch_skip, subset_row, correct_all, [str(lv) for lv in div.levels], device, cluster_d)

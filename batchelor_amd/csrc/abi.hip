@@ -240,6 +240,8 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = bmx::DELTA_SPARSE_GENE_TILE;
         } else if (n == "genevar_gene_tile" || n == "genevar_chunk") {
             *value = n == "genevar_gene_tile" ? bmx::GENEVAR_GENE_TILE : bmx::GENEVAR_CHUNK;
+        } else if (n == "cluster_sparse_gene_tile") {
+            *value = bmx::CLUSTER_SPARSE_GENE_TILE;
         } else if (n == "pca_sparse_row_segment") {
             *value = bmx::PCA_SPARSE_ROW_SEGMENT;
         } else if (n == "asv_tally_reset") {

@@ -172,6 +172,7 @@ constexpr int PCA_SPARSE_ROW_SEGMENT = 256;  // stored entries of a gene row one
 constexpr int DELTA_PAIR_CHUNK = 128;  // pairs of one step a workgroup walks (fixed: the results do not depend on the grid)
 constexpr int DELTA_SPARSE_GENE_TILE = 256;  // genes a one-wave workgroup of the CSC handle's pair passes owns
 constexpr int GENEVAR_GENE_TILE = 2048;  // genes a workgroup of the CSC gene-variance kernel owns (gene_var.hip)
+constexpr int CLUSTER_SPARSE_GENE_TILE = 4096;  // genes a workgroup of the CSC centroid pass keeps in the LDS (cluster_mnn.hip)
 
 // ---- the classic mnnCorrect natives: smooth_gaussian_kernel (sgk.hip), adjust_shift_variance (asv.hip) -------------
 void smooth_gaussian_kernel_device(hipStream_t stream, const double* averaged, int g, int U, const int32_t* index,

@@ -1,6 +1,8 @@
 // Device helpers of the kernels that read a batch kept as CSC (indptr absolute, rows ascending within a column): NormSparse
 // (multi_batch_norm.hip), PcaSparse (pca_sparse.hip), DeltaSparse (delta_variance.hip: two arbitrary columns per pair, one
-// wave a tile) and GeneVarSparse (gene_var.hip, over one block at a time).  The store and the host's checks are in resident_batches.hpp.
+// wave a tile), GeneVarSparse (gene_var.hip, over one block at a time) and ClusterSparse (cluster_mnn.hip: the tile walk
+// over a list of cells, and the wave gather it shares with PcaSparse).  The store and the host's checks are in
+// resident_batches.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,25 +37,33 @@ __device__ __forceinline__ int64_t first_row_at_least(const int32_t* __restrict_
 // the column's entries in the tile, entry(c, k, r) for position k with row r, and a barrier before the next column.  Rows
 // are unique within a canonical column, so no two threads meet at a row; on any pattern r stays inside [g0, g1).  (The
 // callbacks get the cell and not its number in the chunk: handed the number, sp_sort_kernel<true> came out 1.5 % slower.)
+//
+// cols (nullable): the chunk is then the positions [list_b, list_b + list_ncol) of that list of cells, list_ncol <= CELLS
+// (ClusterSparse: the restricted cells sorted by cluster; n and chunk play no part).  A pointer in this one body and not a
+// second walk under both forms: with the mapping of a position to its cell handed in as a callable, the kernels of the
+// callers that pass no list came out with another loop test; this way their code is what it was, instruction for instruction.
 template <int CELLS, class ColBegin, class Entry>
 __device__ __forceinline__ void csc_tile_walk(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, int64_t n,
                                               int64_t chunk, int g0, int g1, int64_t* lo, int64_t* hi, ColBegin&& col_begin,
-                                              Entry&& entry) {
-    const int64_t b = chunk * CELLS;
-    const int ncol = (int)((b + CELLS < n ? b + CELLS : n) - b);
+                                              Entry&& entry, const int32_t* __restrict__ cols = nullptr, int list_b = 0,
+                                              int list_ncol = 0) {
+    const int64_t b = cols ? (int64_t)list_b : chunk * CELLS;
+    const int ncol = cols ? list_ncol : (int)((b + CELLS < n ? b + CELLS : n) - b);
     if ((int)threadIdx.x < ncol) {
-        const int64_t kb = indptr[b + threadIdx.x], ke = indptr[b + threadIdx.x + 1];
+        const int64_t c = cols ? (int64_t)cols[b + threadIdx.x] : b + threadIdx.x;
+        const int64_t kb = indptr[c], ke = indptr[c + 1];
         const int64_t first = first_row_at_least(idx, kb, ke, g0);
         lo[threadIdx.x] = first;
         hi[threadIdx.x] = first_row_at_least(idx, first, ke, g1);
     }
     __syncthreads();
     for (int j = 0; j < ncol; ++j) {
-        col_begin(b + j);
+        const int64_t c = cols ? (int64_t)cols[b + j] : b + j;
+        col_begin(c);
         const int64_t ke = hi[j];
         for (int64_t k = lo[j] + threadIdx.x; k < ke; k += 256) {
             const int r = idx[k];
-            if (r >= g0 && r < g1) entry(b + j, k, r);
+            if (r >= g0 && r < g1) entry(c, k, r);
         }
         __syncthreads();
     }
@@ -80,6 +90,52 @@ __device__ __forceinline__ void csc_wave_walk(csc_rows_ptr idx, csc_vals_ptr val
         const int r = idx[k];
         if (r >= g0 && r < g1) entry(r - g0, val[k]);
     }
+}
+
+// ---- one wave a column (or a row of PcaSparse's companion) against a dense row-major matrix, a lane per matrix column
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {  // v is the same in every lane: keep it in scalar registers
+    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return ((int64_t)hi << 32) | (int64_t)(unsigned)lo;
+}
+__device__ __forceinline__ double lane_value(double x, int l) {  // lane l's x, l the same in every lane
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+    return __hiloint2double(hi, lo);
+}
+
+// Lane j's  sum over the entries k in [kb, ke), in order, of val[k] * M[idx[k] * ldm + j]  (j < 64; kb, ke wave-uniform).
+// An entry whose index is outside [0, bound) is skipped.  The wave reads 64 entries at once, then takes them one after
+// the other, four gathers in flight.
+__device__ __forceinline__ double gather_rows64(const int32_t* __restrict__ idx, const double* __restrict__ val, int64_t kb,
+                                                int64_t ke, const double* __restrict__ M, int64_t ldm, int64_t bound,
+                                                int lane) {
+    double acc = 0.0;
+    for (int64_t k0 = kb; k0 < ke; k0 += 64) {
+        const int64_t k = k0 + lane;
+        int32_t r = -1;
+        double v = 0.0;
+        if (k < ke) {
+            r = idx[k];
+            v = val[k];
+        }
+        const int cnt = (int)(ke - k0 < 64 ? ke - k0 : 64);
+        for (int i = 0; i < cnt; i += 4) {  // (lanes at and after cnt hold r = -1: skipped)
+            int ri[4];
+            double vi[4], q[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                ri[u] = __builtin_amdgcn_readlane(r, i + u);
+                vi[u] = lane_value(v, i + u);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q[u] = (ri[u] >= 0 && ri[u] < bound) ? M[(int64_t)ri[u] * ldm + lane] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (ri[u] >= 0 && ri[u] < bound) acc += vi[u] * q[u];
+        }
+    }
+    return acc;
 }
 
 }  // namespace bmx

@@ -48,51 +48,6 @@ constexpr int SEG = PCA_SPARSE_ROW_SEGMENT;  // entries of a row one wave adds
 constexpr int CH = 128;                      // cells per chunk of the counting sort
 constexpr int GT = 4096;                     // rows per tile of the counting sort (16 KiB of counters in the LDS)
 
-__device__ __forceinline__ int64_t wave_uniform(int64_t v) {  // v is the same in every lane: keep it in scalar registers
-    const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
-    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return ((int64_t)hi << 32) | (int64_t)(unsigned)lo;
-}
-__device__ __forceinline__ double lane_value(double x, int l) {  // lane l's x, l the same in every lane
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
-
-// Lane j's  sum over the entries k in [kb, ke), in order, of val[k] * M[idx[k] * ldm + j]  (j < 64; kb, ke wave-uniform).
-// An entry whose index is outside [0, bound) is skipped.  The wave reads 64 entries at once, then takes them one after
-// the other, four gathers in flight.
-__device__ __forceinline__ double gather_rows64(const int32_t* __restrict__ idx, const double* __restrict__ val, int64_t kb,
-                                                int64_t ke, const double* __restrict__ M, int64_t ldm, int64_t bound,
-                                                int lane) {
-    double acc = 0.0;
-    for (int64_t k0 = kb; k0 < ke; k0 += 64) {
-        const int64_t k = k0 + lane;
-        int32_t r = -1;
-        double v = 0.0;
-        if (k < ke) {
-            r = idx[k];
-            v = val[k];
-        }
-        const int cnt = (int)(ke - k0 < 64 ? ke - k0 : 64);
-        for (int i = 0; i < cnt; i += 4) {  // (lanes at and after cnt hold r = -1: skipped)
-            int ri[4];
-            double vi[4], q[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ri[u] = __builtin_amdgcn_readlane(r, i + u);
-                vi[u] = lane_value(v, i + u);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) q[u] = (ri[u] >= 0 && ri[u] < bound) ? M[(int64_t)ri[u] * ldm + lane] : 0.0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (ri[u] >= 0 && ri[u] < bound) acc += vi[u] * q[u];
-        }
-    }
-    return acc;
-}
-
 // The cells [c0, c0 + m), one wave a cell: cut[c] = the position after the column's last entry below row Gp (its PCA
 // prefix), inv[c] = 1 / max(1e-8, l2 over the prefix) (inv null: not wanted).  flags: the pattern pair (csc_entry_flags).
 __global__ __launch_bounds__(256) void sp_prepare_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,

@@ -1,7 +1,7 @@
-// What the handles that keep genes x cells batches in HBM (Pca, PcaSparse, Cluster, Linear, Norm, NormSparse, Delta,
-// DeltaSparse) have
+// What the handles that keep genes x cells batches in HBM (Pca, PcaSparse, Cluster, ClusterSparse, Linear, Norm,
+// NormSparse, Delta, DeltaSparse) have
 // in common: the guard their C entry points go through, the argument checks of a batch, the bookkeeping of a batch that
-// arrives in column blocks -- dense, or CSC (NormSparse, PcaSparse, DeltaSparse) --, the event-pair stage timer, the store that owns
+// arrives in column blocks -- dense, or CSC (NormSparse, PcaSparse, DeltaSparse, ClusterSparse) --, the event-pair stage timer, the store that owns
 // the cache, the copy stream, the batches and the stage times, and the blocked pass that writes every cell (or every
 // stored entry).  The checks, the bookkeeping and the cutting of output blocks make no HIP call.  GeneVar / GeneVarSparse
 // (gene_var.hip) use the store for everything but the batches' cells, which only pass through two block buffers.

@@ -119,7 +119,8 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * "asv_literal_addends" (addends the re-run cells kept), "asv_chain_tiles" (tiles with a re-run cell).  Waits for the device.
  * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
  * owns, pairs of a step it walks), "delta_sparse_gene_tile" (genes a workgroup of bmx_delta_sparse_run's owns), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
- * genes a workgroup of the sparse one owns). */
+ * genes a workgroup of the sparse one owns), "cluster_sparse_gene_tile" (genes a workgroup of bmx_cluster_sparse_centroids
+ * keeps in the LDS). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
  * call went -- 0 the histogram quantile (a well-conditioned cell), 1 re-run in the reference's order of operations, 2
@@ -490,6 +491,43 @@ int32_t bmx_cluster_propagate(bmx_cluster_t* h, int32_t batch, const double* rot
 /* Diagnostics, milliseconds since the handle was made: out[0] = upload (host wall time of the staged copies), then HIP-event
  * time of the centroid pass, the projection, nearest centroid + median, the smoothing. */
 int32_t bmx_cluster_stage_ms(const bmx_cluster_t* h, double* out5);
+
+/* The same over batches kept in HBM as CSC -- per batch indptr [n + 1] (int64), 0-based int32 row indices strictly
+ * ascending within a column and FP64 values (explicit zeros are values like any other; implicit entries are zeros).  A
+ * batch is announced with its cells and its stored entries and filled in column blocks (per block: indptr [n_block + 1]
+ * relative to the block -- starts at 0, never decreases, ends at nnz; indices and data may be NULL only when nnz is 0;
+ * host memory, read completely when the call returns).  Only the two streaming reads differ from bmx_cluster_t:
+ *   - the centroid pass takes a chunk's cells in list order and adds every stored entry to its gene's accumulator, which
+ *     a workgroup keeps in the LDS for bmx_dev_get "cluster_sparse_gene_tile" genes: the dense handle's sums with their
+ *     terms of +0 left out, so without cos_norm the centroids equal the dense handle's bit for bit;
+ *   - the projection gathers the rotation's rows of a cell's stored entries, one wave a cell, 64 columns at a time.
+ * Under cos_norm a cell's l2 is taken over its stored entries in the subset_row rows, behind the block's upload.  The
+ * reduction over chunks, the centring, the nearest centroid, the median and the smoothing are bmx_cluster_t's kernels,
+ * and so are the arguments' meanings, limits and messages and the five stage times.  No floating-point atomics: the same
+ * calls give the same bits, however the batch was cut into blocks.
+ * What only the device sees of the pattern is flagged behind the upload, and bmx_cluster_sparse_centroids /
+ * bmx_cluster_sparse_propagate refuse with BMX_ERR_ARG before they start: "a row index is outside [0, number of genes)",
+ * "the row indices of a column should be strictly ascending".  Such entries are skipped by every kernel, never used as an
+ * address.  A batch holds at most 2^31 - 1 cells and any number of stored entries. */
+typedef struct bmx_cluster_sparse bmx_cluster_sparse_t;
+/* subset_row / n_subset_row: as for bmx_cluster_create. */
+int32_t bmx_cluster_sparse_create(int32_t device, int32_t n_genes, const int32_t* subset_row, int32_t n_subset_row,
+                                  bmx_cluster_sparse_t** out);
+void bmx_cluster_sparse_destroy(bmx_cluster_sparse_t* h);
+/* A batch of n cells with nnz stored entries in all (reserved once); the other arguments as for bmx_cluster_begin_batch.
+ * Its cells follow in one or more blocks, in order; a block's checks and norms run behind the upload of the next. */
+int32_t bmx_cluster_sparse_begin_batch(bmx_cluster_sparse_t* h, int64_t n, int64_t nnz, const int32_t* clusters0,
+                                       int32_t n_clusters, const int32_t* restrict_idx, int64_t n_restrict, int32_t cos_norm);
+int32_t bmx_cluster_sparse_add_block(bmx_cluster_sparse_t* h, int64_t n_block, const int64_t* indptr, const int32_t* indices,
+                                     const double* data, int64_t nnz);
+/* As bmx_cluster_centroids: out [n_genes x n_clusters] column-major (dense). */
+int32_t bmx_cluster_sparse_centroids(bmx_cluster_sparse_t* h, int32_t batch, double* out);
+/* As bmx_cluster_propagate: out [n x d] column-major (dense). */
+int32_t bmx_cluster_sparse_propagate(bmx_cluster_sparse_t* h, int32_t batch, const double* rotation, int32_t d,
+                                     const double* centers, const double* centroid_pcs, const double* corrected_pcs,
+                                     double* out, double* sigma_out);
+/* As bmx_cluster_stage_ms; the upload includes the wait for the last block's checks and norms. */
+int32_t bmx_cluster_sparse_stage_ms(const bmx_cluster_sparse_t* h, double* out5);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * kmeans(): R's kmeans(x, centers = <matrix>, algorithm = "Lloyd") (what bluster::KmeansParam stands for in
