@@ -202,8 +202,9 @@ def quickCorrect(*batches, batch=None, restrict=None, correct_all=True, PARAM=No
     model_var_args: `trend_fit` and `equiweight`.  PARAM defaults to FastMnnParam().
 
     Sparse counts whose zero stays a zero come out of multiBatchNorm as CSC and go into the sparse variance handle and
-    into fastMNN as they are; where multiBatchNorm returns dense values (pseudo_count != 1) the dense path is taken.
-    What mnnCorrect, rescaleBatches and regressBatches refuse of sparse input, they refuse here."""
+    into fastMNN or mnnCorrect (ClassicMnnParam) as they are; where multiBatchNorm returns dense values
+    (pseudo_count != 1) the dense path is taken.  What rescaleBatches and regressBatches refuse of sparse input, they
+    refuse here."""
     PARAM = FastMnnParam() if PARAM is None else PARAM
     multi_norm_args = dict(multi_norm_args or {})
     model_var_args = dict(model_var_args or {})

@@ -454,9 +454,11 @@ int32_t bmx_mnn_average_correction(const double* refdata, int32_t n1, const doub
     });
 }
 
-int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* data, const int32_t* ncells,
-                        const int32_t* const* restrict_idx, const int32_t* n_restrict, const bmx_mnn_params_t* params,
-                        bmx_mnn_result_t** out) {
+// bmx_mnn_correct and bmx_mnn_correct_sparse: indptr / indices null for dense batches, both set for CSC ones
+static int32_t mnn_correct_entry(int32_t nbatches, int32_t n_genes, const int64_t* const* indptr,
+                                 const int32_t* const* indices, const double* const* data, const int32_t* ncells,
+                                 const int32_t* const* restrict_idx, const int32_t* n_restrict,
+                                 const bmx_mnn_params_t* params, bmx_mnn_result_t** out, bool sparse) {
     return guarded([&] {
         if (!out) throw bmx::Error(BMX_ERR_ARG, "null result pointer");
         *out = nullptr;
@@ -465,11 +467,13 @@ int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* 
         const bmx_mnn_params_t p = read_versioned(params, offsetof(bmx_mnn_params_t, tree_len) + sizeof(int32_t),
                                                   "bmx_mnn_params_t", zeros);
         if (nbatches < 2) throw bmx::Error(BMX_ERR_ARG, "at least two batches must be specified");
-        if (!data || !ncells) throw bmx::Error(BMX_ERR_ARG, "null batch arrays");
+        if (!data || !ncells || (sparse && (!indptr || !indices))) throw bmx::Error(BMX_ERR_ARG, "null batch arrays");
         bmx::MnnCorrectArgs a;
         a.B = nbatches;
         a.G = n_genes;
         a.data = data;
+        a.indptr = indptr;
+        a.indices = indices;
         a.ncells = ncells;
         a.restrict_idx = restrict_idx;
         a.n_restrict = n_restrict;
@@ -493,6 +497,19 @@ int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* 
         bmx::mnn_correct_run(a, res->r);
         *out = res.release();
     });
+}
+
+int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* data, const int32_t* ncells,
+                        const int32_t* const* restrict_idx, const int32_t* n_restrict, const bmx_mnn_params_t* params,
+                        bmx_mnn_result_t** out) {
+    return mnn_correct_entry(nbatches, n_genes, nullptr, nullptr, data, ncells, restrict_idx, n_restrict, params, out, false);
+}
+
+int32_t bmx_mnn_correct_sparse(int32_t nbatches, int32_t n_genes, const int64_t* const* indptr,
+                               const int32_t* const* indices, const double* const* data, const int32_t* ncells,
+                               const int32_t* const* restrict_idx, const int32_t* n_restrict,
+                               const bmx_mnn_params_t* params, bmx_mnn_result_t** out) {
+    return mnn_correct_entry(nbatches, n_genes, indptr, indices, data, ncells, restrict_idx, n_restrict, params, out, true);
 }
 
 int32_t bmx_mnn_result_sizes(const bmx_mnn_result_t* r, int32_t* n_genes_out, int64_t* ncells, int64_t* npairs) {

@@ -15,6 +15,10 @@
 //      output matrix for correction.out; both take the nodes' restrict lists;
 //   5. right += pmax(scaling, 1) * correction in place (:345-348), .combine_restrict on the host.
 // The pairs are reindexed and the rows put back in input order at the end (:364-381).
+//
+// Batches given as CSC (bmx_mnn_correct_sparse) differ in .prepare_input_data alone: one batch's CSC at a time goes up and
+// csc_expand_kernel writes its pool rows from the stored entries -- the subset.row genes, and all genes only for the
+// output matrix of correct.all.  The merges then run on the bits the dense call would have made of toarray().
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -23,12 +27,76 @@
 
 #include "bmx_common.hpp"
 #include "bmx_ops.hpp"
+#include "csc_device.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
 #include "mnn_correct.hpp"
+#include "ordered_sums.hpp"
+#include "resident_batches.hpp"
 
 namespace bmx {
 namespace {
+
+// Pool rows straight from ONE batch's CSC (bmx_mnn_correct_sparse): indptr [m + 1] from 0, idx / val the batch's stored
+// entries, dst [m][W] the batch's slice of the pool.  One wave a cell c, four cells a workgroup:
+//   dst[c * W + j] = 0.0 + the stored value of row rows[j] (rows null: of row j) in column c, else +0.0
+// which are toarray()'s bits: scipy adds the entries into a matrix of zeros, so a stored -0.0 comes out as +0.0 there and
+// here, and every other value as it is.  l2 (nullable, the slice's norms): every element is divided by
+// cos_clamp(l2[c]), apply_cosnorm_kernel's expression, so the bits are that kernel's.
+// The wave first takes every stored entry of the column once, lane l the entries l, l + 64, ..., for the pattern flags
+// (csc_entry_flags, to flags[CSC_F_ROW] / flags[CSC_F_ORDER]).  Then
+//   SEARCH   lane l takes the positions l, l + 64, ... of the row and finds each by first_row_at_least: coalesced stores,
+//            every element written once by one lane, rows that repeat or come in any order cost nothing.  A row index
+//            out of memory is only ever compared, never an address; rows[] is the host's (checked there).
+//   !SEARCH  (rows null, W = G) the slice has been zeroed by hipMemsetAsync on the same stream, and the walk over the
+//            entries stores each at its row -- an entry whose row is outside [0, G) is left out.  Rows are unique in a
+//            canonical column: no two lanes meet; a column where they do is flagged and the call ends with that error.
+//            A cell whose norm is NaN takes the search form, which writes 0 / NaN where the memset left +0.
+template <bool SEARCH>
+__global__ __launch_bounds__(256) void csc_expand_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                         const double* __restrict__ val, int G, int64_t m,
+                                                         const int32_t* __restrict__ rows, int W,
+                                                         const double* __restrict__ l2, double* __restrict__ dst,
+                                                         int32_t* __restrict__ flags) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= m) return;  // (a whole wave leaves)
+    const int64_t kb = wave_uniform(indptr[c]), ke = wave_uniform(indptr[c + 1]);
+    const double L = l2 ? cos_clamp(l2[c]) : 1.0;
+    const bool search = SEARCH || L != L;
+    double* out = dst + c * W;
+    int bad_row = 0, bad_order = 0;
+    for (int64_t k = kb + lane; k < ke; k += 64) {
+        const int32_t r = idx[k];
+        if (csc_entry_flags(idx, k, kb, r, G, bad_row, bad_order) || search) continue;
+        const double v = 0.0 + val[k];
+        out[r] = l2 ? v / L : v;
+    }
+    if (search)
+        for (int j = lane; j < W; j += 64) {
+            const int g = rows ? rows[j] : j;
+            const int64_t p = first_row_at_least(idx, kb, ke, g);
+            double v = 0.0;
+            if (p < ke && idx[p] == g) v += val[p];
+            out[j] = l2 ? v / L : v;
+        }
+    if (bad_row) flags[CSC_F_ROW] = 1;
+    if (bad_order) flags[CSC_F_ORDER] = 1;
+}
+
+// rows null: all G rows in order (W = G), the scatter form; else the search form over rows [W] (0-based, inside [0, G))
+void expand_csc(hipStream_t s, const int64_t* indptr, const int32_t* idx, const double* val, int G, int64_t m,
+                const int32_t* rows, int W, const double* l2, double* dst, int32_t* flags) {
+    if (!rows && W != G) throw Error(BMX_ERR_ARG, "internal: the scatter form writes all genes");
+    const dim3 grid((unsigned)((m + 3) / 4));
+    if (rows) {
+        hipLaunchKernelGGL(csc_expand_kernel<true>, grid, dim3(256), 0, s, indptr, idx, val, G, m, rows, W, l2, dst, flags);
+    } else {
+        BMX_HIP(hipMemsetAsync(dst, 0, (size_t)m * W * sizeof(double), s));
+        hipLaunchKernelGGL(csc_expand_kernel<false>, grid, dim3(256), 0, s, indptr, idx, val, G, m, rows, W, l2, dst, flags);
+    }
+    BMX_LAUNCH_CHECK();
+}
 
 // out [n][ns] = X [n][ld] restricted to the columns cols [ns] (0-based): the subset.row genes of the output matrix
 // (R/mnnCorrect.R:466-471).  One thread per output element.
@@ -116,7 +184,15 @@ void mnn_correct_check(const MnnCorrectArgs& a) {
     if (a.G < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one gene");
     for (int b = 0; b < a.B; ++b) {
         if (a.ncells[b] < 1) throw Error(BMX_ERR_ARG, "every batch needs at least one cell");
-        if (!a.data[b]) throw Error(BMX_ERR_ARG, "null batch matrix");
+        if (a.sparse()) {
+            // one block that is the whole batch; its number of stored entries is where indptr ends
+            const int64_t n = a.ncells[b];
+            if (!a.indptr[b]) throw Error(BMX_ERR_ARG, "the block's 'indptr' is missing");
+            check_csc_block(n, 0, n, a.indptr[b], a.indices ? a.indices[b] : nullptr, a.data ? a.data[b] : nullptr,
+                            a.indptr[b][n]);
+        } else if (!a.data[b]) {
+            throw Error(BMX_ERR_ARG, "null batch matrix");
+        }
         const bool has = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
         if (!has) continue;
         if (a.n_restrict[b] == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
@@ -202,9 +278,6 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
 
     // ---- .prepare_input_data (R/mnnCorrect.R:398-445) ----
     DevBuf<double> raw, subb, inb, outb, l2b;
-    double* X = raw.reserve((size_t)N * G);  // the caller's genes, pool order: a cell's G genes are contiguous in R's layout
-    for (int b = 0; b < B; ++b)
-        upload_pageable(X + pool_off[b] * G, a.data[b], (size_t)a.ncells[b] * G * sizeof(double), s);
     // subset.row equal to every gene in order is no subset (:404)
     bool subset = a.subset != nullptr && a.nsubset > 0;
     if (subset && a.nsubset == G) {
@@ -222,14 +295,56 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
     const int Gs = subset ? a.nsubset : G;
     // S: the subset genes; In = S cosine-normalised with cos.norm.in; Out = all genes (correct.all) or S, cosine-normalised with
     // cos.norm.out by the l2 norms of S (:419-431).  same.set: one matrix serves both.
-    double* S = X;
-    if (subset) {
-        S = subb.reserve((size_t)N * Gs);
-        gather_cols(s, X, N, G, cols, Gs, S);
-    }
-    const bool same = !(subset && a.correct_all) && (a.cos_in != 0) == (a.cos_out != 0);
+    const bool out_all = subset && a.correct_all;
+    const bool same = !out_all && (a.cos_in != 0) == (a.cos_out != 0);
+    const bool norms = a.cos_in || a.cos_out;
     double* l2 = l2b.reserve((size_t)N);
-    if (a.cos_in || a.cos_out) cosine_l2_device(s, S, Gs, (int)N, l2);
+    double* S = nullptr;
+    double* X = nullptr;  // all genes: the dense call's upload; of CSC batches only the output genes of correct.all
+    if (!a.sparse()) {
+        X = raw.reserve((size_t)N * G);  // the caller's genes, pool order: a cell's G genes are contiguous in R's layout
+        for (int b = 0; b < B; ++b)
+            upload_pageable(X + pool_off[b] * G, a.data[b], (size_t)a.ncells[b] * G * sizeof(double), s);
+        S = X;
+        if (subset) {
+            S = subb.reserve((size_t)N * Gs);
+            gather_cols(s, X, N, G, cols, Gs, S);
+        }
+        if (norms) cosine_l2_device(s, S, Gs, (int)N, l2);
+    } else {
+        // One batch's CSC at a time, in buffers sized for the largest batch: its rows of S (the subset's, or all) come
+        // straight from the stored entries, then their norms, then -- correct.all with a subset -- its rows of the output
+        // genes, already divided by those norms with cos.norm.out.  Without correct.all nothing here is [N][G] under a
+        // subset; with it, X is the one such buffer.
+        int64_t max_n = 0, max_nnz = 0;
+        for (int b = 0; b < B; ++b) {
+            max_n = std::max<int64_t>(max_n, a.ncells[b]);
+            max_nnz = std::max(max_nnz, a.indptr[b][a.ncells[b]]);
+        }
+        DevBuf<int64_t> ipb;
+        DevBuf<int32_t> ixb, flagb;
+        DevBuf<double> valb;
+        int64_t* ip = ipb.reserve((size_t)max_n + 1);
+        int32_t* ix = ixb.reserve((size_t)std::max<int64_t>(max_nnz, 1));
+        double* val = valb.reserve((size_t)std::max<int64_t>(max_nnz, 1));
+        int32_t* flags = flagb.reserve(CSC_F_WORDS);
+        BMX_HIP(hipMemsetAsync(flags, 0, CSC_F_WORDS * sizeof(int32_t), s));
+        S = subb.reserve((size_t)N * Gs);
+        if (out_all) X = raw.reserve((size_t)N * G);
+        for (int b = 0; b < B; ++b) {
+            const int64_t n = a.ncells[b], nnz = a.indptr[b][n], off = pool_off[b];
+            upload_pageable(ip, a.indptr[b], (size_t)(n + 1) * sizeof(int64_t), s);
+            upload_pageable(ix, a.indices[b], (size_t)nnz * sizeof(int32_t), s);
+            upload_pageable(val, a.data[b], (size_t)nnz * sizeof(double), s);
+            expand_csc(s, ip, ix, val, G, n, cols, Gs, nullptr, S + off * Gs, flags);
+            if (norms) cosine_l2_device(s, S + off * Gs, Gs, (int)n, l2 + off);
+            if (out_all) expand_csc(s, ip, ix, val, G, n, nullptr, G, a.cos_out ? l2 + off : nullptr, X + off * G, flags);
+        }
+        int32_t hflags[CSC_F_WORDS] = {0, 0};
+        BMX_HIP(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, s));
+        BMX_HIP(hipStreamSynchronize(s));
+        throw_if_bad_pattern(hflags);
+    }
     double* In = S;
     if (a.cos_in) {
         In = inb.reserve((size_t)N * Gs);
@@ -238,9 +353,9 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
     double* Out = In;
     int Go = Gs;
     if (!same) {
-        Out = subset && a.correct_all ? X : S;
-        Go = subset && a.correct_all ? G : Gs;
-        if (a.cos_out) {
+        Out = out_all ? X : S;
+        Go = out_all ? G : Gs;
+        if (a.cos_out && !(a.sparse() && out_all)) {  // (the CSC batches' output genes came out normalised)
             double* o = outb.reserve((size_t)N * Go);
             apply_cosine_norm_device(s, Out, Go, (int)N, l2, o);
             Out = o;

@@ -9,6 +9,10 @@ struct MnnCorrectArgs {
     int B = 0, G = 0;                         // batches, genes of every batch
     const double* const* data = nullptr;      // per batch: G x ncells[b] column-major (R's layout)
     const int32_t* ncells = nullptr;
+    // the batches as CSC (bmx_mnn_correct_sparse): indptr is set, `data` holds every batch's stored values
+    const int64_t* const* indptr = nullptr;   // per batch: [ncells[b] + 1], from 0 to the batch's number of stored entries
+    const int32_t* const* indices = nullptr;  // per batch: 0-based rows, ascending within a column; null without an entry
+    bool sparse() const { return indptr != nullptr; }
     const int32_t* const* restrict_idx = nullptr;  // per batch: 1-based cells, or null (nullable as a whole)
     const int32_t* n_restrict = nullptr;           // per batch: their number, < 0: none
     int k = 20;

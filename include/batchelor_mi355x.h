@@ -302,6 +302,18 @@ typedef struct bmx_mnn_result bmx_mnn_result_t;
 int32_t bmx_mnn_correct(int32_t nbatches, int32_t n_genes, const double* const* data, const int32_t* ncells,
                         const int32_t* const* restrict_idx, const int32_t* n_restrict, const bmx_mnn_params_t* params,
                         bmx_mnn_result_t** out);
+/* The same for batches given as CSC (genes x cells, a column per cell): indptr[b] is [ncells[b] + 1], from 0 to the
+ * batch's number of stored entries and never decreasing; indices[b] the 0-based rows, strictly ascending within a column;
+ * data[b] the stored values (indices[b] and data[b] may be NULL only where the batch has no stored entry).  indptr is
+ * checked before any device work; a row outside [0, n_genes) or rows that do not ascend are seen on the device, where
+ * such an entry is left out, and end the call with BMX_ERR_ARG.  A batch's CSC goes up whole and is expanded there into
+ * the rows the correction needs: with subset.row and without correct.all no all-genes matrix exists on either side.
+ * The result is bmx_mnn_correct's over the same matrices, bit for bit; a stored value v counts as 0.0 + v, so a stored
+ * -0.0 is the +0.0 it becomes when a sparse matrix is made dense by adding its entries into zeros. */
+int32_t bmx_mnn_correct_sparse(int32_t nbatches, int32_t n_genes, const int64_t* const* indptr,
+                               const int32_t* const* indices, const double* const* data, const int32_t* ncells,
+                               const int32_t* const* restrict_idx, const int32_t* n_restrict,
+                               const bmx_mnn_params_t* params, bmx_mnn_result_t** out);
 /* Sizes: genes of the corrected matrix (all genes with correct.all and a subset, else the subset's), cells, and the
  * pairs of every merge (npairs [nbatches - 1], NULL to skip). */
 int32_t bmx_mnn_result_sizes(const bmx_mnn_result_t* r, int32_t* n_genes_out, int64_t* ncells, int64_t* npairs);
