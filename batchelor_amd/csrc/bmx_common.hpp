@@ -16,11 +16,6 @@
 
 namespace bmx {
 
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
 #define BMX_HIP(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \

@@ -32,14 +32,6 @@ struct Node {
     std::vector<int> extras;      // ids of batch vectors in the engine's pool (MNN_treenode@extras)
 };
 
-struct TreeSlot {
-    int left = -1, right = -1;  // children (indices into the slot vector), -1 for a leaf
-    std::unique_ptr<Node> node; // set for finished nodes (materialised leaves or finished merges)
-    int batch = -1;             // a leaf that has not been materialised yet: its batch (0-based) ...
-    int64_t arena_row = 0;      // ... and its first row in the run's arena
-    bool ready() const { return (bool)node || batch >= 0; }
-};
-
 struct MergeRecord {
     std::vector<int> left_set, right_set;
     DevBuf<int32_t> first, second;  // 1-based rows within the left / right node at merge time
@@ -65,7 +57,7 @@ class Engine {
     // production exchange: an RCCL communicator owned by the engine, all-gathers in place on the engine's stream
     void init_rccl(int rank, int world, const void* unique_id);
     // exchange statistics since the last run() started
-    void emulate(int mode, int rank, int world);  // 0 off, 1 record (single rank), 2 replay as rank of world (see engine.hip)
+    void emulate(int mode, int rank, int world);  // 0 off, 1 record (single rank), 2 replay as rank of world (see engine_exchange.hip)
     int64_t exchange_calls() const { return xchg_calls_; }
     int64_t exchange_bytes() const { return xchg_bytes_; }
     // lazy: the matrices are NOT copied here -- the caller keeps them valid until the next run() has returned, which
@@ -142,7 +134,7 @@ class Engine {
     DevBuf<unsigned long long> maskL_;
     SortedRows sorted_;  // k2 > 64: both neighbour lists, each row sorted (pairs.hip)
     DevBuf<double> kthL_;  // per selected left cell: the largest distance of its row of idxLR_ (+inf where unknown)
-    DevBuf<double> distT_, distRL_, averaged_, loc_, vecs_, scal_, means_pool_;
+    DevBuf<double> distT_, distRL_, averaged_, vecs_, scal_, means_pool_;
     DevBuf<float> seedL_;
     DevBuf<double> corr_, asv_ws_, asv_scale_;
     DevBuf<double> arena_;  // [N][d]: the rows of a predefined-tree run, leaves in tree order (root_ aliases it)
@@ -150,16 +142,52 @@ class Engine {
     int n_slots_ = 0, slot_cap_ = 0;
 
   private:
+    // one run (engine.hip): reset, then the predefined tree's merges or auto-merge's, then what the host reads back
     void run_once(const bmx_params_t& p, const int32_t* tree, int tree_len);
+    void reset_run();
+    std::unique_ptr<Node> make_leaf(int b, double* arena_rows);  // arena_rows null: the leaf owns its rows
+    void run_tree(const bmx_params_t& p, const int32_t* tree, int tree_len);
+    void run_auto(const bmx_params_t& p);
+    std::vector<int32_t> recount_merged(const Node& merged, const std::vector<std::unique_ptr<Node>>& rem, const bmx_params_t& p);
+    void finish_run();
     // auto-merge: n independent pair counts dealt round robin over the ranks (each an unsharded search), then all-gathered
-    std::vector<int32_t> solo_counts(int n, const std::function<int(int)>& count, bool dry = false);
+    std::vector<int32_t> solo_counts(int n, const std::function<int(int)>& count);
+    struct SoloRank {  // while it lives this rank runs an unsharded search of its own (rank 0 of 1, solo_ up)
+        Engine* e;
+        int rank, world;
+        explicit SoloRank(Engine* eng) : e(eng), rank(eng->rank_), world(eng->world_) {
+            e->rank_ = 0;
+            e->world_ = 1;
+            e->solo_ = world > 1;
+        }
+        ~SoloRank() {
+            e->rank_ = rank;
+            e->world_ = world;
+            e->solo_ = false;
+        }
+    };
     std::vector<int32_t> gather_counts(const std::vector<int32_t>& mine);
     DevBuf<int32_t> count_xchg_;
     DevBuf<int32_t> xflags_;   // [world][4] the ranks' optimistic-search flags, gathered with every search's lists
     bool solo_ = false;        // this rank is running a whole search of its own (auto-merge counts): read_state does not restart
     bool solo_flag_ = false;   // ... but remembers that it should have; gather_counts tells every rank
     const int32_t* read_state();  // one wait: the run's device words in pinned memory; throws OptimisticRetry
+    // one merge (engine_merge.hip): a driver over phases that share a MergeCtx (engine_internal.hpp)
+    struct MergeCtx;
     void merge_step(int mdx, Node& left, Node& right, const bmx_params_t& p, std::unique_ptr<Node>& merged);
+    void merge_prepare(MergeCtx& c);
+    void merge_batch_vector(MergeCtx& c);
+    bool merge_is_skipped(MergeCtx& c);
+    void merge_correct(MergeCtx& c);
+    void apply_rows_sharded(MergeCtx& c, int safe_k);
+    void apply_var_adj(MergeCtx& c, int safe_k);
+    void merge_skipped_stats(MergeCtx& c);
+    std::unique_ptr<Node> merge_update(MergeCtx& c, bool corrected);
+    int take_slot();  // the next statistics slot / scalar of the run
+    // the exchange transport is in play: several ranks, a recording, or the testing hook "exchange_always" with a transport
+    bool transport_in_play() const;
+    // m restrict rows and (next non-null) the chains of their repeated cells, device to device into the node
+    void copy_restrict(Node& node, int m, const int32_t* rows, const int32_t* next, const int32_t* head);
     // statistics (column means + total variance) of the segments whose slot is stale
     void ensure_stats(Node& node);
     void ensure_stats2(Node& a, Node* b);  // both nodes of a merge in one pass
@@ -243,7 +271,6 @@ class Engine {
     std::vector<MergeRecord> merges_;
     int n_extras_ = 0;
     std::vector<double> scal_host_;
-    friend struct EngineAccess;
 };
 
 }  // namespace bmx

@@ -1,10 +1,20 @@
-// What host code needs that needs no HIP header: the testing knobs and the two integer helpers.  bmx_common.hpp includes it
-// for every unit of the library; knn_plan.hpp includes it alone, so that the plan of a candidate pass compiles with a plain
-// C++ compiler (tests/host/knn_plan_host.cpp).
+// What host code needs that needs no HIP header: the library's error, the testing knobs and the two integer helpers.
+// bmx_common.hpp includes it for every unit of the library; knn_plan.hpp and merge_plan.hpp include it alone, so that the
+// plan of a candidate pass and of a run's merges compile with a plain C++ compiler (tests/host/knn_plan_host.cpp,
+// tests/host/merge_plan_host.cpp).
 #pragma once
 #include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "../../include/batchelor_mi355x.h"
 
 namespace bmx {
+
+struct Error : std::runtime_error {
+    int code;
+    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
 
 // Testing hooks (bmx_dev_set in the C ABI): process-wide knobs that tests and developer scripts set by an explicit call.
 // Nothing in the ENVIRONMENT of the host process changes what the library computes or which tier / form runs

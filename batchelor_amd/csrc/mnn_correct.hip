@@ -30,6 +30,7 @@
 #include "csc_device.hpp"
 #include "engine.hpp"
 #include "host_xfer.hpp"
+#include "merge_plan.hpp"
 #include "mnn_correct.hpp"
 #include "ordered_sums.hpp"
 #include "resident_batches.hpp"
@@ -131,48 +132,39 @@ T* put(DevBuf<T>& b, const T* host, size_t n, hipStream_t s) {
     return p;
 }
 
+// what a leaf or a finished merge of the plan (merge_plan.hpp: its slice of the pool) carries on the host
 struct TNode {
-    int left = -1, right = -1;  // children (indices), -1: a leaf or a finished merge
-    int row0 = 0, n = 0;        // slice of the pool
     std::vector<int> index;     // batch ids (1-based), in row order
     bool has_restrict = false;
     std::vector<int32_t> restrict_rows;  // 0-based rows of the node, in the caller's order
-    bool done() const { return left < 0; }
 };
 
-// .get_next_merge (R/MNN_tree.R:61-69): the right subtree first
-int next_merge(const std::vector<TNode>& t, int at) {
-    const TNode& x = t[at];
-    if (t[x.left].done() && t[x.right].done()) return at;
-    if (!t[x.right].done()) return next_merge(t, x.right);
-    return next_merge(t, x.left);
-}
-
 // a Node view of a slice, with the restrict list and its dup chains (as Engine::upload builds them)
-void make_view(Node& v, double* base, const TNode& t, int d, hipStream_t s) {
-    v.n = t.n;
-    v.data.alias(base + (int64_t)t.row0 * d, (size_t)std::max(1, t.n) * d);
+void make_view(Node& v, double* base, const PlanNode& at, const TNode& t, int d, hipStream_t s) {
+    v.n = (int)at.n;
+    v.data.alias(base + at.row0 * d, (size_t)std::max(1, v.n) * d);
     v.has_restrict = t.has_restrict;
     v.restrict_dups = false;
     if (!t.has_restrict) return;
     const int m = (int)t.restrict_rows.size();
     v.n_restrict = m;
-    std::vector<int32_t> last((size_t)t.n, -1), next((size_t)m, -1), head((size_t)m, 0);
-    for (int i = 0; i < m; ++i) {
-        const int32_t c = t.restrict_rows[i];
-        head[i] = last[c] < 0 ? 1 : 0;
-        if (last[c] >= 0) {
-            next[last[c]] = i;
-            v.restrict_dups = true;
-        }
-        last[c] = i;
-    }
-    put(v.restrict_rows, t.restrict_rows.data(), (size_t)m, s);
-    if (v.restrict_dups) {
-        put(v.dup_next, next.data(), (size_t)m, s);
-        put(v.dup_head, head.data(), (size_t)m, s);
+    const RestrictChains rc = restrict_chains(t.restrict_rows.data(), m, v.n, 0);
+    v.restrict_dups = rc.dups;
+    put(v.restrict_rows, rc.rows.data(), (size_t)m, s);
+    if (rc.dups) {
+        put(v.dup_next, rc.next(), (size_t)m, s);
+        put(v.dup_head, rc.head(), (size_t)m, s);
     }
     BMX_HIP(hipStreamSynchronize(s));  // (the host vectors go out of scope)
+}
+
+// all n rows in order on the device: the restrict list adjust_shift_variance takes of a side without restriction
+const int32_t* identity_rows(DevBuf<int32_t>& b, int n, hipStream_t s) {
+    std::vector<int32_t> io((size_t)n);
+    for (int i = 0; i < n; ++i) io[i] = i;
+    const int32_t* p = put(b, io.data(), io.size(), s);
+    BMX_HIP(hipStreamSynchronize(s));
+    return p;
 }
 
 }  // namespace
@@ -196,9 +188,7 @@ void mnn_correct_check(const MnnCorrectArgs& a) {
         const bool has = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
         if (!has) continue;
         if (a.n_restrict[b] == 0) throw Error(BMX_ERR_ARG, "no cells remaining in a batch after restriction");
-        for (int i = 0; i < a.n_restrict[b]; ++i)
-            if (a.restrict_idx[b][i] < 1 || a.restrict_idx[b][i] > a.ncells[b])
-                throw Error(BMX_ERR_SUBSET, "subset indices out of range");
+        (void)restrict_chains(a.restrict_idx[b], a.n_restrict[b], a.ncells[b], 1);  // (its range check)
     }
     if (a.subset)
         for (int i = 0; i < a.nsubset; ++i)
@@ -210,21 +200,7 @@ void mnn_correct_check(const MnnCorrectArgs& a) {
             if (a.subset[i] > a.nsubset) throw Error(BMX_ERR_SUBSET, "subscript out of bounds");
     if (a.k < 1) throw Error(BMX_ERR_ARG, "'k' must be positive");
     if (!(a.sigma > 0.0)) throw Error(BMX_ERR_ARG, "'sigma' must be positive");
-    // the tree: post-order code, leaf = batch id, 0 = merge
-    std::vector<int> seen((size_t)a.B, 0);
-    int depth = 0;
-    for (int i = 0; i < a.tree_len; ++i) {
-        const int c = a.tree[i];
-        if (c == 0) {
-            if (depth < 2) throw Error(BMX_ERR_TREE, "merge tree structure should contain two children per node");
-            --depth;
-        } else {
-            if (c < 1 || c > a.B || seen[c - 1]) throw Error(BMX_ERR_TREE, "invalid leaf nodes specified in 'merge.order'");
-            seen[c - 1] = 1;
-            ++depth;
-        }
-    }
-    if (depth != 1 || a.tree_len != 2 * a.B - 1) throw Error(BMX_ERR_TREE, "invalid leaf nodes specified in 'merge.order'");
+    (void)plan_merges(a.tree, a.tree_len, a.B, a.ncells);  // the tree: post-order code, leaf = batch id, 0 = merge
 }
 
 void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
@@ -237,43 +213,19 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
     hipStream_t s = e.stream();
 
     // ---- the tree and the pool's row order (leaves left to right) ----
-    std::vector<TNode> t;
-    std::vector<int> stack, leaf_order;
-    for (int i = 0; i < a.tree_len; ++i) {
-        TNode x;
-        if (a.tree[i] != 0) {
-            x.index = {a.tree[i]};
-            leaf_order.push_back(a.tree[i] - 1);
-        } else {
-            x.right = stack.back();
-            stack.pop_back();
-            x.left = stack.back();
-            stack.pop_back();
-        }
-        t.push_back(std::move(x));
-        stack.push_back((int)t.size() - 1);
-    }
-    const int root = stack.back();
+    const MergePlan plan = plan_merges(a.tree, a.tree_len, B, a.ncells);
+    std::vector<TNode> t(plan.nodes.size());
     std::vector<int64_t> in_off((size_t)B + 1, 0), pool_off((size_t)B, 0);
     for (int b = 0; b < B; ++b) in_off[b + 1] = in_off[b] + a.ncells[b];
     const int64_t N = in_off[B];
     if (N > (int64_t)1 << 30) throw Error(BMX_ERR_ARG, "too many cells for int32 indices");
-    {
-        int64_t r = 0;
-        for (int b : leaf_order) {
-            pool_off[b] = r;
-            r += a.ncells[b];
-        }
-    }
-    for (TNode& x : t) {
-        if (x.index.empty()) continue;
-        const int b = x.index[0] - 1;
-        x.row0 = (int)pool_off[b];
-        x.n = a.ncells[b];
-        const bool has = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
-        x.has_restrict = has;
-        if (has)
-            for (int i = 0; i < a.n_restrict[b]; ++i) x.restrict_rows.push_back(a.restrict_idx[b][i] - 1);
+    for (size_t i = 0; i < t.size(); ++i) {
+        const int b = plan.nodes[i].batch;
+        if (b < 0) continue;
+        pool_off[b] = plan.nodes[i].row0;
+        t[i].index = {b + 1};
+        t[i].has_restrict = a.restrict_idx && a.restrict_idx[b] && a.n_restrict && a.n_restrict[b] >= 0;
+        if (t[i].has_restrict) t[i].restrict_rows = restrict_chains(a.restrict_idx[b], a.n_restrict[b], a.ncells[b], 1).rows;
     }
 
     // ---- .prepare_input_data (R/mnnCorrect.R:398-445) ----
@@ -382,18 +334,19 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
         }
     } ev_guard{ev};
     for (int mdx = 0; mdx < nm; ++mdx) {
-        const int at = next_merge(t, root);
-        TNode& L = t[t[at].left];
-        TNode& R = t[t[at].right];
-        if (R.row0 != L.row0 + L.n) throw Error(BMX_ERR_ARG, "internal: merge of non-adjacent nodes");
+        const int at = plan.merges[mdx];
+        const PlanNode& Lp = plan.nodes[plan.nodes[at].left];
+        const PlanNode& Rp = plan.nodes[plan.nodes[at].right];
+        const TNode& L = t[plan.nodes[at].left];
+        const TNode& R = t[plan.nodes[at].right];
         res.left[mdx] = L.index;
         res.right[mdx] = R.index;
-        pl0[mdx] = L.row0;
-        pr0[mdx] = R.row0;
-        const int nl = L.n, nr = R.n;
+        pl0[mdx] = (int)Lp.row0;
+        pr0[mdx] = (int)Rp.row0;
+        const int nl = (int)Lp.n, nr = (int)Rp.n;
         Node Lv, Rv;
-        make_view(Lv, In, L, Gs, s);
-        make_view(Rv, In, R, Gs, s);
+        make_view(Lv, In, Lp, L, Gs, s);
+        make_view(Rv, In, Rp, R, Gs, s);
         e.d_ = Gs;
         // 1. .restricted_mnn
         BMX_HIP(hipEventRecord(ev[0], s));
@@ -428,14 +381,14 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
         double* dw = dens.reserve((size_t)nr + std::max(1, U));
         double* av = avg.reserve((size_t)std::max(1, U) * Gs);
         double* ci = corr_in.reserve((size_t)nr * Gs);
-        double* Lin = In + (int64_t)L.row0 * Gs;
-        double* Rin = In + (int64_t)R.row0 * Gs;
+        double* Lin = In + Lp.row0 * Gs;
+        double* Rin = In + Rp.row0 * Gs;
         average_correction(s, e.red_ws_, Lin, lrows, Rin, rrows, Gs, e.second_u_.p, U, e.partR_.p, e.cntR_.p, mo.k1, av, false,
                            nullptr, nullptr, nullptr, nullptr, rnext);
         double* co = nullptr;
         double* avo = nullptr;
-        double* Lout = Out + (int64_t)L.row0 * Go;
-        double* Rout = Out + (int64_t)R.row0 * Go;
+        double* Lout = Out + Lp.row0 * Go;
+        double* Rout = Out + Rp.row0 * Go;
         if (!same) {
             avo = avg_out.reserve((size_t)std::max(1, U) * Go);
             average_correction(s, e.red_ws_, Lout, lrows, Rout, rrows, Go, e.second_u_.p, U, e.partR_.p, e.cntR_.p, mo.k1, avo,
@@ -452,21 +405,8 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
         BMX_HIP(hipEventRecord(ev[3], s));
         double* sv = scal.reserve((size_t)nr);
         if (a.var_adj) {
-            const int32_t* r1 = lrows;
-            const int32_t* r2 = rrows;
-            std::vector<int32_t> io;
-            if (!r1) {
-                io.resize((size_t)nl);
-                for (int i = 0; i < nl; ++i) io[i] = i;
-                r1 = put(iota1, io.data(), io.size(), s);
-                BMX_HIP(hipStreamSynchronize(s));
-            }
-            if (!r2) {
-                io.resize((size_t)nr);
-                for (int i = 0; i < nr; ++i) io[i] = i;
-                r2 = put(iota2, io.data(), io.size(), s);
-                BMX_HIP(hipStreamSynchronize(s));
-            }
+            const int32_t* r1 = lrows ? lrows : identity_rows(iota1, nl, s);
+            const int32_t* r2 = rrows ? rrows : identity_rows(iota2, nr, s);
             const AsvPlan plan = adjust_shift_variance_plan(Gs, nr, nLs, nRs, 1);
             double* ws = asv_ws.reserve(plan.main_doubles + plan.extra_doubles);
             adjust_shift_variance_device(s, Lin, Gs, nl, Rin, nr, ci, a.sigma, r1, nLs, r2, nRs, sv, ws, plan, 1);
@@ -512,8 +452,6 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
         }
         // 5. UPDATE: rbind (the slices are adjacent), .combine_restrict (R/fastMNN.R:610-622)
         TNode m;
-        m.row0 = L.row0;
-        m.n = nl + nr;
         m.index = L.index;
         m.index.insert(m.index.end(), R.index.begin(), R.index.end());
         m.has_restrict = L.has_restrict || R.has_restrict;
