@@ -122,7 +122,8 @@ class NoCorrectParam(BatchelorParam):
 def batchCorrect(*batches, batch=None, restrict=None, subset_row=None, correct_all=False, PARAM, names=None, device=0):
     """batchCorrect(..., batch=, restrict=, subset.row=, correct.all=, PARAM=) (R/batchCorrect.R:65-98): the function PARAM
     stands for, called with these arguments and PARAM's own; returns what it returns.  NoCorrectParam drops `restrict`
-    (:96), and noCorrect runs on the host, so `device` is dropped with it."""
+    (:96), and noCorrect runs on the host, so `device` is dropped with it.  RegressParam(d=50, deferred=True, residuals=False)
+    returns the PCs of the residuals without forming them (regressBatches)."""
     if not isinstance(PARAM, (FastMnnParam, ClassicMnnParam, RescaleParam, RegressParam, NoCorrectParam)):
         raise TypeError("'PARAM' must be a FastMnnParam, ClassicMnnParam, RescaleParam, RegressParam or NoCorrectParam")
     combined = dict(batch=batch, subset_row=subset_row, correct_all=correct_all, names=names)
@@ -204,7 +205,8 @@ def quickCorrect(*batches, batch=None, restrict=None, correct_all=True, PARAM=No
     Sparse counts whose zero stays a zero come out of multiBatchNorm as CSC and go into the sparse variance handle and
     into fastMNN or mnnCorrect (ClassicMnnParam) as they are; where multiBatchNorm returns dense values
     (pseudo_count != 1) the dense path is taken.  What rescaleBatches and regressBatches refuse of sparse input, they
-    refuse here."""
+    refuse here.  With PARAM=RegressParam(d=50, deferred=True, residuals=False) the PCs over the chosen rows come from the
+    device-resident log-values and no residual of any gene is formed or downloaded (regressBatches)."""
     PARAM = FastMnnParam() if PARAM is None else PARAM
     multi_norm_args = dict(multi_norm_args or {})
     model_var_args = dict(model_var_args or {})

@@ -10,12 +10,20 @@ reference's tests) is, with X genes x cells, D cells x p the design and R the re
 drop = the columns of D not named in `keep`.  Without a design D has one indicator column per batch, coef is the batch
 means and no product is formed.  With a design the host factors D[R, :] (QR) and the device forms both skinny products.
 
+regressBatches(d=): the PCs of the residuals (multiBatchPCA over the batches).  By default the residuals come back to the
+host, are split by batch and go to multiBatchPCA.  With deferred=True (the reference's ResidualMatrix with deferred=TRUE)
+they are never formed: the residual of batch b is x_b - F E_b^T of rank <= 65 away from the resident x_b, so the subspace
+iteration applies its two products to x_b and takes the low-rank term off the two skinny results
+(bmx_residual_pca_*).  residuals=False then skips the second pass and its download altogether.
+
 Out of scope (a clear error): sparse and SingleCellExperiment inputs, designs of more than 64 columns, a design whose
-restricted rows are not of full column rank (R's pivoted QR would drop columns instead), deferred / BSPARAM.
+restricted rows are not of full column rank (R's pivoted QR would drop columns instead), BSPARAM, deferred=True for one
+object with both `design` and `batch` (the resident batch is then the whole object, not the PCA's batches).
 """
 from __future__ import annotations
 
 import ctypes
+import time
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -36,13 +44,14 @@ STAGES = ("upload", "first_pass", "statistics", "second_pass_kernels", "second_p
 @dataclass
 class LinearCorrectResult:
     """What rescaleBatches() / regressBatches() return."""
-    corrected: np.ndarray                      # genes x cells (column-major), cells in the caller's order
+    corrected: Optional[np.ndarray]            # genes x cells (column-major), cells in the caller's order; None: residuals=False
     batch: np.ndarray                          # batch id (1-based) or name per cell
     averages: Optional[np.ndarray] = None      # rescaleBatches: genes x batches, mean unlogged value of the restricted cells
     reference: Optional[np.ndarray] = None     # rescaleBatches: genes, the minimum of `averages` over the batches
     coefficients: Optional[np.ndarray] = None  # regressBatches: genes x p (default design: the batch means)
     pcs: Optional[np.ndarray] = None           # regressBatches(d=): cells x d
-    stats: Optional[dict] = None               # "stage_ms": see STAGES
+    pca: Optional[dict] = None                 # regressBatches(d=, deferred=True): rotation, centers, d, iters_used, residual, path
+    stats: Optional[dict] = None               # "stage_ms": see STAGES; deferred PCA: "pca_fit_ms"
 
 
 def _as_matrices(batches, what):
@@ -146,6 +155,61 @@ class _LinearHandle(ResidentHandle):
         return out
 
 
+class _ResidualPCA:
+    """bmx_residual_pca_t: the PCA of the residuals over the first n_pca_rows rows of a _LinearHandle whose batches are all
+    resident.  The wrapper keeps its _LinearHandle alive; close() this one first."""
+
+    def __init__(self, linear, n_pca_rows):
+        self.linear, self.n_pca, self.d = linear, int(n_pca_rows), 0
+        self._h = ctypes.c_void_p()
+        lib = _lib.lib()
+        lib.bmx_residual_pca_destroy.argtypes = [ctypes.c_void_p]
+        lib.bmx_residual_pca_destroy.restype = None
+        _lib.check(lib.bmx_residual_pca_create(ctypes.c_int32(self.n_pca), linear._h, ctypes.byref(self._h)))
+
+    def fit(self, design, w, keep, d, tol, max_iters, iters=None, weights=None):
+        """bmx_residual_pca_fit: (coefficients, multiBatchPCA's record of the residuals' first n_pca_rows rows).  iters=N:
+        the fixed-count form (N plain subspace steps, no test).  A run that misses tol raises, as DevicePCA.fit."""
+        nS, d, lin = self.n_pca, int(d), self.linear
+        centers, rotation, sdev = np.zeros(nS), np.zeros((nS, d), order="F"), np.zeros(d)
+        used, res = ctypes.c_int32(0), ctypes.c_double(0.0)
+        wts = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if design is None:
+            coef = np.empty((lin.G, len(lin.ncells)), dtype=np.float64, order="F")
+            dargs = (None, ctypes.c_int32(0), None, None, ctypes.c_int32(0))
+        else:
+            design, w = _lib.as_f(design), _lib.as_f(w)
+            keep = np.zeros(0, dtype=np.int32) if keep is None else np.ascontiguousarray(keep, dtype=np.int32)
+            coef = np.empty((lin.G, design.shape[1]), dtype=np.float64, order="F")
+            dargs = (_lib.f64p(design), ctypes.c_int32(design.shape[1]), _lib.f64p(w),
+                     _lib.i32p(keep) if keep.size else None, ctypes.c_int32(int(keep.size)))
+        fixed = iters is not None
+        self.d = d
+        _lib.check(_lib.lib().bmx_residual_pca_fit(
+            self._h, *dargs, None if wts is None else _lib.f64p(wts), ctypes.c_int32(d),
+            ctypes.c_double(0.0 if fixed else float(tol)), ctypes.c_int32(int(iters if fixed else max_iters)),
+            _lib.f64p(coef), _lib.f64p(centers), _lib.f64p(rotation), _lib.f64p(sdev), ctypes.byref(used),
+            ctypes.byref(res)))
+        return coef, {"rotation": np.ascontiguousarray(rotation), "centers": centers, "d": sdev,
+                      "iters_used": int(used.value), "residual": float("nan") if fixed else float(res.value)}
+
+    def project(self, b):
+        out = np.zeros((self.linear.ncells[b], self.d), order="F")
+        _lib.check(_lib.lib().bmx_residual_pca_project(self._h, ctypes.c_int32(int(b)), _lib.f64p(out)))
+        return np.ascontiguousarray(out)
+
+    def close(self):
+        if self._h:
+            _lib.lib().bmx_residual_pca_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _rows(mats, sub):
     return mats if sub is None else [m[sub - 1] for m in mats]
 
@@ -214,13 +278,34 @@ def design_weights(design, restricted_rows):
 
 
 def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, subset_row=None, correct_all=False,
-                   d=None, names=None, device=0) -> LinearCorrectResult:
+                   d=None, names=None, device=0, deferred=False, residuals=True, pca_tol=1e-9, pca_maxit=500,
+                   pca_iters=None) -> LinearCorrectResult:
     """regressBatches(..., batch=, design=, keep=, restrict=, subset.row=, correct.all=, d=) (R/regressBatches.R:93-158):
     the residuals of a per-gene linear model fitted on the restricted cells, for every cell.  Without a design the model
     has one blocking term per batch (each batch is centred on the mean of its restricted cells).  `design` is cells x p
     over all cells in the order given (p <= 64), `keep` names 1-based columns of it that are not regressed out.  A single
     object with a `design` but no `batch` is taken as one batch (:124-128).  `d`: also return the first d PCs of the
-    residuals (multiBatchPCA over the batches)."""
+    residuals (multiBatchPCA over the batches).
+
+    deferred=True (with `d`): the PCs come from the batches resident on the device, the residuals being their data less a
+    term of rank <= 65 that is never written (module docstring); `pcs` is in the caller's cell order and `pca` holds
+    {"rotation", "centers", "d", "iters_used", "residual", "path": "device-deferred"}, over the genes of subset_row where
+    correct_all kept all of them.  pca_tol / pca_maxit / pca_iters are multiBatchPCA's tol / max_iters / iters.  The PCA's
+    batches are the resident ones: the objects, the parts of one object divided by `batch`, or one object with a `design`
+    and no `batch`; one object with both is a ValueError.  A shape the device PCA does not take
+    (multi_batch_pca.device_pca_takes) goes the default way and `pca["path"]` says so.  residuals=False (only with
+    deferred=True and `d`): the second pass and its download are skipped and `corrected` is None."""
+    deferred, residuals = bool(deferred), bool(residuals)
+    if deferred and d is None:
+        raise ValueError("'deferred=True' needs 'd': it is the PCA of the residuals that is deferred")
+    if not residuals and not deferred:
+        raise ValueError("'residuals=False' needs 'deferred=True' and 'd': without them the PCs are taken from the residuals")
+    if deferred:
+        pca_tol = float(pca_tol)
+        if not (np.isfinite(pca_tol) and pca_tol > 0):
+            raise ValueError("'pca_tol' must be positive and finite")
+        if int(pca_maxit) < 1 or (pca_iters is not None and int(pca_iters) < 1):
+            raise ValueError("'pca_maxit' and 'pca_iters' must be positive")
     mats = _as_matrices(batches, "regressBatches")
     if len(mats) == 0:
         raise ValueError("at least two batches must be specified")  # R/regressBatches.R:133
@@ -265,6 +350,10 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
         raise ValueError("'subset_row' selects no genes")
     if d is not None and int(d) < 1:
         raise ValueError("'d' must be positive")
+    if deferred and design is not None and len(mats) == 1 and batch is not None:
+        raise ValueError("'deferred=True' takes the batches resident on the device as the PCA's batches: one object with "
+                         "both 'design' (or 'keep') and 'batch' stays whole there; pass the batches as separate objects "
+                         "or leave 'deferred' off")
 
     if design is None and len(mats) == 1:
         mats, res, labels_out, reorder = _divide(mats[0], labels, res[0])
@@ -279,36 +368,91 @@ def regressBatches(*batches, batch=None, design=None, keep=None, restrict=None, 
             rows = np.concatenate([(np.arange(n) if r is None else np.sort(r.astype(np.int64) - 1)) + o
                                    for r, n, o in zip(res, ncells, offs)])
         w = design_weights(design, rows)
-    mats = _rows(mats, sub)
+    # deferred with correct_all: the rows go up as [subset_row; the others], as multiBatchPCA uploads them, so that the PCA
+    # rows are a prefix; every gene is independent of the others, so its bits do not depend on where it stands
+    order = None
+    n_pca = G if sub is None else sub.size
+    if deferred and correct_all:
+        pca_sub = subset_index(subset_row, G)
+        if pca_sub is not None:
+            if pca_sub.size == 0:
+                raise ValueError("'subset_row' selects no genes")
+            first = pca_sub.astype(np.int64) - 1
+            rest = np.ones(G, dtype=bool)
+            rest[first] = False
+            order, n_pca = np.concatenate([first, np.flatnonzero(rest)]), first.size
+    mats = _rows(mats, sub) if order is None else [m[order] for m in mats]
     _lib.require_gpu()
     h = _LinearHandle(mats[0].shape[0], device)
+    out = pca = pcs = fit_ms = None
     try:
         if OVERLAP and design is None:
             h.expect(1)
         for m, r in zip(mats, res):
             h.add_batch(m, r)
-        out, coef = h.regress(design, w, keep)
+        if deferred:
+            from .multi_batch_pca import device_pca_takes
+            why = None if device_pca_takes(n_pca, sum(h.ncells), int(d)) else \
+                "fewer genes / cells than the device block, or d > 120"
+            if why is None:
+                rp = _ResidualPCA(h, n_pca)
+                try:
+                    t0 = time.perf_counter()
+                    coef, pca = rp.fit(design, w, keep, int(d), pca_tol, pca_maxit, pca_iters)
+                    fit_ms = (time.perf_counter() - t0) * 1e3
+                    pca["path"] = "device-deferred"
+                    pcs = np.concatenate([rp.project(b) for b in range(len(mats))], axis=0)
+                except _lib.BatchelorMI355XError as exc:
+                    if "rank below the subspace width" not in str(exc):
+                        raise
+                    why = "residuals of rank below the device block"
+                finally:
+                    rp.close()
+        if residuals or pca is None:
+            out, coef = h.regress(design, w, keep)
         stage_ms = h.stage_ms()
     finally:
         h.close()
+    if deferred and pca is None:  # today's route, on the PCA rows of the residuals as uploaded
+        pcs, pca = _residual_pcs(out[:n_pca], labels_out, int(d), None, device, tol=pca_tol, max_iters=pca_maxit,
+                                 iters=pca_iters)
+        pca["path"] = "residuals through the host (" + why + "), then " + pca["path"]
+        if not residuals:
+            out = None
+    if order is not None:  # back to the caller's rows (a row named twice went up twice, with the same result)
+        back = np.empty((G, coef.shape[1]), order="F")
+        back[order] = coef
+        coef = back
+        if out is not None:
+            back = np.empty((G, out.shape[1]), order="F")
+            back[order] = out
+            out = back
     if reorder is not None:
-        out = np.asfortranarray(out[:, reorder - 1])
+        out = None if out is None else np.asfortranarray(out[:, reorder - 1])
+        if pcs is not None:
+            pcs = pcs[reorder - 1]
         labels_out = labels_out[reorder - 1]
     result = LinearCorrectResult(corrected=out, batch=labels_out, coefficients=coef, stats={"stage_ms": stage_ms})
-    if d is not None:
-        result.pcs = _residual_pcs(out, labels_out, int(d), subset_index(subset_row, G) if correct_all else None, device)
+    if deferred:
+        result.pcs, result.pca = pcs, pca
+        if fit_ms is not None:
+            result.stats["pca_fit_ms"] = fit_ms  # host wall time of bmx_residual_pca_fit (coefficients and PCA)
+    elif d is not None:
+        result.pcs = _residual_pcs(out, labels_out, int(d), subset_index(subset_row, G) if correct_all else None, device)[0]
     return result
 
 
-def _residual_pcs(corrected, labels, d, sub, device):
+def _residual_pcs(corrected, labels, d, sub, device, **fit):
     """.multi_pca_single (R/multiBatchPCA.R:470-508) on the residuals: multiBatchPCA over the batches (the genes of
-    subset.row when correct.all kept all of them), the cells' coordinates put back in the caller's order."""
+    subset.row when correct.all kept all of them), the cells' coordinates put back in the order of `labels`; and
+    multiBatchPCA's record without its "pcs".  fit: multiBatchPCA's tol / max_iters / iters."""
     from .multi_batch_pca import multiBatchPCA
     x = corrected if sub is None else corrected[sub - 1]
     levels = sorted(set(labels.tolist()))
     where = [np.flatnonzero(labels == lv) for lv in levels]
-    pca = multiBatchPCA(*[x[:, idx] for idx in where], d=d, device=device)
-    pcs = np.empty((x.shape[1], pca["pcs"][0].shape[1]))
-    for idx, pc in zip(where, pca["pcs"]):
+    pca = multiBatchPCA(*[x[:, idx] for idx in where], d=d, device=device, **fit)
+    parts = pca.pop("pcs")
+    pcs = np.empty((x.shape[1], parts[0].shape[1]))
+    for idx, pc in zip(where, parts):
         pcs[idx] = pc
-    return pcs
+    return pcs, pca

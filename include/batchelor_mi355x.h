@@ -611,6 +611,9 @@ int32_t bmx_linear_rescale(bmx_linear_t* h, double log_base, double pseudo_count
  * outs[b] = x - coef[, dropped] %*% t(design[cells of b, dropped]); coef_out [n_genes x p] (nullable). */
 int32_t bmx_linear_regress(bmx_linear_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
                            int32_t n_keep, double* const* outs, double* coef_out);
+/* The checks of bmx_residual_pca_create / _fit's PCA arguments on their own (no device), as bmx_norm_check_*. */
+int32_t bmx_linear_check_pca(int32_t n_genes, int32_t n_pca_rows, int32_t d, double tol, int32_t max_applies,
+                             const double* weights, int32_t n_batches);
 /* The batches as they were uploaded, back into outs[b] (n_genes x n_b) through the download ring with no kernel in
  * between: the least that moving a call's bytes in and out costs (scripts/linear_correct_probe.py measures against it). */
 int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs);
@@ -618,6 +621,33 @@ int32_t bmx_linear_fetch(bmx_linear_t* h, double* const* outs);
  * time of out[1] the first pass (chunk sums / the product with w), out[2] the statistics kernels, out[3] the second pass's
  * kernels; out[4] = host wall time of the second pass with its downloads. */
 int32_t bmx_linear_stage_ms(const bmx_linear_t* h, double* out5);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * regressBatches(d=, deferred=TRUE) (R/regressBatches.R:148-155): the PCA of the residuals, which are never formed.
+ * The handle borrows a bmx_linear_t whose batches have all arrived, as bmx_pca_genes_t borrows a fitted bmx_pca_t: the
+ * PCA runs over the first n_pca_rows rows of its resident batches, which are the PCA's batches.  The bmx_linear_t must
+ * outlive this handle; a batch begun on it since makes every later call here an error.
+ * bmx_residual_pca_fit fits the coefficients exactly as bmx_linear_regress fits them (design, p, w, keep, n_keep and
+ * coef_out as there; the same bits), then runs multiBatchPCA (R/multiBatchPCA.R:211-322) on the residuals: weights
+ * [n_batches] (NULL: equal weights), the grand centre the weighted mean of every batch's mean residual over ALL its cells.
+ * The residual of a batch is its data minus a term of rank <= 65, so the subspace iteration of bmx_pca_fit_tol applies
+ * its two products to the resident data and corrects the two skinny results.  1 <= d <= 120; tol > 0: until the relative
+ * Ritz residual is <= tol, at most max_applies applications of the operator (an error when they do not reach it, after
+ * the results have been written); tol <= 0: exactly max_applies plain steps.  centers_out [n_pca_rows], rotation_out
+ * [n_pca_rows x d] column-major, sdev_out [d], iters_used, residual_out: nullable.  bmx_linear_rescale / _regress on the
+ * bmx_linear_t work as before, whether or not a PCA was fitted.  The same input gives the same bits on every run and for
+ * every blocking of the upload (fixed-order sums, no floating-point atomics).
+ * bmx_residual_pca_project: crossprod(residuals of batch `batch` (0-based) - centers, rotation) of the fit: out [n_b x d]
+ * column-major.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct bmx_residual_pca bmx_residual_pca_t;
+int32_t bmx_residual_pca_create(int32_t n_pca_rows, bmx_linear_t* loaded, bmx_residual_pca_t** out);
+void bmx_residual_pca_destroy(bmx_residual_pca_t* h);
+int32_t bmx_residual_pca_fit(bmx_residual_pca_t* h, const double* design, int32_t p, const double* w, const int32_t* keep,
+                             int32_t n_keep, const double* weights, int32_t d, double tol, int32_t max_applies,
+                             double* coef_out, double* centers_out, double* rotation_out, double* sdev_out,
+                             int32_t* iters_used, double* residual_out);
+int32_t bmx_residual_pca_project(bmx_residual_pca_t* h, int32_t batch, double* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * multiBatchNorm() (R/multiBatchNorm.R:100-280): size factors rescaled between batches, then log-normalized values.
