@@ -108,7 +108,9 @@ bmx_params_t read_params(const bmx_params_t* params) {
     bmx_params_t defaults;
     std::memset(&defaults, 0, sizeof(defaults));
     defaults.sigma = 0.1;
-    return read_versioned(params, offsetof(bmx_params_t, auto_merge) + sizeof(int32_t), "bmx_params_t", defaults);
+    const bmx_params_t p = read_versioned(params, offsetof(bmx_params_t, auto_merge) + sizeof(int32_t), "bmx_params_t", defaults);
+    if (p.var_adj_strict != 0 && p.var_adj == 0) throw bmx::Error(BMX_ERR_ARG, "bmx_params_t.var_adj_strict needs var_adj");
+    return p;
 }
 
 template <class T>
@@ -212,6 +214,7 @@ int32_t bmx_dev_set(const char* name, int32_t value) {
     else if (n == "refine_wave") k.refine_wave = value;
     else if (n == "asv_wide") k.asv_wide = value;
     else if (n == "asv_chunk") k.asv_chunk = value;
+    else if (n == "asv_strict") k.asv_strict = value;
     else if (n == "reset") k = bmx::DevKnobs();
     else {
         g_last_error = "bmx_dev_set: unknown knob '" + n + "'";
@@ -466,6 +469,7 @@ static int32_t mnn_correct_entry(int32_t nbatches, int32_t n_genes, const int64_
         std::memset(&zeros, 0, sizeof(zeros));
         const bmx_mnn_params_t p = read_versioned(params, offsetof(bmx_mnn_params_t, tree_len) + sizeof(int32_t),
                                                   "bmx_mnn_params_t", zeros);
+        if (p.var_adj_strict != 0 && p.var_adj == 0) throw bmx::Error(BMX_ERR_ARG, "bmx_mnn_params_t.var_adj_strict needs var_adj");
         if (nbatches < 2) throw bmx::Error(BMX_ERR_ARG, "at least two batches must be specified");
         if (!data || !ncells || (sparse && (!indptr || !indices))) throw bmx::Error(BMX_ERR_ARG, "null batch arrays");
         bmx::MnnCorrectArgs a;
@@ -483,6 +487,7 @@ static int32_t mnn_correct_entry(int32_t nbatches, int32_t n_genes, const int64_
         a.cos_in = p.cos_norm_in;
         a.cos_out = p.cos_norm_out;
         a.var_adj = p.var_adj;
+        a.var_adj_strict = p.var_adj_strict;
         a.correct_all = p.correct_all;
         a.svd_dim = p.svd_dim;
         a.auto_merge = p.auto_merge;
@@ -547,6 +552,13 @@ int32_t bmx_mnn_result_stage_ms(const bmx_mnn_result_t* r, double* out5) {
     return guarded([&] {
         if (!r || !out5) throw bmx::Error(BMX_ERR_ARG, "null argument");
         for (int i = 0; i < 5; ++i) out5[i] = r->r.stage_ms[i];
+    });
+}
+
+int32_t bmx_mnn_result_strict_cells(const bmx_mnn_result_t* r, int64_t* out) {
+    return guarded([&] {
+        if (!r || !out) throw bmx::Error(BMX_ERR_ARG, "null argument");
+        for (size_t i = 0; i < r->r.strict_cells.size(); ++i) out[i] = r->r.strict_cells[i];
     });
 }
 
@@ -705,11 +717,13 @@ int32_t bmx_smooth_gaussian_kernel(const double* averaged, int32_t g, int32_t U,
     });
 }
 
-int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, const double* data2, int32_t g2,
-                                  int32_t n2, const double* vect, int32_t vrow, int32_t vcol, double sigma2,
-                                  const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
-                                  double* out) {
+// bmx_adjust_shift_variance and bmx_adjust_shift_variance_ex: the legacy native, strict = 0 and counts = null for the former
+static int32_t adjust_shift_variance_entry(const double* data1, int32_t g1, int32_t n1, const double* data2, int32_t g2,
+                                           int32_t n2, const double* vect, int32_t vrow, int32_t vcol, double sigma2,
+                                           const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
+                                           double* out, int32_t strict, int64_t* counts) {
     return guarded([&] {
+        if (counts) counts[0] = counts[1] = counts[2] = counts[3] = -1;
         if (g1 != g2 || g1 != vcol)  // src/adjust_shift_variance.cpp:33-36
             throw bmx::Error(BMX_ERR_DIM_GENES, "number of genes do not match up between matrices");
         if (n2 != vrow)  // :38-41
@@ -734,14 +748,31 @@ int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, c
         const int32_t* q2 = upload(dr2, restrict2, (size_t)nr2, s);
         double* po = dO.reserve(n2);
         const bmx::AsvPlan plan = bmx::adjust_shift_variance_plan(g, n2, nr1, nr2, 0);
-        double* pw = dW.reserve(plan.main_doubles + plan.extra_doubles);
+        double* pw = dW.reserve(bmx::adjust_shift_variance_scratch(plan, g, n2, nr1, nr2, strict));
         NativeTimer timer(s);
-        bmx::adjust_shift_variance_device(s, p1, g, n1, p2, n2, pv, sigma2, q1, nr1, q2, nr2, po, pw, plan);
+        bmx::adjust_shift_variance_device(s, p1, g, n1, p2, n2, pv, sigma2, q1, nr1, q2, nr2, po, pw, plan, 0, 0, -1, strict,
+                                          counts);
         timer.stop();
         BMX_HIP(hipMemcpyAsync(out, po, (size_t)n2 * sizeof(double), hipMemcpyDeviceToHost, s));
         BMX_HIP(hipStreamSynchronize(s));
         timer.read();
     });
+}
+
+int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, const double* data2, int32_t g2,
+                                  int32_t n2, const double* vect, int32_t vrow, int32_t vcol, double sigma2,
+                                  const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
+                                  double* out) {
+    return adjust_shift_variance_entry(data1, g1, n1, data2, g2, n2, vect, vrow, vcol, sigma2, restrict1, nr1, restrict2, nr2,
+                                       out, 0, nullptr);
+}
+
+int32_t bmx_adjust_shift_variance_ex(const double* data1, int32_t g1, int32_t n1, const double* data2, int32_t g2,
+                                     int32_t n2, const double* vect, int32_t vrow, int32_t vcol, double sigma2,
+                                     const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
+                                     double* out, int32_t strict, int64_t* counts) {
+    return adjust_shift_variance_entry(data1, g1, n1, data2, g2, n2, vect, vrow, vcol, sigma2, restrict1, nr1, restrict2, nr2,
+                                       out, strict, counts);
 }
 
 int32_t bmx_adjust_shift_variance_form(int32_t n2, int32_t nr1, int32_t nr2) {
@@ -917,6 +948,13 @@ int32_t bmx_engine_var_adj_tally(bmx_engine_t* e, int32_t merge, int64_t* out3) 
     return guarded([&] {
         if (!out3) throw bmx::Error(BMX_ERR_ARG, "null output");
         e->impl->var_adj_tally(merge, out3);
+    });
+}
+
+int32_t bmx_engine_var_adj_strict_cells(bmx_engine_t* e, int32_t merge, int64_t* cells) {
+    return guarded([&] {
+        if (!cells) throw bmx::Error(BMX_ERR_ARG, "null output");
+        e->impl->var_adj_strict_cells(merge, cells);
     });
 }
 

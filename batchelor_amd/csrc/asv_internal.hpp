@@ -90,6 +90,16 @@ void launch_asv_literal(hipStream_t stream, const double* data1, int g, const do
                         int cell_end);
 void launch_asv_tile(hipStream_t stream, const double* data1, int g, const double* data2, int n2, const double* vect,
                      int vect_row_major, double sigma2, const int32_t* restrict1, int nr1, const int32_t* restrict2, int nr2,
-                     double* out, double* ws_pairs, const AsvPlan& pl, int cell_begin, int cell_end);
+                     double* out, double* ws_pairs, const AsvPlan& pl, int cell_begin, int cell_end,
+                     unsigned char* modes = nullptr);  // modes: strict mode's per-call record of the cells' ways, [n2], or null
+// Strict mode (asv_literal.hip): the record -> the ascending list of the mode-2 cells of [cell_begin, cell_end) and
+// count[0..1] = {its length, cells re-run literally}; then the wide form over list[0, count), sp.chunk entries at a time,
+// writing out[cell] over the histogram value (count: what the host has read back; 0 launches nothing).
+void launch_asv_strict_compact(hipStream_t stream, const unsigned char* modes, int cell_begin, int cell_end, int32_t* list,
+                               unsigned int* count);
+void launch_asv_strict_pass(hipStream_t stream, const double* data1, int g, const double* data2, const double* vect,
+                            int64_t vs_cell, int64_t vs_x, double sigma2, const int32_t* restrict1, int nr1,
+                            const int32_t* restrict2, int nr2, double* out, double* ws_wide, const AsvStrictPlan& sp,
+                            const int32_t* list, int count);
 
 }  // namespace bmx

@@ -157,14 +157,16 @@ __global__ __launch_bounds__(T) void asv_exact_kernel(const double* __restrict__
 //                   into the cell's scratch in asv_exact_kernel's layout (AsvLiteralLayout);
 //   asv_wide_cells: one workgroup per cell, asv_cell_phase on those values.
 // scratch: AsvLiteralLayout per cell of a chunk and its wide tail behind the chunk's cells.
+// With a cell list (strict mode: the mode-2 cells of a tiled call) cell i of the chunk is list[c0 + i] instead of c0 + i; c0
+// and nc then count entries of the list, and c0 + nc never passes the count the host has read.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void asv_wide_prep(const double* __restrict__ data2, int g, const double* __restrict__ vect,
                                                      int64_t vs_cell, int64_t vs_x, int c0, int nc,
-                                                     double* __restrict__ gradn, double* __restrict__ l2o,
-                                                     double* __restrict__ projo) {
+                                                     const int32_t* __restrict__ list, double* __restrict__ gradn,
+                                                     double* __restrict__ l2o, double* __restrict__ projo) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nc) return;
-    const int64_t cell = (int64_t)c0 + i;
+    const int64_t cell = list ? (int64_t)list[c0 + i] : (int64_t)c0 + i;
     double l2 = 0.0;
     for (int x = 0; x < g; ++x) {
         const double v = vect[(int64_t)x * vs_x + cell * vs_cell];
@@ -185,8 +187,8 @@ __global__ __launch_bounds__(256) void asv_wide_prep(const double* __restrict__ 
 __global__ __launch_bounds__(256) void asv_wide_pairs(const double* __restrict__ data1, const double* __restrict__ data2, int g,
                                                       const int32_t* __restrict__ r1, int nr1, const int32_t* __restrict__ r2,
                                                       int nr2, int npad, double sigma2, int c0, int nc, int sb0,
-                                                      const double* __restrict__ gradn, const double* __restrict__ projo,
-                                                      double* __restrict__ scratch) {
+                                                      const int32_t* __restrict__ list, const double* __restrict__ gradn,
+                                                      const double* __restrict__ projo, double* __restrict__ scratch) {
     __shared__ double sO[AW_KC][AW_S];   // streamed cells: [gene][cell]
     __shared__ double sG[AW_KC][AW_C];   // unit correction vectors of the tile's cells
     __shared__ double sX[AW_KC][AW_C];   // the tile's cells
@@ -216,7 +218,12 @@ __global__ __launch_bounds__(256) void asv_wide_pairs(const double* __restrict__
         }
         for (int e = tid; e < AW_C * AW_KC; e += 256) {
             const int i = e / AW_KC, x = e % AW_KC;
-            sX[x][i] = (x < kx && i0 + i < nc) ? data2[((int64_t)c0 + i0 + i) * g + x0 + x] : 0.0;
+            double v = 0.0;
+            if (x < kx && i0 + i < nc) {  // (entry c0 + i0 + i of the list lies below the count: i0 + i < nc)
+                const int64_t cell = list ? (int64_t)list[c0 + i0 + i] : (int64_t)c0 + i0 + i;
+                v = data2[cell * g + x0 + x];
+            }
+            sX[x][i] = v;
         }
         __syncthreads();
         return kx;
@@ -263,14 +270,15 @@ __global__ __launch_bounds__(256) void asv_wide_pairs(const double* __restrict__
             base[L.kw + s] = lw;
         } else {
             const int s2 = s - nr1;
-            const bool same = r2[s2] == c0 + i;  // the cell itself: weight exp(0), always counted (:78-84)
+            const bool same = r2[s2] == (list ? list[c0 + i] : c0 + i);  // the cell itself: weight exp(0), always counted (:78-84)
             base[L.lw2 + s2] = same ? 0.0 : lw;
             base[L.add2 + s2] = (same || !(pr[q] > projo[i])) ? 1.0 : 0.0;
         }
     }
 }
 
-__global__ __launch_bounds__(T) void asv_wide_cells(int nr1, int nr2, int npad, int c0, int nc, const double* __restrict__ l2o,
+__global__ __launch_bounds__(T) void asv_wide_cells(int nr1, int nr2, int npad, int c0, int nc,
+                                                    const int32_t* __restrict__ list, const double* __restrict__ l2o,
                                                     const double* __restrict__ projo, double* __restrict__ scratch,
                                                     double* __restrict__ out) {
     __shared__ double sh3[3];
@@ -284,11 +292,72 @@ __global__ __launch_bounds__(T) void asv_wide_cells(int nr1, int nr2, int npad, 
             kw[o] = __builtin_inf();
         }
         __syncthreads();
-        asv_cell_phase(base + L.lw2, base + L.add2, kp, kw, nr1, nr2, npad, projo[i], l2o[i], out + c0 + i, sh3);
+        asv_cell_phase(base + L.lw2, base + L.add2, kp, kw, nr1, nr2, npad, projo[i], l2o[i],
+                       out + (list ? list[c0 + i] : c0 + i), sh3);
+    }
+}
+
+// Strict mode: the record of a tiled call's ways (modes, one byte per cell) -> the ascending list of the mode-2 cells of
+// [cell_begin, cell_end) and its length in count[0]; count[1]: the cells re-run literally.  One workgroup: every thread
+// takes a contiguous run of the cells, an exclusive scan over the threads' counts places the runs -- the order is the
+// cells' own, whatever the timing (no atomic append).
+__global__ __launch_bounds__(T) void asv_strict_compact(const unsigned char* __restrict__ modes, int cell_begin, int cell_end,
+                                                        int32_t* __restrict__ list, unsigned int* __restrict__ count) {
+    __shared__ int sc[T];
+    __shared__ int s1[T];
+    const int tid = threadIdx.x;
+    const int n = cell_end - cell_begin;
+    const int per = (n + T - 1) / T;
+    const int b = cell_begin + min(n, tid * per), e = cell_begin + min(n, (tid + 1) * per);
+    int n2 = 0, n1 = 0;
+    for (int c = b; c < e; ++c) {
+        const unsigned char m = modes[c];
+        n2 += m == 2;
+        n1 += m == 1;
+    }
+    sc[tid] = n2;
+    const int lits = block_sum(n1, s1);  // (ends in a barrier: sc is written)
+    for (int o = 1; o < T; o <<= 1) {    // inclusive scan
+        const int v = tid >= o ? sc[tid - o] : 0;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    int at = sc[tid] - n2;
+    for (int c = b; c < e; ++c)
+        if (modes[c] == 2) list[at++] = c;
+    if (tid == T - 1) {
+        count[0] = (unsigned int)sc[tid];
+        count[1] = (unsigned int)lits;
     }
 }
 
 }  // namespace
+
+// the wide form over the cells [c_begin, c_end) -- or, with a list, over its entries [c_begin, c_end) -- nc_max at a time
+static void launch_wide_chunks(hipStream_t stream, const double* data1, int g, const double* data2, const double* vect,
+                               int64_t vs_cell, int64_t vs_x, double sigma2, const int32_t* restrict1, int nr1,
+                               const int32_t* restrict2, int nr2, double* out, double* ws, int nc_max, int npad, int blocks,
+                               const int32_t* list, int c_begin, int c_end) {
+    const AsvLiteralLayout L(nr2, npad);
+    double* gradn = ws + L.wide_gradn(nc_max);  // [g][nc]
+    double* l2o = ws + L.wide_l2(g, nc_max);
+    double* projo = ws + L.wide_proj(g, nc_max);
+    for (int c0 = c_begin; c0 < c_end; c0 += nc_max) {
+        const int nc = std::min(nc_max, c_end - c0);
+        hipLaunchKernelGGL(asv_wide_prep, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, stream, data2, g, vect, vs_cell, vs_x, c0,
+                           nc, list, gradn, l2o, projo);
+        const int S = nr1 + nr2;
+        const int sblocks = cdiv(S, AW_S);
+        for (int sb0 = 0; sb0 < sblocks; sb0 += 65535)
+            hipLaunchKernelGGL(asv_wide_pairs, dim3((unsigned)cdiv(nc, AW_C), (unsigned)std::min(65535, sblocks - sb0)), dim3(256),
+                               0, stream, data1, data2, g, restrict1, nr1, restrict2, nr2, npad, sigma2, c0, nc, sb0, list,
+                               (const double*)gradn, (const double*)projo, ws);
+        hipLaunchKernelGGL(asv_wide_cells, dim3((unsigned)std::min(nc, blocks)), dim3(T), 0, stream, nr1, nr2, npad, c0, nc, list,
+                           (const double*)l2o, (const double*)projo, ws, out);
+        BMX_LAUNCH_CHECK();
+    }
+}
 
 void launch_asv_literal(hipStream_t stream, const double* data1, int g, const double* data2, int n2, const double* vect,
                         int64_t vs_cell, int64_t vs_x, double sigma2, const int32_t* restrict1, int nr1,
@@ -296,30 +365,28 @@ void launch_asv_literal(hipStream_t stream, const double* data1, int g, const do
                         int cell_end) {
     const int blocks = pl.blocks;
     if (pl.wide) {
-        const int nc_max = pl.chunk;
-        const AsvLiteralLayout L(nr2, pl.npad);
-        double* gradn = ws_pairs + L.wide_gradn(nc_max);  // [g][nc]
-        double* l2o = ws_pairs + L.wide_l2(g, nc_max);
-        double* projo = ws_pairs + L.wide_proj(g, nc_max);
-        for (int c0 = cell_begin; c0 < cell_end; c0 += nc_max) {
-            const int nc = std::min(nc_max, cell_end - c0);
-            hipLaunchKernelGGL(asv_wide_prep, dim3((unsigned)cdiv(nc, 256)), dim3(256), 0, stream, data2, g, vect, vs_cell, vs_x,
-                               c0, nc, gradn, l2o, projo);
-            const int S = nr1 + nr2;
-            const int sblocks = cdiv(S, AW_S);
-            for (int sb0 = 0; sb0 < sblocks; sb0 += 65535)
-                hipLaunchKernelGGL(asv_wide_pairs, dim3((unsigned)cdiv(nc, AW_C), (unsigned)std::min(65535, sblocks - sb0)), dim3(256),
-                                   0, stream, data1, data2, g, restrict1, nr1, restrict2, nr2, pl.npad, sigma2, c0, nc, sb0,
-                                   (const double*)gradn, (const double*)projo, ws_pairs);
-            hipLaunchKernelGGL(asv_wide_cells, dim3((unsigned)std::min(nc, blocks)), dim3(T), 0, stream, nr1, nr2, pl.npad, c0, nc,
-                               (const double*)l2o, (const double*)projo, ws_pairs, out);
-            BMX_LAUNCH_CHECK();
-        }
+        launch_wide_chunks(stream, data1, g, data2, vect, vs_cell, vs_x, sigma2, restrict1, nr1, restrict2, nr2, out, ws_pairs,
+                           pl.chunk, pl.npad, blocks, nullptr, cell_begin, cell_end);
         return;
     }
     hipLaunchKernelGGL(asv_exact_kernel, dim3(blocks), dim3(T), (size_t)2 * g * sizeof(double), stream, data1, g, data2, n2,
                        vect, vs_cell, vs_x, sigma2, restrict1, nr1, restrict2, nr2, pl.npad, out, ws_pairs, cell_begin, cell_end);
     BMX_LAUNCH_CHECK();
+}
+
+void launch_asv_strict_compact(hipStream_t stream, const unsigned char* modes, int cell_begin, int cell_end, int32_t* list,
+                               unsigned int* count) {
+    hipLaunchKernelGGL(asv_strict_compact, dim3(1), dim3(T), 0, stream, modes, cell_begin, cell_end, list, count);
+    BMX_LAUNCH_CHECK();
+}
+
+void launch_asv_strict_pass(hipStream_t stream, const double* data1, int g, const double* data2, const double* vect,
+                            int64_t vs_cell, int64_t vs_x, double sigma2, const int32_t* restrict1, int nr1,
+                            const int32_t* restrict2, int nr2, double* out, double* ws_wide, const AsvStrictPlan& sp,
+                            const int32_t* list, int count) {
+    if (count <= 0) return;  // (nothing flagged beyond the re-run: nothing is launched)
+    launch_wide_chunks(stream, data1, g, data2, vect, vs_cell, vs_x, sigma2, restrict1, nr1, restrict2, nr2, out, ws_wide,
+                       sp.chunk, sp.npad, std::min(sp.chunk, 2048), list, 0, count);  // (a cell's chains run on single lanes: eight workgroups a CU)
 }
 
 }  // namespace bmx

@@ -214,4 +214,39 @@ inline AsvPlan plan_adjust_shift_variance(int g, int n2, int nr1, int nr2, int v
     return pl;
 }
 
+// ---- strict mode (var_adj_strict) ---------------------------------------------------------------------------------
+// The tiled form records the way each cell of the call went (0 the histogram way, 1 re-run literally, 2 flagged but beyond
+// the re-run), asv_strict_compact turns the record into the ascending list of the mode-2 cells, and the literal wide form
+// recomputes exactly those, a chunk of the list at a time.  The scratch of that pass lies BEHIND the plan's own
+// (main_doubles + extra_doubles) in the caller's reservation; offsets in doubles from there:
+//   wide   [chunk * wide_per_cell]  AsvLiteralLayout per cell of a chunk and the wide tail (asv_literal.hip)
+//   list   [n2] int32               the mode-2 cells of the call's cell range, ascending
+//   count  2 uint32                 cells in the list, cells re-run literally (mode 1)
+//   modes  [n2] uint8               the record, indexed by cell
+// A pure function of (g, n2, nr1, nr2), the byte budget below and the testing hook "asv_chunk".
+constexpr size_t ASV_STRICT_BUDGET_BYTES = (size_t)32 << 30;  // of pair values in flight (adjust_shift_variance, strict mode)
+
+struct AsvStrictPlan {
+    int chunk = 1;  // cells of the list whose pair values sit in scratch at once (>= 1)
+    int npad = 1;   // nr1 rounded up to a power of two, as the plan's
+    size_t wide = 0, list = 0, count = 0, modes = 0, doubles = 0;
+};
+
+inline AsvStrictPlan plan_asv_strict(int g, int n2, int nr1, int nr2, const DevKnobs& knobs) {
+    AsvStrictPlan sp;
+    int p = 1;
+    while (p < std::max(nr1, 1)) p <<= 1;
+    sp.npad = p;
+    const size_t per_cell = (size_t)AsvLiteralLayout(nr2, p).wide_per_cell(g);
+    const size_t cells = (size_t)std::max(n2, 1);
+    sp.chunk = (int)std::max<size_t>(1, std::min<size_t>(cells, ASV_STRICT_BUDGET_BYTES / sizeof(double) / per_cell));
+    if (knobs.asv_chunk > 0) sp.chunk = std::min(sp.chunk, knobs.asv_chunk);  // (testing hook "asv_chunk")
+    sp.wide = 0;
+    sp.list = sp.wide + per_cell * (size_t)sp.chunk;
+    sp.count = sp.list + (cells + 1) / 2;
+    sp.modes = sp.count + 1;
+    sp.doubles = sp.modes + (cells + 7) / 8;
+    return sp;
+}
+
 }  // namespace bmx

@@ -1568,7 +1568,7 @@ __global__ __launch_bounds__(T) void asv_tile_kernel(int g, const double* __rest
                                                      const int32_t* __restrict__ sid, double* __restrict__ out,
                                                      double* __restrict__ scratch, int cell_begin, int cell_end, int lcap,
                                                      unsigned long long* __restrict__ tally, unsigned int* __restrict__ gbar,
-                                                     unsigned int* __restrict__ tile_ctr) {
+                                                     unsigned int* __restrict__ tile_ctr, unsigned char* __restrict__ modes) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int GP = asv_tile_gp(g);
     double* cx = reinterpret_cast<double*>(smem_raw);
@@ -1642,7 +1642,8 @@ __global__ __launch_bounds__(T) void asv_tile_kernel(int g, const double* __rest
                 // up to lcap addends per chain; between 1e-9 and 1e-6 the histogram way is right on all but a few cells of a
                 // small call (and on every sampled cell of config 5 at sigma 1), and a re-run of tens of thousands of addends for
                 // each of the 2.5 % of config 5's cells that sit there doubled the step: up to 8 192.
-                const bool flagged = tc.lit_on && (-prob2 < 1e-6 || prob2 < -12.0);
+                const bool ill = -prob2 < 1e-6 || prob2 < -12.0;
+                const bool flagged = tc.lit_on && ill;
                 const int lcap_c = (-prob2 < 1e-9 || prob2 < -12.0) ? lcap : (lcap < 8192 ? lcap : 8192);
                 const int cG = cell_first_histogram(lds, tc, c, flagged, cw);
                 if (flagged) {
@@ -1657,6 +1658,8 @@ __global__ __launch_bounds__(T) void asv_tile_kernel(int g, const double* __rest
                     }
                     if (!literal) ++n_back;
                     cell_mode = literal ? 1 : 2;
+                } else if (modes && ill) {
+                    cell_mode = 2;  // strict mode, no re-run at all (lcap = 0): the flag holds whatever lcap is
                 }
                 if (!literal) ref_quan = cell_histogram_quantile(lds, tc, c, cw, prob2);
             }
@@ -1664,6 +1667,8 @@ __global__ __launch_bounds__(T) void asv_tile_kernel(int g, const double* __rest
             // (testing hook "asv_modes": which way every cell went, one byte per cell behind the tallies)
             if (tid == 0 && tally && (unsigned long long)(c0 + c) < tally[3])
                 reinterpret_cast<unsigned char*>(tally + 4)[c0 + c] = (unsigned char)cell_mode;
+            // (strict mode: the call's own record, which the strict pass compacts into the list of mode-2 cells)
+            if (tid == 0 && modes) modes[c0 + c] = (unsigned char)cell_mode;
             __syncthreads();
         }
         if (tc.lit_on) {
@@ -1783,7 +1788,7 @@ static int device_cu_count() {
 
 void launch_asv_tile(hipStream_t stream, const double* data1, int g, const double* data2, int n2, const double* vect,
                      int vect_row_major, double sigma2, const int32_t* restrict1, int nr1, const int32_t* restrict2, int nr2,
-                     double* out, double* ws_pairs, const AsvPlan& pl, int cell_begin, int cell_end) {
+                     double* out, double* ws_pairs, const AsvPlan& pl, int cell_begin, int cell_end, unsigned char* modes) {
     if (g > 256) throw Error(BMX_ERR_ARG, "adjust_shift_variance: more than 256 dimensions at this size are not supported");
     const int blocks = pl.blocks;
     const AsvTileLayout L(g, nr1, nr2, pl.lcap, n2, vect_row_major);
@@ -1816,7 +1821,7 @@ void launch_asv_tile(hipStream_t stream, const double* data1, int g, const doubl
         ensure_dynamic_lds(reinterpret_cast<const void*>(&asv_tile_kernel<NB8>), lds);                                       \
         hipLaunchKernelGGL(asv_tile_kernel<NB8>, dim3(blocks), dim3(T), lds, stream, g, data2, n2, vrm, sigma2, nr1, nr2,     \
                            (const double*)S, (const double*)snrm, (const int32_t*)sid, out, ws_pairs, cell_begin, cell_end,  \
-                           pl.lcap, tally, gbar, tile_ctr);                                                                \
+                           pl.lcap, tally, gbar, tile_ctr, modes);                                                         \
         break
     switch (asv_tile_nb8(g)) {
 #ifdef BMX_ASV_AB_ONLY13

@@ -189,6 +189,15 @@ void asv_modes_read(unsigned char* dst, size_t n);  // testing hook "asv_modes":
 void adjust_shift_variance_device(hipStream_t stream, const double* data1, int g, int n1, const double* data2, int n2,
                                   const double* vect, double sigma2, const int32_t* restrict1, int nr1,
                                   const int32_t* restrict2, int nr2, double* out, double* ws_pairs, const AsvPlan& plan,
-                                  int vect_row_major = 0, int cell_begin = 0, int cell_end = -1);
+                                  int vect_row_major = 0, int cell_begin = 0, int cell_end = -1, int strict = 0,
+                                  int64_t* counts = nullptr);
+// Strict mode (var_adj_strict; strict != 0, or every call under the testing hook "asv_strict" = 1): a call that takes the
+// tiled form also records the way of each of its cells, and the cells it flags as ill-conditioned but could not re-run
+// go through the literal wide form afterwards -- their values are the exact form's bits.  The host waits once per call for
+// the number of such cells.  counts (nullable, host): {cells the tiled form handled, re-run literally, flagged beyond the
+// re-run, recomputed by the strict pass}, all -1 where strict is off or the plan is exact / wide (strict is a no-op there).
+// The caller reserves adjust_shift_variance_scratch doubles (the plan's own, and behind them plan_asv_strict's when the
+// call will be strict) BEFORE the launch and passes the same `strict`.
+size_t adjust_shift_variance_scratch(const AsvPlan& plan, int g, int n2, int nr1, int nr2, int strict);
 
 }  // namespace bmx

@@ -41,6 +41,7 @@ struct MergeRecord {
     bool batch_size_na = true;
     bool skipped = false;
     int64_t asv_tally[3] = {-1, -1, -1};  // testing hook "asv_modes": cells this merge's tiled adjust_shift_variance re-ran / flagged beyond the re-run / handled
+    int64_t asv_strict = -1;       // var_adj_strict: cells this merge's strict pass recomputed on this rank (-1: strict off, or not the tiled form)
     int bs_slot = -1;              // slot of batch.size in the device scalar buffer
     std::vector<int> var_batches;  // per segment (left segments first): batch id, ...
     std::vector<int> old_slot, new_slot;  // ... slots of its total variance before / after the merge's centring
@@ -92,6 +93,7 @@ class Engine {
     // testing hook "asv_modes" on during the run: per merge the tiled form's tallies (re-run, flagged beyond it, handled; -1:
     // not recorded), and the way every right cell of the snapshot merge went (dst[0, n): 0 / 1 / 2, 255 beyond the record)
     void var_adj_tally(int merge, int64_t* out3) const;
+    void var_adj_strict_cells(int merge, int64_t* cells) const;  // params.var_adj_strict: cells the merge's strict pass recomputed (-1: none ran)
     void snapshot_var_adj_modes(unsigned char* dst, int64_t n) const;
     void profile(double* topk_ms, int64_t* launches, int64_t* fallbacks);
     // out[0..9]: full-pass ms / launches of the fp16 kernel, of the split-bf16 kernel, sample-pass ms / launches,

@@ -410,7 +410,8 @@ void Engine::apply_var_adj(MergeCtx& c, int safe_k) {
     int64_t cb = 0, ce = right.n;
     bmx_shard_range_impl(right.n, rank_, world_, &cb, &ce);
     const int64_t per_cells = bmx_shard_rows_per_rank(right.n, world_);
-    double* ws = asv_ws_.reserve(plan.main_doubles + plan.extra_doubles);
+    // (params.var_adj_strict: the strict pass's scratch lies behind the plan's own)
+    double* ws = asv_ws_.reserve(adjust_shift_variance_scratch(plan, d_, right.n, nLs, nRs, p.var_adj_strict));
     double* scaling = asv_scale_.reserve((size_t)per_cells * world_);
     c.sec.reset();  // (the variance adjustment is timed on its own: event tag 4, bmx_engine_profile_var_adj)
     std::pair<hipEvent_t, hipEvent_t> aev{nullptr, nullptr};
@@ -423,8 +424,10 @@ void Engine::apply_var_adj(MergeCtx& c, int safe_k) {
     const bool tallies = dev_knobs().asv_modes > 0 && !plan.exact;
     unsigned long long t0[3] = {0, 0, 0};
     if (tallies) asv_tally_read(t0, false);
+    int64_t counts[4] = {-1, -1, -1, -1};  // (strict mode: the call waits once for the number of cells to recompute)
     adjust_shift_variance_device(stream_, left.data.p, d_, left.n, right.data.p, right.n, corr, p.sigma, r1, nLs, r2,
-                                 nRs, scaling, ws, plan, /* vect_row_major */ 1, (int)cb, (int)ce);
+                                 nRs, scaling, ws, plan, /* vect_row_major */ 1, (int)cb, (int)ce, p.var_adj_strict, counts);
+    c.rec.asv_strict = counts[3];
     if (aev.second) (void)hipEventRecord(aev.second, stream_);
     if (tallies) {
         unsigned long long t1[3] = {0, 0, 0};

@@ -267,6 +267,11 @@ void Engine::var_adj_tally(int merge, int64_t* out3) const {
     for (int i = 0; i < 3; ++i) out3[i] = merges_[merge].asv_tally[i];
 }
 
+void Engine::var_adj_strict_cells(int merge, int64_t* cells) const {
+    if (merge < 0 || merge >= (int)merges_.size()) throw Error(BMX_ERR_ARG, "merge index out of range");
+    *cells = merges_[merge].asv_strict;
+}
+
 void Engine::snapshot_var_adj_modes(unsigned char* dst, int64_t n) const {
     for (int64_t i = 0; i < n; ++i) dst[i] = (size_t)i < snap_modes_.size() ? snap_modes_[(size_t)i] : 255;
 }

@@ -35,7 +35,8 @@ struct DevKnobs {
     int exchange_always = 0;  // a single rank goes through its exchange transport too (an all-gather of one)
     int refine_wave = 0;      // the exact re-rank takes a whole wave for every query (no half-wave form)
     int asv_wide = 0;         // adjust_shift_variance: the literal wide form (asv_wide_pairs + asv_wide_cells) whatever the size
-    int asv_chunk = 0;        // wide form: at most this many cells a chunk (0: as many as 1 GiB of scratch holds)
+    int asv_chunk = 0;        // wide form: at most this many cells a chunk (0: as many as 1 GiB of scratch holds); the strict pass's chunks likewise
+    int asv_strict = -1;      // adjust_shift_variance: 1 = every call is strict (var_adj_strict), -1: as the call says
 };
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

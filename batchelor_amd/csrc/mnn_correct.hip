@@ -320,6 +320,7 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
     res.right.assign(nm, {});
     res.pairs_left.assign(nm, {});
     res.pairs_right.assign(nm, {});
+    res.strict_cells.assign((size_t)nm * 2, -1);
     std::vector<int> pl0(nm), pr0(nm);
     DevBuf<double> avg, avg_out, corr_in, corr_out, dens, dens_out, scal, scal2, asv_ws, subL, subR, subC;
     DevBuf<int32_t> first, second, idx, iota1, iota2;
@@ -408,8 +409,11 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
             const int32_t* r1 = lrows ? lrows : identity_rows(iota1, nl, s);
             const int32_t* r2 = rrows ? rrows : identity_rows(iota2, nr, s);
             const AsvPlan plan = adjust_shift_variance_plan(Gs, nr, nLs, nRs, 1);
-            double* ws = asv_ws.reserve(plan.main_doubles + plan.extra_doubles);
-            adjust_shift_variance_device(s, Lin, Gs, nl, Rin, nr, ci, a.sigma, r1, nLs, r2, nRs, sv, ws, plan, 1);
+            double* ws = asv_ws.reserve(adjust_shift_variance_scratch(plan, Gs, nr, nLs, nRs, a.var_adj_strict));
+            int64_t counts[4];
+            adjust_shift_variance_device(s, Lin, Gs, nl, Rin, nr, ci, a.sigma, r1, nLs, r2, nRs, sv, ws, plan, 1, 0, -1,
+                                         a.var_adj_strict, counts);
+            res.strict_cells[(size_t)mdx * 2] = counts[3];
             double* sv2 = nullptr;
             if (!same) {
                 // locations from the subset.row genes of the output matrix (R/mnnCorrect.R:466-471).  R keeps subset.row
@@ -431,7 +435,9 @@ void mnn_correct_run(const MnnCorrectArgs& a, MnnCorrectResult& res) {
                     cv = a3;
                 }
                 sv2 = scal2.reserve((size_t)nr);
-                adjust_shift_variance_device(s, l1, Gs, nl, l2p, nr, cv, a.sigma, r1, nLs, r2, nRs, sv2, ws, plan, 1);
+                adjust_shift_variance_device(s, l1, Gs, nl, l2p, nr, cv, a.sigma, r1, nLs, r2, nRs, sv2, ws, plan, 1, 0, -1,
+                                             a.var_adj_strict, counts);
+                res.strict_cells[(size_t)mdx * 2 + 1] = counts[3];
             }
             BMX_HIP(hipEventRecord(ev[4], s));
             add_scaled_rows(s, Rin, nr, Gs, ci, sv);

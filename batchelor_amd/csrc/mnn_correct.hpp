@@ -19,6 +19,7 @@ struct MnnCorrectArgs {
     double prop_k = 0.0;                      // NaN: NULL
     double sigma = 0.1;
     int cos_in = 1, cos_out = 1, var_adj = 1, correct_all = 0, svd_dim = 0, auto_merge = 0;
+    int var_adj_strict = 0;                   // with var_adj: adjust_shift_variance in strict mode (bmx_ops.hpp)
     const int32_t* subset = nullptr;          // 1-based genes (subset.row), or null
     int nsubset = 0;
     const int32_t* tree = nullptr;            // post-order code: leaf = batch id, 0 = merge
@@ -31,6 +32,7 @@ struct MnnCorrectResult {
     std::vector<int32_t> batch;               // 1-based, per cell
     std::vector<std::vector<int>> left, right;  // batch ids of every merge
     std::vector<std::vector<int32_t>> pairs_left, pairs_right;  // per merge, 1-based rows of the output
+    std::vector<int64_t> strict_cells;        // [merges][2]: cells the strict pass recomputed in the merge's call on the input genes / on the output genes (-1: none ran)
     double stage_ms[5] = {0, 0, 0, 0, 0};     // HIP-event time over all merges: search + pairs, averaging, smoothing, asv, apply
 };
 

@@ -31,7 +31,8 @@ class BmxMnnParams(ctypes.Structure):
                 ("sigma", ctypes.c_double), ("cos_norm_in", ctypes.c_int32), ("cos_norm_out", ctypes.c_int32),
                 ("var_adj", ctypes.c_int32), ("correct_all", ctypes.c_int32), ("svd_dim", ctypes.c_int32),
                 ("auto_merge", ctypes.c_int32), ("subset_row", ctypes.c_void_p), ("n_subset_row", ctypes.c_int32),
-                ("tree", ctypes.c_void_p), ("tree_len", ctypes.c_int32)]
+                ("tree", ctypes.c_void_p), ("tree_len", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("var_adj_strict", ctypes.c_int32)]
 
 
 @dataclass
@@ -48,6 +49,9 @@ class MnnCorrectResult:
     batch: np.ndarray         # batch id (1-based) or name per cell
     merge_info: MnnCorrectMergeInfo
     stage_ms: Optional[dict] = None  # device time over all merges by stage (bmx_mnn_result_stage_ms)
+    # var_adj_strict: per merge, cells the strict pass recomputed in its two adjust_shift_variance calls -- on the input genes
+    # and on the output genes ([nbatches - 1, 2]; -1: strict off, no such call, or the call did not take the tiled form)
+    strict_cells: Optional[np.ndarray] = None
 
 
 def _check(batches, restrict, svd_dim, auto_merge, sparse=False):
@@ -73,7 +77,7 @@ def _csc_arrays(c):
 
 
 def _mnn_correct(batches, restrict, k, prop_k, sigma, cos_norm_in, cos_norm_out, var_adj, subset_row, correct_all,
-                 merge_order, names, device, sparse=False):
+                 merge_order, names, device, sparse=False, var_adj_strict=False):
     """.mnn_correct (R/mnnCorrect.R:179-231) through bmx_mnn_correct, or for scipy.sparse batches through
     bmx_mnn_correct_sparse."""
     check_unique_names(names)  # R/mnnCorrect.R:222
@@ -94,7 +98,7 @@ def _mnn_correct(batches, restrict, k, prop_k, sigma, cos_norm_in, cos_norm_out,
     p = BmxMnnParams(ctypes.sizeof(BmxMnnParams), int(k), float("nan") if prop_k is None else float(prop_k), float(sigma),
                      int(bool(cos_norm_in)), int(bool(cos_norm_out)), int(bool(var_adj)), int(bool(correct_all)), 0, 0,
                      None if sub is None else sub.ctypes.data, 0 if sub is None else int(sub.size), code.ctypes.data,
-                     int(code.size))
+                     int(code.size), 0, int(bool(var_adj_strict)))
     L = _lib.lib()
     h = ctypes.c_void_p()
     if sparse:
@@ -121,22 +125,28 @@ def _mnn_correct(batches, restrict, k, prop_k, sigma, cos_norm_in, cos_norm_out,
         _lib.check(L.bmx_mnn_result_into(h, _lib.f64p(corrected), _lib.i32p(batch), _lib.i32p(ml), _lib.i32p(mr), lp, rp))
         st = np.zeros(5, dtype=np.float64)
         _lib.check(L.bmx_mnn_result_stage_ms(h, _lib.f64p(st)))
+        sc = np.full((B - 1, 2), -1, dtype=np.int64)
+        _lib.check(L.bmx_mnn_result_strict_cells(h, sc.ctypes.data_as(_lib.c_i64p)))
     finally:
         L.bmx_mnn_result_free(h)
     info = MnnCorrectMergeInfo(left=[[int(x) for x in row if x] for row in ml],
                                right=[[int(x) for x in row if x] for row in mr], pairs=list(zip(pl, pr)))
     out = MnnCorrectResult(corrected=corrected, batch=batch, merge_info=info,
-                           stage_ms=dict(zip(("search", "averaging", "smoothing", "asv", "apply"), st.tolist())))
+                           stage_ms=dict(zip(("search", "averaging", "smoothing", "asv", "apply"), st.tolist())),
+                           strict_cells=sc)
     return apply_names(out, names)  # R/mnnCorrect.R:219-226
 
 
 def mnnCorrect(*batches, batch=None, restrict=None, k=20, prop_k=None, sigma=0.1, cos_norm_in=True, cos_norm_out=True,
                svd_dim=0, var_adj=True, subset_row=None, correct_all=False, merge_order=None, auto_merge=False, names=None,
-               device=0) -> MnnCorrectResult:
+               device=0, var_adj_strict=False) -> MnnCorrectResult:
     """mnnCorrect(..., batch=, restrict=, k=, prop.k=, sigma=, cos.norm.in=, cos.norm.out=, svd.dim=, var.adj=,
     subset.row=, correct.all=, merge.order=, auto.merge=) (R/mnnCorrect.R:125-168).  Each batch is genes x cells; the batches
     are all dense or all scipy.sparse (implicit zeros are zeros), and the result is the same dense one either way (the
-    module docstring)."""
+    module docstring).  var_adj_strict (with var_adj): where a call of adjust_shift_variance is large enough for the tiled
+    form, the cells that form flags as ill-conditioned and cannot re-run get the reference's own chains, bit for bit."""
+    if var_adj_strict and not var_adj:
+        raise ValueError("'var_adj_strict' needs 'var_adj'")
     batches = unpack_batches(batches)
     sparse = all_sparse(batches, "mnnCorrect")  # (before anything is converted)
     mats = list(batches) if sparse else [np.asarray(b, dtype=np.float64) for b in batches]
@@ -153,7 +163,7 @@ def mnnCorrect(*batches, batch=None, restrict=None, k=20, prop_k=None, sigma=0.1
         div = divide_into_batches(x, batch, None if restrict is None else restrict[0])
         rparts = _check(div.parts, div.restricted, svd_dim, auto_merge, sparse)
         out = _mnn_correct(div.parts, rparts, k, prop_k, sigma, cos_norm_in, cos_norm_out, var_adj, subset_row, correct_all,
-                           merge_order, [str(l) for l in div.levels], device, sparse)
+                           merge_order, [str(l) for l in div.levels], device, sparse, var_adj_strict)
         # the caller's column order (R/mnnCorrect.R:161-165)
         out.corrected = out.corrected[:, div.reorder - 1]
         out.batch = out.batch[div.reorder - 1]
@@ -161,4 +171,4 @@ def mnnCorrect(*batches, batch=None, restrict=None, k=20, prop_k=None, sigma=0.1
         return out
     restrict = _check(mats, restrict, svd_dim, auto_merge, sparse)
     return _mnn_correct(mats, restrict, k, prop_k, sigma, cos_norm_in, cos_norm_out, var_adj, subset_row, correct_all,
-                        merge_order, names, device, sparse)
+                        merge_order, names, device, sparse, var_adj_strict)

@@ -35,18 +35,24 @@ def smooth_gaussian_kernel(averaged, index, mat, sigma2):
     return out
 
 
-def adjust_shift_variance(data1, data2, vect, sigma2, restrict1, restrict2):
-    """adjust_shift_variance(data1, data2, vect, sigma2, restrict1, restrict2) (src/adjust_shift_variance.cpp:30-164)."""
+def adjust_shift_variance(data1, data2, vect, sigma2, restrict1, restrict2, strict=False, counts=False):
+    """adjust_shift_variance(data1, data2, vect, sigma2, restrict1, restrict2) (src/adjust_shift_variance.cpp:30-164).
+    strict: where the call takes the tiled form, the cells it flags as ill-conditioned and cannot re-run are recomputed in
+    the reference's order of operations (bmx_adjust_shift_variance_ex).  counts: also return int64 [4] -- cells the tiled
+    form handled, re-run literally, flagged beyond the re-run, recomputed by the strict pass (-1 each where the tiled form
+    did not run or strict is off)."""
     _lib.require_gpu()
     data1, data2, vect = _lib.as_f(data1), _lib.as_f(data2), _lib.as_f(vect)
     r1 = np.ascontiguousarray(restrict1, dtype=np.int32)
     r2 = np.ascontiguousarray(restrict2, dtype=np.int32)
     out = np.zeros(data2.shape[1], dtype=np.float64)
-    _lib.check(_lib.lib().bmx_adjust_shift_variance(_lib.f64p(data1), data1.shape[0], data1.shape[1], _lib.f64p(data2),
-                                                    data2.shape[0], data2.shape[1], _lib.f64p(vect), vect.shape[0],
-                                                    vect.shape[1], ctypes.c_double(sigma2), _lib.i32p(r1), r1.size,
-                                                    _lib.i32p(r2), r2.size, _lib.f64p(out)))
-    return out
+    cnt = np.full(4, -1, dtype=np.int64)
+    _lib.check(_lib.lib().bmx_adjust_shift_variance_ex(_lib.f64p(data1), data1.shape[0], data1.shape[1], _lib.f64p(data2),
+                                                       data2.shape[0], data2.shape[1], _lib.f64p(vect), vect.shape[0],
+                                                       vect.shape[1], ctypes.c_double(sigma2), _lib.i32p(r1), r1.size,
+                                                       _lib.i32p(r2), r2.size, _lib.f64p(out), 1 if strict else 0,
+                                                       cnt.ctypes.data_as(_lib.c_i64p)))
+    return (out, cnt) if counts else out
 
 
 def adjust_shift_variance_form(n2, nr1, nr2):

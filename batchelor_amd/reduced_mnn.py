@@ -22,7 +22,13 @@ from .merge_tree import encode_postorder, resolve_merge_order
 class BmxParams(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int32), ("k", ctypes.c_int32), ("prop_k", ctypes.c_double), ("ndist", ctypes.c_double),
                 ("min_batch_skip", ctypes.c_double), ("auto_merge", ctypes.c_int32), ("var_adj", ctypes.c_int32),
-                ("sigma", ctypes.c_double)]
+                ("sigma", ctypes.c_double), ("var_adj_strict", ctypes.c_int32)]
+
+
+def _check_strict(var_adj, var_adj_strict):
+    """var_adj_strict re-runs the flagged cells of var_adj's scaling: without var_adj there is nothing to re-run."""
+    if var_adj_strict and not var_adj:
+        raise ValueError("'var_adj_strict' needs 'var_adj'")
 
 
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64)
@@ -104,10 +110,13 @@ class MnnEngine:
         self.nbatches, self.nrows, self.d = B, nrows.tolist(), d
 
     def run(self, k=20, prop_k=None, ndist=3.0, min_batch_skip=0.0, merge_tree=None, auto_merge=False, var_adj=False,
-            sigma=0.1):
+            sigma=0.1, var_adj_strict=False):
+        """var_adj_strict: every cell the tiled adjust_shift_variance flags as ill-conditioned and could not re-run is
+        recomputed in the reference's order of operations (see var_adj_strict_cells)."""
+        _check_strict(var_adj, var_adj_strict)
         p = BmxParams(ctypes.sizeof(BmxParams), int(k), float("nan") if prop_k is None else float(prop_k), float(ndist),
                       float("nan") if min_batch_skip is None else float(min_batch_skip), 1 if auto_merge else 0,
-                      1 if var_adj else 0, float(sigma))
+                      1 if var_adj else 0, float(sigma), 1 if var_adj_strict else 0)
         code = encode_postorder(merge_tree if merge_tree is not None
                                 else resolve_merge_order(self.nbatches))
         rc = _lib.lib().bmx_engine_run(self._h, ctypes.byref(p), _lib.i32p(code), int(code.size))
@@ -179,6 +188,16 @@ class MnnEngine:
             out.append(dict(zip(("rerun", "beyond", "tiled"), a.tolist())))
         return out
 
+    def var_adj_strict_cells(self):
+        """Per merge of the last run: cells the strict pass recomputed (var_adj_strict; -1: strict was off or the call did
+        not take the tiled form)."""
+        out = []
+        for m in range(self.nbatches - 1):
+            v = ctypes.c_int64(-1)
+            _lib.check(_lib.lib().bmx_engine_var_adj_strict_cells(self._h, m, ctypes.byref(v)))
+            out.append(int(v.value))
+        return out
+
     def snapshot_var_adj_modes(self, n):
         """The way every right cell of the snapshot merge's tiled adjust_shift_variance went (0 / 1 / 2; 255: not recorded)."""
         a = np.zeros(int(n), dtype=np.uint8)
@@ -246,15 +265,17 @@ class MnnEngine:
 
 
 def fast_mnn_one_shot(batches, restrict=None, k=20, prop_k=None, ndist=3.0, min_batch_skip=0.0, merge_tree=None,
-                      auto_merge=False, var_adj=False, sigma=0.1, with_pairs=True, c_order=True) -> MnnResult:
+                      auto_merge=False, var_adj=False, sigma=0.1, with_pairs=True, c_order=True,
+                      var_adj_strict=False) -> MnnResult:
     """bmx_fast_mnn(): the single call INTEGRATION.md's .Call shim makes -- host matrices in (R layout: cells x d,
     column-major), host results out; the library pulls the batches through its pinned staging ring while the first
     merges already run.  `merge_tree`: binary tree with 1-based integer leaves (None: 1..B progressive)."""
+    _check_strict(var_adj, var_adj_strict)
     _lib.require_gpu()
     keep, B, d, data, nrows, rptr, rn = _pack_batches(batches, restrict)
     p = BmxParams(ctypes.sizeof(BmxParams), int(k), float("nan") if prop_k is None else float(prop_k), float(ndist),
                   float("nan") if min_batch_skip is None else float(min_batch_skip), 1 if auto_merge else 0,
-                  1 if var_adj else 0, float(sigma))
+                  1 if var_adj else 0, float(sigma), 1 if var_adj_strict else 0)
     code = encode_postorder(merge_tree if merge_tree is not None else resolve_merge_order(B))
     N, nm = int(nrows.sum()), B - 1
     corrected = np.empty((N, d), dtype=np.float64, order="F")  # (every element is written by the library)
@@ -283,8 +304,9 @@ def fast_mnn_one_shot(batches, restrict=None, k=20, prop_k=None, ndist=3.0, min_
 
 
 def fast_mnn_core(batches, k, prop_k, restrict, ndist, merge_order, auto_merge, min_batch_skip, names, device=0,
-              var_adj=False, sigma=0.1):
+              var_adj=False, sigma=0.1, var_adj_strict=False):
     """.fast_mnn (R/fastMNN.R:398-429)."""
+    _check_strict(var_adj, var_adj_strict)
     inputs.check_unique_names(names)  # R/fastMNN.R:422
     restrict = inputs.restrict_list(restrict, [np.asarray(b).shape[0] for b in batches])  # R/fastMNN.R:405
     # the one call the .Call shim makes (bmx_fast_mnn: upload hidden behind the first merges), on the device asked for
@@ -292,7 +314,8 @@ def fast_mnn_core(batches, k, prop_k, restrict, ndist, merge_order, auto_merge, 
     _lib.check(_lib.lib().bmx_set_device(int(device)))
     tree = None if auto_merge else resolve_merge_order(len(batches), merge_order, names)
     out = fast_mnn_one_shot(batches, restrict, k=k, prop_k=prop_k, ndist=ndist, min_batch_skip=min_batch_skip,
-                            merge_tree=tree, auto_merge=auto_merge, var_adj=var_adj, sigma=sigma)
+                            merge_tree=tree, auto_merge=auto_merge, var_adj=var_adj, sigma=sigma,
+                            var_adj_strict=var_adj_strict)
     return inputs.apply_names(out, names)  # R/fastMNN.R:419-427
 
 
@@ -306,9 +329,11 @@ _reindex_pairings = inputs.reindex_pairings
 
 
 def reducedMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, ndist=3, merge_order=None, auto_merge=False,
-               min_batch_skip=0.0, names=None, device=0, var_adj=False, sigma=0.1) -> MnnResult:
+               min_batch_skip=0.0, names=None, device=0, var_adj=False, sigma=0.1, var_adj_strict=False) -> MnnResult:
     """reducedMNN(..., batch=, k=, prop.k=, restrict=, ndist=, merge.order=, auto.merge=, min.batch.skip=)
-    (R/reducedMNN.R:61-95).  `names` plays the role of the argument names of `...`."""
+    (R/reducedMNN.R:61-95).  `names` plays the role of the argument names of `...`.  var_adj_strict (with var_adj): the
+    cells whose scaling the tiled adjust_shift_variance could not settle get the reference's own chains, bit for bit."""
+    _check_strict(var_adj, var_adj_strict)
     batches = inputs.unpack_batches(batches)
     if len(batches) == 0:
         raise ValueError("at least two batches must be specified")
@@ -319,11 +344,11 @@ def reducedMNN(*batches, batch=None, k=20, prop_k=None, restrict=None, ndist=3, 
             raise ValueError("'batch' must be specified if '...' has only one object")  # R/checkInputs.R:128
         div = divideIntoBatches(batches[0], batch, None if restrict is None else restrict[0])
         out = fast_mnn_core(div["batches"], k, prop_k, div["restricted"], ndist, merge_order, auto_merge, min_batch_skip,
-                        [str(l) for l in div["levels"]], device, var_adj, sigma)
+                        [str(l) for l in div["levels"]], device, var_adj, sigma, var_adj_strict)
         reo = div["reorder"]
         out.corrected = out.corrected[reo - 1]
         out.batch = out.batch[reo - 1]
         out.merge_info.pairs = _reindex_pairings(out.merge_info.pairs, reo)
         return out
     return fast_mnn_core([np.asarray(b, dtype=np.float64) for b in batches], k, prop_k, restrict, ndist, merge_order,
-                     auto_merge, min_batch_skip, names, device, var_adj, sigma)
+                     auto_merge, min_batch_skip, names, device, var_adj, sigma, var_adj_strict)

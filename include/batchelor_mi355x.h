@@ -66,6 +66,22 @@ int32_t bmx_adjust_shift_variance(const double* data1, int32_t g1, int32_t n1, c
                                   const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
                                   double* out);
 
+/* The same native with strict mode.  Form 2 below (the tiled form, taken beyond 4e7 pairs) settles a cell one of three ways:
+ * the histogram quantile (a well-conditioned cell: the reference's value to 1e-8), a re-run in the reference's own order of
+ * operations (a cell flagged as ill-conditioned: bit-equal), or -- a flagged cell with more significant pairs than the re-run
+ * holds -- the histogram quantile again, which may then land on ANOTHER quantile.  strict != 0: the call records the way of
+ * every cell, and the cells of that third kind are recomputed in the reference's order of operations (the literal wide
+ * form, form 3): every flagged cell then has the reference's bits, every other one stays within 1e-8.  The cost grows with
+ * the number of such cells (sequential chains over all restricted cells, each), and the host waits once per call for that
+ * number.  Where the call takes form 1 or 3 anyway strict changes nothing.  With strict == 0 and counts == NULL this IS
+ * bmx_adjust_shift_variance.
+ * counts (nullable): {cells the tiled form handled, re-run literally, flagged beyond the re-run, recomputed by the strict
+ * pass}, from this call's own buffers; each -1 where the tiled form did not run or strict is off. */
+int32_t bmx_adjust_shift_variance_ex(const double* data1, int32_t g1, int32_t n1, const double* data2, int32_t g2,
+                                     int32_t n2, const double* vect, int32_t vrow, int32_t vcol, double sigma2,
+                                     const int32_t* restrict1, int32_t nr1, const int32_t* restrict2, int32_t nr2,
+                                     double* out, int32_t strict, int64_t* counts);
+
 /* Which form of adjust_shift_variance a call of these sizes takes (a pure function of the sizes): 1 = the reference's order
  * of operations literally (bit-equal to the CPU restatement, every cell; up to 4e7 (cell, restricted cell) pairs), 2 =
  * 16-cell tiles on the FP64 matrix cores with a histogram quantile (beyond that: a cell whose quantile walk is decided on
@@ -106,8 +122,9 @@ void bmx_set_force_exact_knn(int32_t on);
  * tiles -- the default; 1 = they do, measured slower), "sample_split" (ranges the threshold sample of a search with few
  * query blocks is split into; -1 = automatic, the default; 0 = never), "lk_seed" (searches with k beyond the tiers' lists: 1 = the
  * reference's partitions after the first are searched within the first's 36th distance, the default; 0 = all plainly), "tau_replay" (developer experiment: 1 = every search of
- * a run records its queries' final thresholds, 2 = the same sequence of searches starts its full passes from them), "reset"
- * (all back to their defaults).
+ * a run records its queries' final thresholds, 2 = the same sequence of searches starts its full passes from them),
+ * "asv_strict" (-1 = every adjust_shift_variance call is strict where its caller says so, the default; 1 = every call is
+ * strict: times strict mode on a workload whose driver has no switch for it), "reset" (all back to their defaults).
  * Unknown name: BMX_ERR_ARG. */
 int32_t bmx_dev_set(const char* name, int32_t value);
 /* Counters for tests and bench.py, current device: "asv_tiled_cells" (cells the tiled form of adjust_shift_variance has
@@ -158,6 +175,8 @@ typedef struct {
                               pmax(adjust_shift_variance(left, right, correction, sigma), 1) * correction
                               (R/mnnCorrect.R:331-342,462-481).  fastMNN() has no such switch: 0 is its behaviour */
     double sigma;          /* bandwidth handed to adjust_shift_variance as `sigma2` (R/mnnCorrect.R:477), 0.1 */
+    int32_t var_adj_strict; /* non-zero (needs var_adj, else BMX_ERR_ARG): every adjust_shift_variance call of the run in
+                              strict mode (bmx_adjust_shift_variance_ex); 0 for a caller whose header ends at sigma */
 } bmx_params_t;
 
 /* Multi-GPU exchange: called by the engine when `buf` (a DEVICE buffer of world * bytes_per_rank bytes whose slice
@@ -242,6 +261,9 @@ int32_t bmx_engine_snapshot_var_adj(bmx_engine_t* e, double* left_rm, double* ri
  * cell of the SNAPSHOT merge went (dst[0, n): 0 histogram quantile, 1 re-run, 2 flagged beyond it; 255 not recorded). */
 int32_t bmx_engine_var_adj_tally(bmx_engine_t* e, int32_t merge, int64_t* out3);
 int32_t bmx_engine_snapshot_var_adj_modes(bmx_engine_t* e, uint8_t* dst, int64_t n);
+/* params.var_adj_strict: cells merge `merge`'s strict pass recomputed on this rank, from the call's own buffers (no testing
+ * hook needed); -1: strict was off or the call did not take the tiled form. */
+int32_t bmx_engine_var_adj_strict_cells(bmx_engine_t* e, int32_t merge, int64_t* cells);
 /* Per kernel class (profiling on, since the last run started): out[0], out[1] = milliseconds and launches of the fp16
  * full pass, out[2], out[3] of the split-bf16 full pass, out[4], out[5] of the sample passes, out[6] = milliseconds of
  * the merges' streaming sections (everything that is not a kNN search), out[7] = queries that took the exact FP64
@@ -295,6 +317,11 @@ typedef struct {
     int32_t n_subset_row;
     const int32_t* tree;      /* the binarised merge tree in post-order: leaf = batch id, 0 = merge (as bmx_fast_mnn) */
     int32_t tree_len;
+    int32_t reserved;         /* the four bytes that were padding behind tree_len in the header before var_adj_strict: never
+                                 read, whatever they hold (a caller built against that header leaves them unspecified) */
+    int32_t var_adj_strict;   /* non-zero (needs var_adj, else BMX_ERR_ARG): both adjust_shift_variance calls of every merge
+                                 in strict mode (bmx_adjust_shift_variance_ex).  Behind the earlier header's 80 bytes, so it
+                                 is read only where struct_size covers it: a caller with that header gets 0 */
 } bmx_mnn_params_t;
 typedef struct bmx_mnn_result bmx_mnn_result_t;
 /* Runs mnnCorrect on the calling thread's current device; every argument is checked before any device work.  *out holds
@@ -325,6 +352,10 @@ int32_t bmx_mnn_result_into(const bmx_mnn_result_t* r, double* corrected, int32_
 /* Diagnostics: device time (HIP events, ms) over all merges of the stages search + pairs, averaging, smoothing,
  * adjust_shift_variance (both calls), apply. */
 int32_t bmx_mnn_result_stage_ms(const bmx_mnn_result_t* r, double* out5);
+/* params.var_adj_strict: out [(nbatches - 1) x 2] row-major, per merge the cells the strict pass recomputed in its
+ * adjust_shift_variance call on the input genes and in the one on the output genes (-1: strict off, no such call, or the
+ * call did not take the tiled form). */
+int32_t bmx_mnn_result_strict_cells(const bmx_mnn_result_t* r, int64_t* out);
 void bmx_mnn_result_free(bmx_mnn_result_t* r);
 
 /* Row range [begin, end) of `n` query rows owned by `rank` of `world` (pure host arithmetic, no GPU). */
