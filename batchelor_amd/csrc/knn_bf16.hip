@@ -19,7 +19,7 @@
 //     A consumer that is busy merging a candidate list therefore delays nobody until the ring runs dry;
 //   * the consumer loop is software-pipelined: under the dependent MFMA chain of tile t the wave refills its
 //     fragment registers with tile t + 1 and filters tile t - 1; appends and list merges of tile t - 1 follow.
-#include "knn_internal.hpp"
+#include "knn_tier.hpp"
 
 #include <cmath>
 
@@ -190,9 +190,7 @@ __host__ __device__ constexpr int ring_slots(int NS, int KS, int NCONS, int PLN)
 #endif
 #ifdef BMX_STAMPS
 __device__ unsigned long long bmx_dbg[48];
-#define STAMP() __builtin_readcyclecounter()
 #endif
-__device__ __forceinline__ int lds_load_volatile(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // SAMPLE = true: threshold estimation only, entirely in registers and branch-free.  Each (tile, lane) contributes the
 // minimum of its 16 values as ONE candidate; a lane keeps the KS/2 smallest of its candidates in a sorted register
@@ -225,19 +223,9 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: branches on it are scalar
-    // work items in launch order: first the query blocks that sweep the whole reference as one range (best selection
-    // efficiency), then the remaining query blocks split into `nranges` ranges each (short items that fill the last
-    // round of workgroups evenly)
-    int qblock = blockIdx.x, rng = 0, nrng = 1, r_begin = first_begin, r_end = r_limit;
-    if ((int)blockIdx.x >= n_full) {
-        // range-major: the workgroups in flight at any time stream the same stretch of the reference (L2 reuse)
-        const int nsplit = (gridDim.x - n_full) / nranges, j = blockIdx.x - n_full;
-        rng = j / nsplit;
-        qblock = n_full + (j - rng * nsplit);
-        nrng = nranges;
-        r_begin = first_begin + rng * range_len;
-        r_end = min(r_limit, r_begin + range_len);
-    }
+    // the work item: a query block and its reference range (whole-reference blocks first, then the split ones, range-major)
+    const WorkItem wi = decode_work_item(first_begin, range_len, r_limit, n_full, nranges);
+    const int qblock = wi.qblock, rng = wi.rng, nrng = wi.nrng, r_begin = wi.r_begin, r_end = wi.r_end;
     const int ntiles = (r_end - r_begin) >> 5;
     const int out_chunk = out_chunk0 + rng;
     if (tid < NSLOT * (1 + NCONS)) ready[tid] = 0;  // ready[] and done[] are contiguous
