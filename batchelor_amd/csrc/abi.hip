@@ -215,6 +215,7 @@ int32_t bmx_dev_set(const char* name, int32_t value) {
     else if (n == "asv_wide") k.asv_wide = value;
     else if (n == "asv_chunk") k.asv_chunk = value;
     else if (n == "asv_strict") k.asv_strict = value;
+    else if (n == "mfma_shape") k.mfma_shape = value;
     else if (n == "reset") k = bmx::DevKnobs();
     else {
         g_last_error = "bmx_dev_set: unknown knob '" + n + "'";
@@ -247,6 +248,12 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = bmx::CLUSTER_SPARSE_GENE_TILE;
         } else if (n == "pca_sparse_row_segment") {
             *value = bmx::PCA_SPARSE_ROW_SEGMENT;
+        } else if (n == "knn_exact_fallbacks" || n == "knn_tier2_queries") {
+            // what bmx_engine_profile_detail reports of an engine, here of the engine behind this thread's single-primitive
+            // entry points (queryKNN, findMutualNN ...): queries that left the first candidate tier, added up over its searches
+            *value = !g_prim ? 0 : (n == "knn_exact_fallbacks" ? g_prim->knn_ws_.exact_total : g_prim->knn_ws_.tier2_total);
+        } else if (n == "knn_mfma_shape") {
+            *value = g_prim ? g_prim->knn_ws_.last_mfma_shape : -1;  // of that engine's last fp16 full pass (-1: none yet)
         } else if (n == "asv_tally_reset") {
             bmx::asv_tally_read(t, true);
             *value = 0;

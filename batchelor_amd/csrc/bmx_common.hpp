@@ -392,6 +392,7 @@ struct KnnWorkspace {
     std::vector<int> event_tag;  // per used pair: 0 = sample pass, 1 = fp16 full pass, 2 = split-bf16 full pass, 3 = streaming section
     size_t events_used = 0;
     std::string last_kernel;     // name of the last full-pass candidate kernel, as rocprofv3 prints it
+    int last_mfma_shape = -1;    // ... and, of the fp16 tier's, its MFMA shape (knn_topk_f16's MS)
     std::pair<hipEvent_t, hipEvent_t> next_events(int tag = 1) {
         if (event_tag.size() <= events_used) event_tag.resize(events_used + 1);
         event_tag[events_used] = tag;

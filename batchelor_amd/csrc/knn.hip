@@ -228,7 +228,8 @@ void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const d
         float* margin = no_margin ? nullptr : ws.margin.reserve(nq_pad);
         uint32_t* tau_seed = seed_d2 ? ws.tau_seed.reserve(nq_pad) : nullptr;
         // without a sample pass the thresholds start at the seed (or at +inf): prep writes them
-        f16_prep_all(stream, X, ref_rows, nr, nr_pad, Qs, qrs, nq, nq_pad, d, NS, centre, reinterpret_cast<uint16_t*>(pr),
+        L.shape = f16_pick_shape(NS, KS);  // (the reference image is laid out for the MFMA shape of the sweep)
+        f16_prep_all(stream, X, ref_rows, nr, nr_pad, Qs, qrs, nq, nq_pad, d, NS, L.shape, centre, reinterpret_cast<uint16_t*>(pr),
                      reinterpret_cast<uint16_t*>(pq), rn2, qn2, maxbits, slots, flagged, margin, pe, seed_d2, tau_seed,
                      S == 0 || plan.CS > 1 ? tau_g : nullptr);
         if (margin) {

@@ -10,7 +10,8 @@
 // with |v' - exact| <= 2^-9 (1 + 2^-12) |q'||r'| + f32 accumulation terms: 4 MFMAs per 32 x 32 tile at 50 PCs
 // (K = 64) against 10 for the split-bf16 pass (K = 160).  At 50 PCs on 100 000 reference cells the bound is about
 // 0.05 against a gap of 0.35 between the 20th and the 32nd neighbour, so with KS = 32 kept candidates practically
-// every query is certified.  (The prepared images: knn_f16_prep.hip.)
+// every query is certified.  (The prepared images: knn_f16_prep.hip.  The same tile as four 16 x 16 blocks of
+// v_mfma_f32_16x16x32_f16, the kernel's MS = 1: at knn_topk_f16 below; what follows describes MS = 0.)
 //
 // With the matrix work that cheap, what happens around it sets the pace, so a workgroup (one per CU) splits it over
 // three kinds of waves.  knn_topk_f16 decodes the work item, carves the LDS and dispatches; producers and service waves
@@ -38,8 +39,10 @@
 #include "knn_f16_shape.hpp"
 #include "knn_tier.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <string>
+#include <vector>
 
 namespace bmx {
 namespace {
@@ -87,8 +90,15 @@ __device__ __forceinline__ void stamps_out_service(const Stamps& st, const int l
         atomicAdd(&bmx_dbg16[15], st.get(Stamps::IDLE));
     }
 }
+// the sweep of the first consumer of every workgroup in cycles and in 100 MHz ticks: launch() prints the median clock
+constexpr int CLK_WGS = 4096;
+__device__ unsigned long long bmx_clk16[2 * CLK_WGS];
 template <bool SAMPLE>
-__device__ __forceinline__ void stamps_out_consumer(const Stamps& st, const int lane, const int ntiles) {
+__device__ __forceinline__ void stamps_out_consumer(const Stamps& st, const int lane, const int wave, const int ntiles) {
+    if (lane == 0 && wave == 0 && blockIdx.x < CLK_WGS) {
+        bmx_clk16[2 * blockIdx.x] = st.sweep_cycles;
+        bmx_clk16[2 * blockIdx.x + 1] = st.sweep_ticks;
+    }
     if (lane == 0) {
         atomicAdd(&bmx_dbg16[0], st.elapsed());
         atomicAdd(&bmx_dbg16[1], st.get(Stamps::SPIN));
@@ -105,7 +115,7 @@ __device__ __forceinline__ void stamps_out_consumer(const Stamps& st, const int 
 #else
 __device__ __forceinline__ void stamps_out_service(const Stamps&, const int) {}
 template <bool SAMPLE>
-__device__ __forceinline__ void stamps_out_consumer(const Stamps&, const int, const int) {}
+__device__ __forceinline__ void stamps_out_consumer(const Stamps&, const int, const int, const int) {}
 #endif
 
 // =====================================================================================================================
@@ -367,7 +377,7 @@ __device__ __forceinline__ void producer_role(const PassCtx<NS, KS>& cx) {
 // ---- one drain pass: up to 32 records (128 values) of consumer c's queue, from position r0.  Every lane
 // takes one value of a record of the first half and one of the second (two independent chains of LDS read ->
 // the query's threshold -> LDS atomic slot -> store, issued together).
-template <int NS, int KS>
+template <int MS, int NS, int KS>
 __device__ __forceinline__ void drain_pass(const PassCtx<NS, KS>& cx, Stamps& st, const int c, const int r0, const int n) {
     constexpr int LCAP = F16Shape<NS, KS>::LCAP;
     const int lane = cx.lane;
@@ -397,10 +407,17 @@ __device__ __forceinline__ void drain_pass(const PassCtx<NS, KS>& cx, Stamps& st
     int jq[2], ref[2];
 #pragma unroll
     for (int x = 0; x < 2; ++x) {
-        const int srcl = tag[x] & 63;  // the lane that spilled the record: query srcl & 31, row half srcl >> 5
-        jq[x] = srcl & 31;
-        ref[x] = cx.r_begin + ((int)(tag[x] >> 8) << 5) + (int)((tag[x] >> 6) & 3u) * 8 + (srcl >> 5) * 4 +
-                 (lane & 3);
+        const int srcl = tag[x] & 63, u = (int)((tag[x] >> 6) & 3u);  // the lane that spilled the record, its group
+        if constexpr (MS == 0) {
+            // query srcl & 31, row half srcl >> 5; group u: rows 8 u ...
+            jq[x] = srcl & 31;
+            ref[x] = cx.r_begin + ((int)(tag[x] >> 8) << 5) + u * 8 + (srcl >> 5) * 4 + (lane & 3);
+        } else {
+            // 16 x 16 blocks: group u = 2 a + b is the block of reference half a and query half b, the lane's column is
+            // query srcl & 15 of that half, its rows 4 (srcl >> 4) ... of the block
+            jq[x] = 16 * (u & 1) + (srcl & 15);
+            ref[x] = cx.r_begin + ((int)(tag[x] >> 8) << 5) + 16 * (u >> 1) + 4 * (srcl >> 4) + (lane & 3);
+        }
     }
     for (;;) {
         float tq[2];
@@ -444,7 +461,7 @@ __device__ __forceinline__ void drain_pass(const PassCtx<NS, KS>& cx, Stamps& st
     st.since(Stamps::DRAIN, d0);
 }
 
-template <int NS, int KS>
+template <int MS, int NS, int KS>
 __device__ __forceinline__ void service_role(const PassCtx<NS, KS>& cx) {
     constexpr int CPS = F16Shape<NS, KS>::CPS;
     const int lane = cx.lane;
@@ -476,7 +493,7 @@ __device__ __forceinline__ void service_role(const PassCtx<NS, KS>& cx) {
             // a short queue is left to grow (a pass costs the same for 1 record as for 32) unless its consumer
             // waits for room or is through
             if (avail >= DRAIN_MIN || (state != 0 && avail > 0)) {
-                drain_pass(cx, st, c, r, avail < 32 ? avail : 32);
+                drain_pass<MS>(cx, st, c, r, avail < 32 ? avail : 32);
                 worked = true;
             } else if (state == 2) {
                 // nothing will be appended any more: the consumer wave writes the first EPI_CONS final lists out
@@ -570,6 +587,58 @@ __device__ __forceinline__ void sample_epilogue(const PassCtx<NS, KS>& cx, const
     }
 }
 
+// The same for the 16 x 16 blocks: a lane holds KS / 4 candidates of each of its two queries (query half b: best[b KS / 4 ...]),
+// the four lanes 16 apart those of one query -- again 4 x KS / 4 distinct references, the same statistic.
+template <int NS, int KS>
+__device__ __forceinline__ void sample_epilogue_16(const PassCtx<NS, KS>& cx, const float (&best)[KS / 2]) {
+    constexpr int KL = KS / 4;
+    const int lane = cx.lane, g = lane >> 4, nrng = cx.nrng, kq = cx.kq;
+    const float* const margin_g = cx.margin_g;
+    uint32_t* const tau_g = cx.tau_g;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int q = cx.qblock * NQ + cx.wave * 32 + 16 * b + (lane & 15);
+        uint32_t start = f32_orderable(best[b * KL + KL - 1]);
+        start = max(start, __shfl_xor(start, 16));
+        start = max(start, __shfl_xor(start, 32));
+        if (margin_g && kq >= 1 && kq <= KS) {
+            // rank in the union = place in the lane's own (sorted) list + the entries of the three other lanes in front of it
+            // (equal values: the lower lane's first)
+            int r[KL];
+#pragma unroll
+            for (int i = 0; i < KL; ++i) r[i] = i;
+#pragma unroll
+            for (int x = 1; x < 4; ++x) {
+                const bool first = (g ^ x) < g;
+#pragma unroll
+                for (int e = 0; e < KL; ++e) {
+                    const float pe = __shfl_xor(best[b * KL + e], 16 * x);
+#pragma unroll
+                    for (int i = 0; i < KL; ++i) r[i] += (pe < best[b * KL + i] || (pe == best[b * KL + i] && first)) ? 1 : 0;
+                }
+            }
+            float uk = __builtin_inff();
+#pragma unroll
+            for (int i = 0; i < KL; ++i) uk = r[i] == kq - 1 ? best[b * KL + i] : uk;
+            uk = fminf(uk, __shfl_xor(uk, 16));
+            uk = fminf(uk, __shfl_xor(uk, 32));
+            const float tm = uk + margin_g[q] + fabsf(uk) * 2.384185791015625e-07f;  // (the f32 sum rounded up)
+            if (tm == tm) start = min(start, f32_orderable(tm));  // (no k-th value yet: inf, nothing changes)
+        }
+        if (g == 0) {
+            if (nrng > 1) atomicMin(&tau_g[q], start);
+            else tau_g[q] = cx.tau_seed ? min(start, cx.tau_seed[q]) : start;
+        }
+        if (nrng > 1 && cx.cand_v) {
+            float* dst = cx.cand_v + ((int64_t)q * nrng + cx.rng) * KS + g * KL;
+#pragma unroll
+            for (int e = 0; e < KL; e += 4)
+                *reinterpret_cast<f32x4*>(dst + e) =
+                    f32x4{best[b * KL + e], best[b * KL + e + 1], best[b * KL + e + 2], best[b * KL + e + 3]};
+        }
+    }
+}
+
 // The full pass: everything is in the queue; once the service wave has worked it off, both write final lists out.
 template <int NS, int KS>
 __device__ __forceinline__ void consumer_epilogue(const PassCtx<NS, KS>& cx, Stamps& st, const int wr) {
@@ -583,7 +652,15 @@ __device__ __forceinline__ void consumer_epilogue(const PassCtx<NS, KS>& cx, Sta
 }
 
 // LCAP restates F16Shape<NS, KS>::LCAP: profiles, bmx_engine_knn_kernel and the bench's roofline key on the kernel's name.
-template <int NS, int KS, int LCAP, bool SAMPLE>
+//
+// MS, the MFMA shape of the consumers' sweep: 0 = v_mfma_f32_32x32x16_f16, one 32 x 32 accumulator per tile, a lane holds 16
+// values of ONE query (lane & 31; references 8 u + 4 (lane >> 5) + i of the tile in group u); 1 = v_mfma_f32_16x16x32_f16
+// (even NS), four 16 x 16 blocks per tile -- reference half a, query half b, NS / 2 MFMAs each: the same pipe time and as many
+// accumulator registers -- and a lane holds values of TWO queries, 16 b + (lane & 15), of each the references
+// 16 a + 4 (lane >> 4) + i of both a.  The prepared reference image comes in the fragment order of the shape
+// (knn_f16_prep.hip); ring, hand-over, queues, service waves and lists are the same for both.  knn_f16_shape.hpp
+// (mfma_shape_for) has which shape runs where.
+template <int NS, int KS, int LCAP, bool SAMPLE, int MS>
 __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     const uint16_t* __restrict__ Pq, const uint16_t* __restrict__ PrF, int first_begin, int range_len, int r_limit,
     int n_full, int nranges, int out_chunk0, int out_nchunks, uint32_t* __restrict__ tau_g, int32_t* __restrict__ cand,
@@ -625,7 +702,7 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
         return;
     }
     if (wave >= NCONS + NPROD) {
-        if constexpr (!SAMPLE) service_role(cx);  // (the sample pass appends to no list: its service waves end here)
+        if constexpr (!SAMPLE) service_role<MS>(cx);  // (the sample pass appends to no list: its service waves end here)
         return;
     }
 
@@ -633,17 +710,26 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     // in the kernel's body, its steps always-inline lambdas on the kernel's own locals, as the parent of this split had it: as a
     // function of its own (or a struct of member functions) behind PassCtx the NS = 4 full pass compiled to another block layout
     // and measured 0.8 % slower (MEASUREMENTS.md).
+    static_assert(MS == 0 || (MS == 1 && NS % 2 == 0), "the K of 32 of the 16 x 16 blocks: whole pairs of k-steps");
     Stamps st;
-    const int j = lane & 31, h = lane >> 5;
+    constexpr int QL = MS == 0 ? 1 : 2;   // queries a lane holds values of: j, and with the 16 x 16 blocks 16 + j too
+    constexpr int QW = MS == 0 ? 32 : 16;  // lanes that share a set of columns
+    const int j = lane & (QW - 1), h = lane >> (MS == 0 ? 5 : 4);
     const int q = qblock * NQ + wave * 32 + j;
 
-    float tau = tauL[wave * 32 + j];
-
-    f16x8 bq[NS];
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(Pq + (int64_t)q * (16 * NS) + h * (8 * NS));
+    float tau[QL];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) bq[s] = __builtin_bit_cast(f16x8, src[s]);
+    for (int b = 0; b < QL; ++b) tau[b] = tauL[wave * 32 + 16 * b + j];
+
+    // the query image is row-major: lane part h holds the h-th of a row's 64 / QW stretches of columns, the fragment of k-step
+    // s is 8 columns of it (the reference image follows the same column order).  MS = 1: bq[b NS / 2 + ks] of query half b
+    f16x8 bq[NS];
+#pragma unroll
+    for (int b = 0; b < QL; ++b) {
+        const f32x4* src =
+            reinterpret_cast<const f32x4*>(Pq + (int64_t)(q + 16 * b) * (16 * NS) + h * (8 * NS / QL));
+#pragma unroll
+        for (int s = 0; s < NS / QL; ++s) bq[b * (NS / QL) + s] = __builtin_bit_cast(f16x8, src[s]);
     }
 
     float* qv = qvals + wave * QCAP * 4;
@@ -669,7 +755,9 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     lds_iptr wr_p = (lds_iptr)&wrL[wave];
     int one = 1;
     asm volatile("" : "+v"(wr_p), "+v"(one));
-    float tau_next = tau;
+    float tau_next[QL];
+#pragma unroll
+    for (int b = 0; b < QL; ++b) tau_next[b] = tau[b];
     int seen = 0;
     f32x4 a[NS], b[NS];  // fragments of the even / odd tile of the current slot
     // SAMPLE: the lane's KS / 2 smallest candidates, ascending.  Insertion of x into a sorted list is one median per
@@ -704,13 +792,18 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     // one slot later (they are back long before the reads the wave has to wait for anyway)
     auto poll = [&](const int k) __attribute__((always_inline)) {
         seen = *(volatile lds_iptr)ready_p[k];
-        if constexpr (!SAMPLE)
-            tau_next = __hip_atomic_load(&tauL[wave * 32 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    auto sample_insert = [&](const float x) __attribute__((always_inline)) {
+        if constexpr (!SAMPLE) {
 #pragma unroll
-        for (int i = (SAMPLE ? KS / 2 : 1) - 1; i > 0; --i) best[i] = __builtin_amdgcn_fmed3f(best[i - 1], best[i], x);
-        best[0] = fminf(fminf(best[0], x), x);
+            for (int b = 0; b < QL; ++b)
+                tau_next[b] = __hip_atomic_load(&tauL[wave * 32 + 16 * b + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+    // (the list of query half b: best[b KL ...], KL = KS / 2 / QL entries)
+    auto sample_insert = [&](const int b, const float x) __attribute__((always_inline)) {
+        constexpr int KL = SAMPLE ? KS / 2 / QL : 1;
+#pragma unroll
+        for (int i = KL - 1; i > 0; --i) best[b * KL + i] = __builtin_amdgcn_fmed3f(best[b * KL + i - 1], best[b * KL + i], x);
+        best[b * KL] = fminf(fminf(best[b * KL], x), x);
     };
 
     // room for `need` (<= QCAP) more records: the service wave's progress is looked at only when the last known state
@@ -731,37 +824,52 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     };
 
     // ---- filter of one tile (products in `acc`, tile number t) and, where a value is below its query's threshold, the
-    // spill.  Returns the lane minimum (SAMPLE uses nothing else).
-    auto sift = [&](const f32x16& acc, const int t) __attribute__((always_inline)) {
-        // group minima (4 consecutive references each), then the lane minimum.  Every fminf below is half of a
+    // spill.  Leaves the lane minimum of each of the lane's queries in mn (SAMPLE uses nothing else).  The tile's values come
+    // as four groups of four consecutive references: MS = 0, one 32 x 32 accumulator, group u = its registers 4 u ..., all of
+    // one query; MS = 1, four 16 x 16 blocks, group u = 2 a + b = the block of reference half a and query half b.
+    auto sift = [&](const auto& acc, const int t, float(&mn)[QL]) __attribute__((always_inline)) {
+        auto at = [&](const int u, const int i) __attribute__((always_inline)) {
+            if constexpr (MS == 0)
+                return acc[4 * u + i];
+            else
+                return acc[u][i];
+        };
+        // group minima, then the lane minimum of a query.  Every fminf below is half of a
         // three-way minimum: the compiler forms v_min3_f32 from such pairs and, unlike for a lone v_min_f32, does not put
         // a v_max x, x (signalling-NaN quieting) in front of its inputs.  The threshold rides along as the sixth operand
         // of a group: min(group, tau) < tau iff min(group) < tau (SAMPLE: tau = +inf, the plain minimum)
         float g[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const float m3 = fminf(fminf(acc[4 * u], acc[4 * u + 1]), acc[4 * u + 2]);
-            g[u] = fminf(fminf(m3, acc[4 * u + 3]), tau);
+            const float m3 = fminf(fminf(at(u, 0), at(u, 1)), at(u, 2));
+            g[u] = fminf(fminf(m3, at(u, 3)), tau[u & (QL - 1)]);
         }
-        const float mn = fminf(fminf(fminf(fminf(g[0], g[1]), g[2]), g[3]), tau);
-        if constexpr (SAMPLE) {
-            return mn;
+        if constexpr (MS == 0) {
+            mn[0] = fminf(fminf(fminf(fminf(g[0], g[1]), g[2]), g[3]), tau[0]);
         } else {
-            const unsigned long long any = __builtin_amdgcn_ballot_w64(mn < tau);
-            if (any == 0) return mn;
+#pragma unroll
+            for (int b = 0; b < QL; ++b) mn[b] = fminf(fminf(g[b], g[2 + b]), tau[b]);
+        }
+        if constexpr (SAMPLE) {
+            return;
+        } else {
+            bool below = mn[0] < tau[0];
+            if constexpr (QL == 2) below |= mn[1] < tau[1];
+            const unsigned long long any = __builtin_amdgcn_ballot_w64(below);
+            if (any == 0) return;
             st.count(Stamps::EVT);
             const unsigned long long e0 = st.now();
             // ---- spill the groups with survivors: four raw values and a tag per (lane, group) into the wave's queue;
             // the service wave takes it from there.  (A lambda: it lives on sift's g[] and on the wave's tau and wr.)
             const uint32_t tagbase = ((uint32_t)t << 8) | (uint32_t)lane;
             auto spill = [&](const int u, const unsigned long long m) __attribute__((always_inline)) {
-                if (g[u] < tau) {  // the lanes of m
+                if (g[u] < tau[u & (QL - 1)]) {  // the lanes of m
                     const int slot = (wr + mbcnt64(m)) & (QCAP - 1);
                     f32x4 rec;
-                    rec[0] = acc[4 * u];
-                    rec[1] = acc[4 * u + 1];
-                    rec[2] = acc[4 * u + 2];
-                    rec[3] = acc[4 * u + 3];
+                    rec[0] = at(u, 0);
+                    rec[1] = at(u, 1);
+                    rec[2] = at(u, 2);
+                    rec[3] = at(u, 3);
                     *reinterpret_cast<f32x4*>(qv + slot * 4) = rec;
                     qt[slot] = tagbase | ((uint32_t)u << 6);
                 }
@@ -772,7 +880,7 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
             int tot = 0;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                m[u] = __builtin_amdgcn_ballot_w64(g[u] < tau);
+                m[u] = __builtin_amdgcn_ballot_w64(g[u] < tau[u & (QL - 1)]);
                 tot += __builtin_popcountll(m[u]);
             }
             if (wr + tot - rd_seen > QCAP) {
@@ -782,15 +890,18 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         // (taken again: an earlier group of this tile may have waited and come back with a lower threshold)
-                        unsigned long long mu = __builtin_amdgcn_ballot_w64(g[u] < tau);
+                        unsigned long long mu = __builtin_amdgcn_ballot_w64(g[u] < tau[u & (QL - 1)]);
                         if (mu == 0) continue;
                         const int c = __builtin_popcountll(mu);
                         if (wr + c - rd_seen > QCAP) {
                             wait_room(c);
-                            const float tl =
-                                __hip_atomic_load(&tauL[wave * 32 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            tau = tl < tau ? tl : tau;
-                            mu = __builtin_amdgcn_ballot_w64(g[u] < tau);
+#pragma unroll
+                            for (int b = 0; b < QL; ++b) {
+                                const float tl = __hip_atomic_load(&tauL[wave * 32 + 16 * b + j], __ATOMIC_RELAXED,
+                                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+                                tau[b] = tl < tau[b] ? tl : tau[b];
+                            }
+                            mu = __builtin_amdgcn_ballot_w64(g[u] < tau[u & (QL - 1)]);
                         }
                         if (mu) {
                             spill(u, mu);
@@ -799,14 +910,13 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
                         }
                     }
                     st.since(Stamps::EVC, e0);
-                    return mn;
+                    return;
                 }
                 wait_room(tot);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) spill(u, m[u]);  // (the count goes out with the next done word)
             st.since(Stamps::EVC, e0);
-            return mn;
         }
     };
 
@@ -816,31 +926,64 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
     // both tiles.  The two consumer waves of a SIMD fall into opposite phases: one's vector phase runs under the
     // other's MFMAs.  With slots of four tiles (TP = 2) only every other pair crosses a slot boundary: the ready
     // check, the polls and the hand-back happen once per four tiles.
+    // MS = 1: fragment f = 2 ks + a of a tile is reference half a in k-step ks (of 32); it feeds the blocks of both query
+    // halves and is refilled after the second; the eight blocks of the pair are eight independent chains.
     auto tile_pair = [&](const lds_f4ptr tp, const int t0, const int hand_back_pos) __attribute__((always_inline)) {
-        f32x16 accA, accB;
+        float mnA[QL], mnB[QL];
+        if constexpr (MS == 0) {
+            f32x16 accA, accB;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) accA[e] = accB[e] = 0.f;
-        __builtin_amdgcn_sched_barrier(0);
+            for (int e = 0; e < 16; ++e) accA[e] = accB[e] = 0.f;
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            accA = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[s]), bq[s], accA, 0, 0, 0);
-            a[s] = tp[s * 64];
-            accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, b[s]), bq[s], accB, 0, 0, 0);
-            b[s] = tp[(NS + s) * 64];
+            for (int s = 0; s < NS; ++s) {
+                accA = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[s]), bq[s], accA, 0, 0, 0);
+                a[s] = tp[s * 64];
+                accB = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, b[s]), bq[s], accB, 0, 0, 0);
+                b[s] = tp[(NS + s) * 64];
+            }
+#pragma unroll
+            for (int s = 0; s < 2 * NS; ++s) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one LDS read
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (hand_back_pos >= 0) hand_back(hand_back_pos);  // that slot's tiles are all on their way into registers
+            sift(accA, t0, mnA);
+            sift(accB, t0 + 1, mnB);
+        } else {
+            f32x4 cA[4], cB[4];  // block 2 a + b
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) cA[u][e] = cB[u][e] = 0.f;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int f = 0; f < NS; ++f) {
+                const int ks = f >> 1, u0 = 2 * (f & 1);
+                const f16x8 fa = __builtin_bit_cast(f16x8, a[f]), fb = __builtin_bit_cast(f16x8, b[f]);
+                cA[u0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, bq[ks], cA[u0], 0, 0, 0);
+                cA[u0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa, bq[NS / 2 + ks], cA[u0 + 1], 0, 0, 0);
+                a[f] = tp[f * 64];
+                cB[u0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, bq[ks], cB[u0], 0, 0, 0);
+                cB[u0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb, bq[NS / 2 + ks], cB[u0 + 1], 0, 0, 0);
+                b[f] = tp[(NS + f) * 64];
+            }
+#pragma unroll
+            for (int s = 0; s < 2 * NS; ++s) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);  // two MFMAs: a fragment's two blocks
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one LDS read
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (hand_back_pos >= 0) hand_back(hand_back_pos);
+            sift(cA, t0, mnA);
+            sift(cB, t0 + 1, mnB);
         }
-#pragma unroll
-        for (int s = 0; s < 2 * NS; ++s) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // one LDS read
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (hand_back_pos >= 0) hand_back(hand_back_pos);  // that slot's tiles are all on their way into registers
-        const float mnA = sift(accA, t0);
-        const float mnB = sift(accB, t0 + 1);
         if constexpr (SAMPLE) {
-            // sorted insertion of ONE candidate per pair: the lane's minimum over both tiles (32 references of
-            // one query; still one distinct reference per candidate, half the insertions)
-            sample_insert(fminf(fminf(mnA, mnB), mnB));
+            // sorted insertion of ONE candidate per pair and query: the lane's minimum over both tiles (32 references of the
+            // query, 16 with the 16 x 16 blocks; still one distinct reference per candidate, half the insertions)
+#pragma unroll
+            for (int qb = 0; qb < QL; ++qb) sample_insert(qb, fminf(fminf(mnA[qb], mnB[qb]), mnB[qb]));
         }
     };
 
@@ -880,7 +1023,10 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
                         tile_pair((lds_f4ptr)(ring_lane + k * SLOT_BYTES + 2 * TILE_BYTES), 4 * sl, k);
                     }
                     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this pair's fragments, the next slot's ready word, tau
-                    if constexpr (!SAMPLE) asm("v_min_f32 %0, %0, %1" : "+v"(tau) : "v"(tau_next));
+                    if constexpr (!SAMPLE) {
+#pragma unroll
+                        for (int b = 0; b < QL; ++b) asm("v_min_f32 %0, %0, %1" : "+v"(tau[b]) : "v"(tau_next[b]));
+                    }
                     spin_until_staged(sl + 1, kn);
                     __atomic_signal_fence(__ATOMIC_SEQ_CST);
                     poll((kn + 1) % NSLOT);
@@ -891,19 +1037,22 @@ __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(
         __builtin_amdgcn_s_setprio(0);
     };
     sweep();
-    if constexpr (SAMPLE)
+    st.sweep_end();
+    if constexpr (!SAMPLE)
+        consumer_epilogue(cx, st, wr);
+    else if constexpr (MS == 0)
         sample_epilogue(cx, best);
     else
-        consumer_epilogue(cx, st, wr);
-    stamps_out_consumer<SAMPLE>(st, lane, ntiles);
+        sample_epilogue_16(cx, best);
+    stamps_out_consumer<SAMPLE>(st, lane, wave, ntiles);
 }
 
-template <int NS, int KS>
+template <int NS, int KS, int MS>
 void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
     using S = F16Shape<NS, KS>;
     constexpr size_t lds = S::lds_bytes;
     static_assert(lds <= LDS_TOTAL, "LDS budget");
-    const auto full = &knn_topk_f16<NS, KS, S::LCAP, false>, sample = &knn_topk_f16<NS, KS, S::LCAP, true>;
+    const auto full = &knn_topk_f16<NS, KS, S::LCAP, false, MS>, sample = &knn_topk_f16<NS, KS, S::LCAP, true, MS>;
     ensure_dynamic_lds(reinterpret_cast<const void*>(full), lds);
     ensure_dynamic_lds(reinterpret_cast<const void*>(sample), lds);
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
@@ -911,9 +1060,10 @@ void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
         ev = ws.next_events(L.sample ? 0 : 1);
         BMX_HIP(hipEventRecord(ev.first, stream));
     }
+    if (!L.sample) ws.last_mfma_shape = MS;
     if (!L.sample)
         ws.last_kernel = "knn_topk_f16<" + std::to_string(NS) + ", " + std::to_string(KS) + ", " + std::to_string(S::LCAP) +
-                         ", false>";
+                         ", false, " + std::to_string(MS) + ">";
     const int items = L.n_full + (L.nqb - L.n_full) * L.nranges;
     const auto pass = L.sample ? sample : full;
     hipLaunchKernelGGL(pass, dim3(items), dim3(S::NWAVES * 64), lds, stream, L.pq, L.pr, L.first_begin, L.range_len, L.r_limit,
@@ -938,6 +1088,17 @@ void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
                 hh[4] / sw, hh[4] ? (double)hh[11] / hh[4] : 0.0, hh[15] / sw);
         unsigned long long z[48] = {0};
         BMX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(bmx_dbg16), z, sizeof(z)));
+        // the clock the sweeps ran at: cycles / 100 MHz ticks of the first consumer of every workgroup, the median of them
+        std::vector<unsigned long long> ck(2 * CLK_WGS);
+        BMX_HIP(hipMemcpyFromSymbol(ck.data(), HIP_SYMBOL(bmx_clk16), ck.size() * sizeof(unsigned long long)));
+        std::vector<double> ghz;
+        for (int w = 0; w < std::min(items, CLK_WGS); ++w)
+            if (ck[2 * w + 1] > 0) ghz.push_back((double)ck[2 * w] / (double)ck[2 * w + 1] * 0.1);
+        if (!ghz.empty()) {
+            std::sort(ghz.begin(), ghz.end());
+            fprintf(stderr, "[stamps f16] shape %d in-kernel clock: median %.3f GHz (min %.3f, max %.3f) over %zu workgroups\n", MS,
+                    ghz[ghz.size() / 2], ghz.front(), ghz.back(), ghz.size());
+        }
     }
 #endif
 }
@@ -991,13 +1152,35 @@ int f16_pick_ns(int d, int KS) {
     return 0;
 }
 
+// The MFMA shape of a search's sweeps (knn_topk_f16's MS): the table of knn_f16_shape.hpp, or what the testing hook forces;
+// the 16 x 16 blocks exist for even NS only.  The prepared reference image is written for the shape (f16_prep_all).
+int f16_pick_shape(int NS, int KS) {
+    if (NS % 2 != 0) return 0;
+    const int forced = dev_knobs().mfma_shape;
+    return forced == 0 || forced == 1 ? forced : mfma_shape_for(NS, KS);
+}
+
+namespace {
+template <int NS, int KS>
+void launch_shape(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
+    if constexpr (NS % 2 == 0) {
+        if (L.shape == 1) {
+            launch<NS, KS, 1>(stream, ws, L);
+            return;
+        }
+    }
+    launch<NS, KS, 0>(stream, ws, L);
+}
+}  // namespace
+
 bool f16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L) {
+    if (L.shape != 0 && (L.shape != 1 || NS % 2 != 0)) return false;
 #define BMX_CASE(N)                       \
     case N:                               \
         if (KS == BMX_KS1)                \
-            launch<N, BMX_KS1>(stream, ws, L); \
+            launch_shape<N, BMX_KS1>(stream, ws, L); \
         else if constexpr (N <= 4)        \
-            launch<N, 48>(stream, ws, L); \
+            launch_shape<N, 48>(stream, ws, L); \
         else                              \
             return false;                 \
         return true;

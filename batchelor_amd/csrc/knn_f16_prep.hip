@@ -34,7 +34,7 @@ __host__ __device__ __forceinline__ double f16_scale(double max_n2) {
 // of a row all hold it).
 template <int PHASE>
 __device__ __forceinline__ double prep_rows(char* smem_pp, int block, const double* __restrict__ X,
-                                            const int32_t* __restrict__ rows, int n, int d, int NS,
+                                            const int32_t* __restrict__ rows, int n, int d, int NS, int shape,
                                             const double* __restrict__ mean, int is_query, uint16_t* __restrict__ P,
                                             double* __restrict__ n2, unsigned long long* __restrict__ max_slots,
                                             double scale) {
@@ -109,10 +109,17 @@ __device__ __forceinline__ double prep_rows(char* smem_pp, int block, const doub
                 ++prow;
                 i -= 2 * NS;
             }
-        } else {
+        } else if (shape == 0) {
             prow = p & 31;
             const int ih = p >> 5;  // = 2 * k-step + lane half
             i = (ih & 1) * NS + (ih >> 1);
+        } else {
+            // 16x16x32 fragments (even NS): piece p is lane p & 63 of fragment f = 2 * k-step + reference half; the lane holds
+            // row 16 * half + (lane & 15), and of the row's four stretches of 4 NS columns the (lane >> 4)-th, as the query's
+            // lane does of its (row-major) row
+            const int l = p & 63, f = p >> 6;
+            prow = 16 * (f & 1) + (l & 15);
+            i = (l >> 4) * (NS >> 1) + (f >> 1);
         }
         const bool plive = r0 + prow < n;
         const float nf = nrm[prow];  // three fp16 pieces reproduce the f32 value exactly (33 bits)
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(256) void knn_prep_f16_norms(const double* __restri
                                                           int d, int NS, const double* __restrict__ mean,
                                                           double* __restrict__ n2, unsigned long long* __restrict__ max_slots) {
     extern __shared__ __attribute__((aligned(16))) char smem_pp[];
-    (void)prep_rows<0>(smem_pp, blockIdx.x, X, rows, n, d, NS, mean, 0, nullptr, n2, max_slots, 1.0);
+    (void)prep_rows<0>(smem_pp, blockIdx.x, X, rows, n, d, NS, 0, mean, 0, nullptr, n2, max_slots, 1.0);
 }
 
 // PHASE 1 of references AND queries in one launch (workgroups [0, nrb): reference tiles, the others: query tiles), with
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(256) void knn_prep_f16_norms(const double* __restri
 // sample pass folds into the thresholds it publishes, or straight into tau_g when there is no sample pass (tau_init).
 __global__ __launch_bounds__(256) void knn_prep_f16_rq(const double* __restrict__ X, const int32_t* __restrict__ rrows, int nr,
                                                        int nrb, const double* __restrict__ Q,
-                                                       const int32_t* __restrict__ qrows, int nq, int d, int NS,
+                                                       const int32_t* __restrict__ qrows, int nq, int d, int NS, int shape,
                                                        const double* __restrict__ mean, uint16_t* __restrict__ Pr,
                                                        uint16_t* __restrict__ Pq, double* __restrict__ rn2,
                                                        double* __restrict__ qn2, const unsigned long long* __restrict__ slots,
@@ -187,11 +194,11 @@ __global__ __launch_bounds__(256) void knn_prep_f16_rq(const double* __restrict_
     const double max_rn2 = sh_max;
     const double scale = f16_scale(max_rn2);
     if ((int)blockIdx.x < nrb) {
-        (void)prep_rows<1>(smem_pp, blockIdx.x, X, rrows, nr, d, NS, mean, 0, Pr, rn2, nullptr, scale);
+        (void)prep_rows<1>(smem_pp, blockIdx.x, X, rrows, nr, d, NS, shape, mean, 0, Pr, rn2, nullptr, scale);
         return;
     }
     const int qb = blockIdx.x - nrb;
-    const double s = prep_rows<1>(smem_pp, qb, Q, qrows, nq, d, NS, mean, 1, Pq, qn2, nullptr, scale);
+    const double s = prep_rows<1>(smem_pp, qb, Q, qrows, nq, d, NS, shape, mean, 1, Pq, qn2, nullptr, scale);
     const int rr = threadIdx.x >> 3, sub = threadIdx.x & 7;
     if (sub == 0) {
         const int q = qb * 32 + rr;
@@ -213,14 +220,14 @@ __global__ __launch_bounds__(256) void knn_prep_f16_rq(const double* __restrict_
 // References (norm pass, then the scaled image) and queries (image, norm, margin, seed threshold) of one search: two
 // launches.  `slots` (64 x 16 words) must be zero on entry -- knn_refine leaves them so for the next search.
 void f16_prep_all(hipStream_t stream, const double* X, const int32_t* rrows, int nr, int nr_pad, const double* Q,
-                  const int32_t* qrows, int nq, int nq_pad, int d, int NS, const double* mean, uint16_t* Pr, uint16_t* Pq,
+                  const int32_t* qrows, int nq, int nq_pad, int d, int NS, int shape, const double* mean, uint16_t* Pr, uint16_t* Pq,
                   double* rn2, double* qn2, unsigned long long* maxbits, unsigned long long* slots, int32_t* flagged0,
                   float* margin, const PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init) {
     const size_t lds = (size_t)32 * d * 4 + 128 + 16;
     hipLaunchKernelGGL(knn_prep_f16_norms, dim3(nr_pad / 32), dim3(256), lds, stream, X, rrows, nr, d, NS, mean, rn2, slots);
     BMX_LAUNCH_CHECK();
     hipLaunchKernelGGL(knn_prep_f16_rq, dim3(nr_pad / 32 + nq_pad / 32), dim3(256), lds, stream, X, rrows, nr, nr_pad / 32, Q, qrows,
-                       nq, d, NS, mean, Pr, Pq, rn2, qn2, (const unsigned long long*)slots, maxbits, flagged0, margin, pe, seed_d2,
+                       nq, d, NS, shape, mean, Pr, Pq, rn2, qn2, (const unsigned long long*)slots, maxbits, flagged0, margin, pe, seed_d2,
                        tau_seed, tau_init);
     BMX_LAUNCH_CHECK();
 }

@@ -89,6 +89,12 @@ BMX_F16_HD constexpr int list_cap(int NS, int KS) {
     return KS + 16 <= 64 ? KS + 16 : 64;
 }
 
+// The MFMA shape of the consumers' sweep per (NS, KS): 0 = 32x32x16, one accumulator per tile; 1 = 16x16x32, four 16 x 16
+// blocks per tile (even NS only; knn_f16.hip has what a lane holds under either).  Same LDS, same pipe time, same registers:
+// an entry is 1 only where the step measured faster by wall time with it; unmeasured shapes stay 0.  Measured: NS = 4,
+// KS = 32 (config 3): 4 % more cycles a tile at a 9 % higher clock, the step 1.2 - 2.5 % shorter (MEASUREMENTS.md).
+BMX_F16_HD constexpr int mfma_shape_for(int NS, int KS) { return NS == 4 && KS == 32 ? 1 : 0; }
+
 // Everything a (NS, KS) instantiation derives from the four functions above, once.
 template <int NS_, int KS_>
 struct F16Shape {

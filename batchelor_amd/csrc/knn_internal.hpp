@@ -34,6 +34,7 @@ struct PassLaunch {
     const float* margin = nullptr;
     int k = 0;
     const uint32_t* tau_seed = nullptr;  // fp16 tier, sample pass of a seeded search: tau_g = min(sampled, tau_seed)
+    int shape = 0;          // fp16 tier: MFMA shape of the sweep (f16_pick_shape), the one pr was prepared for
 };
 // split-bf16 candidate pass (knn_bf16.hip)
 int bf16_pick_ns(int d);         // MFMA k-steps (16 bf16 each) for 3 d + 3 columns; 0 = unsupported
@@ -45,8 +46,9 @@ bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const Pas
 // fp16 candidate pass (knn_f16.hip; f16_prep_all: knn_f16_prep.hip)
 int f16_pick_ns(int d, int KS);
 int f16_rows_per_slot(int NS, int KS);  // reference rows a ring slot of the fp16 tier holds (ranges are multiples of it)
+int f16_pick_shape(int NS, int KS);     // MFMA shape of the sweep: 0 = 32x32x16, 1 = 16x16x32 (table, or the "mfma_shape" hook)
 void f16_prep_all(hipStream_t stream, const double* X, const int32_t* rrows, int nr, int nr_pad, const double* Q,
-                  const int32_t* qrows, int nq, int nq_pad, int d, int NS, const double* mean, uint16_t* Pr, uint16_t* Pq,
+                  const int32_t* qrows, int nq, int nq_pad, int d, int NS, int shape, const double* mean, uint16_t* Pr, uint16_t* Pq,
                   double* rn2, double* qn2, unsigned long long* maxbits, unsigned long long* slots, int32_t* flagged0,
                   float* margin, const sel::PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init);
 bool f16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L);

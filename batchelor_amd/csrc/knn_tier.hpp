@@ -42,14 +42,25 @@ struct Stamps {
 #ifdef BMX_STAMPS
     unsigned long long v[NCOUNTERS] = {};
     unsigned long long t0 = 0;
+    unsigned long long rt0 = 0, sweep_cycles = 0, sweep_ticks = 0;
     __device__ __forceinline__ static unsigned long long now() { return __builtin_readcyclecounter(); }
-    __device__ __forceinline__ void begin() { t0 = now(); }
+    // the constant 100 MHz counter (s_memrealtime) beside the cycle counter (s_memtime), read where a consumer's sweep
+    // starts and where it ends: cycles / ticks x 100 MHz is the clock the sweep ran at
+    __device__ __forceinline__ void begin() {
+        rt0 = __builtin_amdgcn_s_memrealtime();
+        t0 = now();
+    }
+    __device__ __forceinline__ void sweep_end() {
+        sweep_cycles = now() - t0;
+        sweep_ticks = __builtin_amdgcn_s_memrealtime() - rt0;
+    }
     __device__ __forceinline__ unsigned long long elapsed() const { return now() - t0; }
     __device__ __forceinline__ void add(Counter c, unsigned long long x) { v[c] += x; }
     __device__ __forceinline__ unsigned long long get(Counter c) const { return v[c]; }
 #else
     __device__ __forceinline__ static unsigned long long now() { return 0; }
     __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void sweep_end() {}
     __device__ __forceinline__ unsigned long long elapsed() const { return 0; }
     __device__ __forceinline__ void add(Counter, unsigned long long) {}
     __device__ __forceinline__ unsigned long long get(Counter) const { return 0; }

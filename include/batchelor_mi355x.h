@@ -124,7 +124,9 @@ void bmx_set_force_exact_knn(int32_t on);
  * reference's partitions after the first are searched within the first's 36th distance, the default; 0 = all plainly), "tau_replay" (developer experiment: 1 = every search of
  * a run records its queries' final thresholds, 2 = the same sequence of searches starts its full passes from them),
  * "asv_strict" (-1 = every adjust_shift_variance call is strict where its caller says so, the default; 1 = every call is
- * strict: times strict mode on a workload whose driver has no switch for it), "reset" (all back to their defaults).
+ * strict: times strict mode on a workload whose driver has no switch for it), "mfma_shape" (fp16 tier: the MFMA shape of the
+ * candidate sweep, 0 = 32x32x16, 1 = 16x16x32 where the row width has it; -1 = the library's table, the default),
+ * "reset" (all back to their defaults).
  * Unknown name: BMX_ERR_ARG. */
 int32_t bmx_dev_set(const char* name, int32_t value);
 /* Counters for tests and bench.py, current device: "asv_tiled_cells" (cells the tiled form of adjust_shift_variance has
@@ -137,7 +139,10 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
  * owns, pairs of a step it walks), "delta_sparse_gene_tile" (genes a workgroup of bmx_delta_sparse_run's owns), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
  * genes a workgroup of the sparse one owns), "cluster_sparse_gene_tile" (genes a workgroup of bmx_cluster_sparse_centroids
- * keeps in the LDS). */
+ * keeps in the LDS).  Of the searches of this thread's single-primitive entry points (bmx_query_knn, bmx_find_mutual_nn ...),
+ * added up since the thread's first: "knn_exact_fallbacks" (queries finished by the FP64 paths) and "knn_tier2_queries" (queries
+ * the first candidate tier handed to the second) -- what bmx_engine_profile_detail reports of an engine; "knn_mfma_shape"
+ * (the MFMA shape the last fp16 candidate pass of those searches ran with: 0 = 32x32x16, 1 = 16x16x32, -1 = none yet). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
  * call went -- 0 the histogram quantile (a well-conditioned cell), 1 re-run in the reference's order of operations, 2
