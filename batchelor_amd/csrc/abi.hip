@@ -76,6 +76,54 @@ __global__ void idx_to_r_layout(const int32_t* __restrict__ in, int nq, int k, i
     }
 }
 
+// The way out of queryKNN / findKNN: a search's lists pi / pd [nq][k] (device, 0-based, row-major; the search still on the
+// engine's stream) into the caller's index / distance in R's layout (either may be null).  Notes the search's exact
+// fall-backs for bmx_last_knn_exact_fallbacks; returns with the stream idle.
+void knn_lists_to_caller(bmx::Engine& e, const int32_t* pi, const double* pd, int nq, int k, int32_t* index, double* distance) {
+    hipStream_t s = e.stream();
+    // (k = 5 000 on 100 000 queries is 6 GB of results: no value-initialised vectors, the copies through the pinned staging
+    // ring, the transposition into R's column-major layout by the pool of host threads, 512 queries a piece)
+    const size_t nres = (size_t)nq * k;
+    if (nres >= ((size_t)1 << 22)) {
+        // large results: transposed into R's layout ON THE DEVICE and sent straight into the caller's arrays through the
+        // staging ring (k = 5 000 on 100 000 queries: 6 GB that the host threads -- 16 CPUs of quota on this pool's boxes --
+        // would otherwise read and write once more)
+        g_last_fallbacks = e.knn_ws_.last_exact;
+        bmx::DevBuf<int32_t> dIc;
+        if (index) {
+            int32_t* pc = dIc.reserve(nres);
+            hipLaunchKernelGGL(idx_to_r_layout, dim3((unsigned)((nq + 31) / 32), (unsigned)((k + 31) / 32)), dim3(32, 8), 0, s,
+                               pi, nq, k, pc);
+            BMX_LAUNCH_CHECK();
+            bmx::download_pageable(index, pc, nres * sizeof(int32_t), s);
+        }
+        if (distance) {
+            bmx::DevBuf<double> dDc;
+            double* pc = dDc.reserve(nres);
+            bmx::transpose_rm_to_cm(s, pd, nq, k, pc, nq, 0);
+            bmx::download_pageable(distance, pc, nres * sizeof(double), s);
+            BMX_HIP(hipStreamSynchronize(s));
+        }
+        BMX_HIP(hipStreamSynchronize(s));
+        return;
+    }
+    std::unique_ptr<int32_t[]> hi(index ? new int32_t[nres] : nullptr);
+    std::unique_ptr<double[]> hd(distance ? new double[nres] : nullptr);
+    if (index) bmx::download_pageable(hi.get(), pi, nres * sizeof(int32_t), s);
+    if (distance) bmx::download_pageable(hd.get(), pd, nres * sizeof(double), s);
+    BMX_HIP(hipStreamSynchronize(s));
+    g_last_fallbacks = e.knn_ws_.last_exact;
+    const int64_t piece = 512, npieces = (nq + piece - 1) / piece;
+    bmx::HostPool::get().parallel_for((size_t)npieces, [&](size_t pc) {
+        const int64_t q0 = (int64_t)pc * piece, q1 = std::min<int64_t>(nq, q0 + piece);
+        for (int64_t j = 0; j < k; ++j)
+            for (int64_t q = q0; q < q1; ++q) {
+                if (index) index[j * nq + q] = hi[(size_t)(q * k + j)] + 1;
+                if (distance) distance[j * nq + q] = hd[(size_t)(q * k + j)];
+            }
+    });
+}
+
 // host column-major [n x d] -> device row-major
 double* upload_rm(bmx::DevBuf<double>& tmp, bmx::DevBuf<double>& out, const double* cm, int n, int d, hipStream_t s) {
     const double* dcm = upload(tmp, cm, (size_t)n * d, s);
@@ -295,52 +343,44 @@ int32_t bmx_query_knn(const double* X, int32_t nx, const double* query, int32_t 
         bmx::CacheScope cache_scope(e.cache());
         hipStream_t s = e.stream();
         bmx::DevBuf<double> t1, t2, dX, dQ, dD;
-        bmx::DevBuf<int32_t> dI, dIc;
+        bmx::DevBuf<int32_t> dI;
         const double* px = upload_rm(t1, dX, X, nx, d, s);
         const double* pq = upload_rm(t2, dQ, query, nq, d, s);
         int32_t* pi = dI.reserve((size_t)nq * k);
         double* pd = dD.reserve((size_t)nq * k);
         e.knn(px, nullptr, nx, pq, nullptr, nq, k, pi, pd);
-        // (k = 5 000 on 100 000 queries is 6 GB of results: no value-initialised vectors, the copies through the pinned staging
-        // ring, the transposition into R's column-major layout by the pool of host threads, 512 queries a piece)
-        const size_t nres = (size_t)nq * k;
-        if (nres >= ((size_t)1 << 22)) {
-            // large results: transposed into R's layout ON THE DEVICE and sent straight into the caller's arrays through the
-            // staging ring (k = 5 000 on 100 000 queries: 6 GB that the host threads -- 16 CPUs of quota on this pool's boxes --
-            // would otherwise read and write once more)
-            g_last_fallbacks = e.knn_ws_.last_exact;
-            if (index) {
-                int32_t* pc = dIc.reserve(nres);
-                hipLaunchKernelGGL(idx_to_r_layout, dim3((unsigned)((nq + 31) / 32), (unsigned)((k + 31) / 32)), dim3(32, 8), 0, s,
-                                   (const int32_t*)pi, nq, k, pc);
-                BMX_LAUNCH_CHECK();
-                bmx::download_pageable(index, pc, nres * sizeof(int32_t), s);
-            }
-            if (distance) {
-                bmx::DevBuf<double> dDc;
-                double* pc = dDc.reserve(nres);
-                bmx::transpose_rm_to_cm(s, pd, nq, k, pc, nq, 0);
-                bmx::download_pageable(distance, pc, nres * sizeof(double), s);
-                BMX_HIP(hipStreamSynchronize(s));
-            }
-            BMX_HIP(hipStreamSynchronize(s));
-            return;
+        knn_lists_to_caller(e, pi, pd, nq, k, index, distance);
+    });
+}
+
+int32_t bmx_find_knn(const double* X, int32_t n, int32_t d, int32_t k, const int32_t* subset, int32_t n_subset,
+                     int32_t* index, double* distance) {
+    return guarded([&] {
+        if (n < 0 || d <= 0 || k < 0) throw bmx::Error(BMX_ERR_ARG, "findKNN: negative dimension");
+        if (subset && n_subset < 0) throw bmx::Error(BMX_ERR_ARG, "findKNN: negative length of 'subset'");
+        if (k > n - 1) throw bmx::Error(BMX_ERR_ARG, "findKNN: 'k' exceeds the number of other points in 'X'");
+        const int nq = subset ? n_subset : n;
+        std::vector<int32_t> rows(subset ? (size_t)nq : 0);  // 0-based
+        for (int i = 0; i < (int)rows.size(); ++i) {
+            if (subset[i] < 1 || subset[i] > n) throw bmx::Error(BMX_ERR_ARG, "findKNN: 'subset' indices out of range");
+            rows[i] = subset[i] - 1;
         }
-        std::unique_ptr<int32_t[]> hi(index ? new int32_t[nres] : nullptr);
-        std::unique_ptr<double[]> hd(distance ? new double[nres] : nullptr);
-        if (index) bmx::download_pageable(hi.get(), pi, nres * sizeof(int32_t), s);
-        if (distance) bmx::download_pageable(hd.get(), pd, nres * sizeof(double), s);
-        BMX_HIP(hipStreamSynchronize(s));
-        g_last_fallbacks = e.knn_ws_.last_exact;
-        const int64_t piece = 512, npieces = (nq + piece - 1) / piece;
-        bmx::HostPool::get().parallel_for((size_t)npieces, [&](size_t pc) {
-            const int64_t q0 = (int64_t)pc * piece, q1 = std::min<int64_t>(nq, q0 + piece);
-            for (int64_t j = 0; j < k; ++j)
-                for (int64_t q = q0; q < q1; ++q) {
-                    if (index) index[j * nq + q] = hi[(size_t)(q * k + j)] + 1;
-                    if (distance) distance[j * nq + q] = hd[(size_t)(q * k + j)];
-                }
-        });
+        if (nq == 0 || k == 0) return;
+        bmx::Engine& e = prim(d);
+        bmx::CacheScope cache_scope(e.cache());
+        hipStream_t s = e.stream();
+        bmx::DevBuf<double> t1, dX, dD1, dD;
+        bmx::DevBuf<int32_t> dR, dI1, dI;
+        const double* px = upload_rm(t1, dX, X, n, d, s);  // once: the reference rows and the queries
+        const int32_t* pr = subset ? upload(dR, rows.data(), rows.size(), s) : nullptr;
+        // the search at k + 1 (the row itself is a neighbour at distance 0), then the row itself out of its list (knn_self.hip)
+        int32_t* pi1 = dI1.reserve((size_t)nq * (k + 1));
+        double* pd1 = dD1.reserve((size_t)nq * (k + 1));
+        e.knn(px, nullptr, n, px, pr, nq, k + 1, pi1, pd1);
+        int32_t* pi = dI.reserve((size_t)nq * k);
+        double* pd = dD.reserve((size_t)nq * k);
+        bmx::knn_drop_self(s, pi1, pd1, pr, nq, k, pi, pd);
+        knn_lists_to_caller(e, pi, pd, nq, k, index, distance);  // (waits for the stream: `rows` may go)
     });
 }
 

@@ -155,6 +155,13 @@ void add_scaled_rows(hipStream_t stream, double* X, int n, int d, const double* 
 void transpose_cm_to_rm(hipStream_t stream, const double* cm, int n, int d, double* rm);  // [n x d] col-major -> row-major
 void transpose_rm_to_cm(hipStream_t stream, const double* rm, int n, int d, double* cm, int ld_cm, int row_off);
 
+// ---- findKNN (knn_self.hip) ---------------------------------------------------------------------------
+// The lists of a search of X against itself at k + 1, idx_in / dist_in [nq][k + 1] (0-based rows of X, knn_device), without
+// the query's own row (q_rows[q], null: q): idx_out / dist_out [nq][k], other buffers than the inputs.  Where the own row is
+// not among the k + 1 the last entry goes.  dist_in / dist_out may both be null.
+void knn_drop_self(hipStream_t stream, const int32_t* idx_in, const double* dist_in, const int32_t* q_rows, int nq, int k,
+                   int32_t* idx_out, double* dist_out);
+
 // ---- upstream of the engine (prepca.hip): cosineNorm + PCA projection, x is genes x cells column-major ----------
 void cosine_l2_device(hipStream_t stream, const double* x, int G, int n, double* l2);
 // out[c] = l2 of cell c over the 0-based genes listed (genes0 null: over all G), c in [0, n); inverse: 1 / pmax(1e-8, l2)

@@ -1,4 +1,5 @@
-"""BiocNeighbors-shaped entry points used on the fastMNN path (queryKNN, findMutualNN), served by the HIP kernels."""
+"""BiocNeighbors-shaped entry points used on the fastMNN path (queryKNN, findMutualNN) and after it (findKNN on the
+corrected coordinates), served by the HIP kernels."""
 from __future__ import annotations
 
 import ctypes
@@ -6,6 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .inputs import subset_index
 
 
 def query_knn(X, query, k, get_index=True, get_distance=True):
@@ -26,6 +28,36 @@ def query_knn(X, query, k, get_index=True, get_distance=True):
     _lib.check(_lib.lib().bmx_query_knn(_lib.f64p(X), nx, _lib.f64p(query), nq, d, k,
                                         _lib.i32p(index) if get_index else None,
                                         _lib.f64p(distance) if get_distance else None))
+    return index, distance
+
+
+def find_knn(X, k, subset=None, get_index=True, get_distance=True):
+    """findKNN(X, k, subset=): each row's k nearest OTHER rows of X (or those of the rows `subset` names: 1-based integers in
+    any order, repeats kept, or a logical mask over the rows).
+
+    Returns (index [nq x k] 1-based into rows of X, distance [nq x k] Euclidean), ascending distance, exact, ties to the
+    lower row.  A row is never in its own list; rows that coincide with it are.  X goes to the device once; the search is
+    query_knn's at k + 1 (so k = 36 on at most 61 columns and k = 20 beyond take its partitioned path: exact, slower).
+    """
+    X = _lib.as_f(X)
+    if X.ndim != 2:
+        raise ValueError("'X' must be a matrix")
+    n, d = X.shape
+    k = int(k)
+    if k < 0 or k > n - 1:
+        raise ValueError("'k' must be between 0 and the number of other points in 'X'")
+    rows = subset_index(subset, n)
+    if rows is not None and rows.ndim != 1:
+        raise ValueError("'subset' must be a vector")
+    if d == 0:
+        raise ValueError("'X' has no columns")
+    _lib.require_gpu()
+    nq = n if rows is None else rows.size
+    index = np.zeros((nq, k), dtype=np.int32, order="F")
+    distance = np.zeros((nq, k), dtype=np.float64, order="F")
+    _lib.check(_lib.lib().bmx_find_knn(_lib.f64p(X), n, d, k, None if rows is None else _lib.i32p(rows), nq,
+                                       _lib.i32p(index) if get_index else None,
+                                       _lib.f64p(distance) if get_distance else None))
     return index, distance
 
 

@@ -92,13 +92,25 @@ int32_t bmx_adjust_shift_variance_form(int32_t n2, int32_t nr1, int32_t nr2);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Third-party contract on the path: BiocNeighbors::queryKNN / findMutualNN (re-export R/findMutualNN.R:1-3; call
- * sites R/MNN_tree.R:129, R/fastMNN.R:605).  Exact Euclidean search, ascending distance, ties by lowest index.
+ * sites R/MNN_tree.R:129, R/fastMNN.R:605), and queryKNN's sibling findKNN for what workflows do next with the corrected
+ * coordinates.  Exact Euclidean search, ascending distance, ties by lowest index.
  * ---------------------------------------------------------------------------------------------------------------- */
 
 /* queryKNN(X, query, k): X [nx x d], query [nq x d] column-major; index [nq x k] 1-based, distance [nq x k]
  * (either output may be NULL).  k is clamped to nx by the caller (safe.k, R/fastMNN.R:604). */
 int32_t bmx_query_knn(const double* X, int32_t nx, const double* query, int32_t nq, int32_t d, int32_t k,
                       int32_t* index, double* distance);
+
+/* findKNN(X, k, subset): for each row of X (or each row named in `subset`, 1-based, any order, repeats allowed; NULL = all)
+ * its k nearest OTHER rows of X: index 1-based [nq x k] column-major, distance Euclidean, ascending, ties to the lower
+ * row; the row itself is never in its own list, rows that coincide with it are.  0 <= k <= n - 1.  X as in bmx_query_knn.
+ * nq = n_subset with a subset (n_subset is ignored without one), else n; either output may be NULL; k = 0 or no query
+ * row writes nothing.  X goes to the device once and is searched against itself at k + 1 by the search of bmx_query_knn;
+ * on the device each list then loses the row's own entry, or its last entry where k + 1 lower-numbered copies of the row
+ * fill the list.  Searching at k + 1 means that k = 36 on rows of at most 61 columns and k = 20 on longer rows leave the
+ * candidate tiers' lists for the partitioned search: exact as everything here, slower. */
+int32_t bmx_find_knn(const double* X, int32_t n, int32_t d, int32_t k, const int32_t* subset, int32_t n_subset,
+                     int32_t* index, double* distance);
 
 /* findMutualNN(data1, data2, k1, k2) -> first / second, 1-based, malloc'ed (bmx_free). */
 int32_t bmx_find_mutual_nn(const double* data1, int32_t n1, const double* data2, int32_t n2, int32_t d, int32_t k1,
@@ -139,7 +151,7 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * Constants, no device needed: "delta_gene_tile" / "delta_pair_chunk" (genes a workgroup of bmx_delta_run's pair passes
  * owns, pairs of a step it walks), "delta_sparse_gene_tile" (genes a workgroup of bmx_delta_sparse_run's owns), "genevar_chunk" / "genevar_gene_tile" (cells of a chunk of the gene-variance handles,
  * genes a workgroup of the sparse one owns), "cluster_sparse_gene_tile" (genes a workgroup of bmx_cluster_sparse_centroids
- * keeps in the LDS).  Of the searches of this thread's single-primitive entry points (bmx_query_knn, bmx_find_mutual_nn ...),
+ * keeps in the LDS).  Of the searches of this thread's single-primitive entry points (bmx_query_knn, bmx_find_knn, bmx_find_mutual_nn ...),
  * added up since the thread's first: "knn_exact_fallbacks" (queries finished by the FP64 paths) and "knn_tier2_queries" (queries
  * the first candidate tier handed to the second) -- what bmx_engine_profile_detail reports of an engine; "knn_mfma_shape"
  * (the MFMA shape the last fp16 candidate pass of those searches ran with: 0 = 32x32x16, 1 = 16x16x32, -1 = none yet). */
