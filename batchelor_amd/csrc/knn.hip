@@ -144,7 +144,7 @@ PassEps tier_pass_eps(const Tier& T, int d) {
         pe.eps_qr = 6.0;                                                   // three product blocks, each <= 2 |q||r|
         pe.eps_split = 1.5 * 3.03 * 2.0 * 1.52587890625e-05;               // dropped ql.rl, qh.r3, q3.rh: 3.03 * 2^-16 * 2|q||r|
         pe.eps_den = 0.0;
-        pe.scaled = 0;
+        pe.scaled = 0;                                                     // (where that holds: pass_window, knn_select.hpp)
     }
     return pe;
 }

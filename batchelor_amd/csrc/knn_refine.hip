@@ -36,7 +36,7 @@ __device__ __forceinline__ PassError pass_error(double qn2q, const unsigned long
     const double max_rn2 = __longlong_as_double((long long)*max_rn2_bits);
     const double s = scaled ? pass_scale(max_rn2) : 1.0;
     const double s2inv = 1.0 / (s * s);
-    const double eps = pass_eps(sqrt(qn2q), sqrt(max_rn2), s, eps_k, eps_qr, eps_split, eps_den);
+    const double eps = pass_bound(qn2q, max_rn2, s, scaled, eps_k, eps_qr, eps_split, eps_den);
     return PassError{s, s2inv, eps};
 }
 

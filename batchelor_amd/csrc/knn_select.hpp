@@ -45,12 +45,30 @@ __device__ __forceinline__ double pass_eps(double qn, double rm, double s, doubl
            eps_split * qn * rm + eps_den * ((2.0 * qn + rm) * s + 1.0) / (s * s);
 }
 
+// Exponent window of an UNSCALED pass (split-bf16 tier): its norms are (float)|r~|^2, its products and sums f32, and
+// pass_eps is a relative bound -- it holds while nothing overflows and while what underflows is small against u |r|^2.
+//   above: |q~|^2, max |r~|^2 <= 2^100 keeps every norm, product and partial sum (<= |r|^2 + 6 |q||r|) below 2^103;
+//   below: max |r~|^2 >= 2^-80: the ~2^10 products and additions of a value lose at most 2^-126 each to underflow
+//          (flushed or not), 2^-116 in all, against the 0.5 u (eps_k + 1) |r|^2 >= 2^-105 that pass_eps keeps in hand.
+// (max |r~|^2 = 0: every reference IS the centre, every value an exact 0.)  Outside the window the bound is +inf: every
+// query fails the certificate of knn_refine and goes on to the next tier, as a query with a NaN norm does in the fp16 tier.
+__device__ __forceinline__ bool pass_window(double qn2, double max_rn2) {
+    return (max_rn2 == 0.0 || max_rn2 >= 0x1p-80) && max_rn2 <= 0x1p100 && qn2 <= 0x1p100;  // (NaN: outside)
+}
+
+// pass_eps of query |q~|^2 = qn2 for the tier's constants; +inf for an unscaled pass outside its window
+__device__ __forceinline__ double pass_bound(double qn2, double max_rn2, double s, int scaled, double eps_k, double eps_qr,
+                                             double eps_split, double eps_den) {
+    if (!scaled && !pass_window(qn2, max_rn2)) return __builtin_inf();
+    return pass_eps(sqrt(qn2), sqrt(max_rn2), s, eps_k, eps_qr, eps_split, eps_den);
+}
+
 // Twice the pass's error bound for a query of squared norm qn2, in the pass's own (scaled) units, rounded up: a reference
 // whose approximate value exceeds the k-th best approximate value by more than this is farther, exactly, than each of
 // those k -- the cut knn_refine applies to the candidates, handed to the pass itself so that it stops collecting them.
 __device__ __forceinline__ float pass_margin(double qn2, double max_rn2, const PassEps& pe) {
     const double s = pe.scaled ? pass_scale(max_rn2) : 1.0;
-    const double eps = pass_eps(sqrt(qn2), sqrt(max_rn2), s, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den);
+    const double eps = pass_bound(qn2, max_rn2, s, pe.scaled, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den);
     const double x = 2.0 * eps * (s * s) * 1.0000002 + 1e-30;
     return (float)(x * 1.000001);  // (the f32 rounding cannot land below x)
 }
@@ -60,7 +78,7 @@ __device__ __forceinline__ float pass_margin(double qn2, double max_rn2, const P
 // filtered out.
 __device__ __forceinline__ uint32_t pass_seed_tau(double seed_d2, double qn2, double max_rn2, const PassEps& pe) {
     const double s = pe.scaled ? pass_scale(max_rn2) : 1.0;
-    const double eps = pass_eps(sqrt(qn2), sqrt(max_rn2), s, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den);
+    const double eps = pass_bound(qn2, max_rn2, s, pe.scaled, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den);
     const double x = (seed_d2 - qn2 + eps) * (s * s);
     const float t = (float)(x + fabs(x) * 9.5367431640625e-7 + 1e-30);  // + 2^-20 relative: the f32 rounding cannot land below x
     return f32_orderable(t);
