@@ -6,9 +6,10 @@
 // and ONE v_mfma_f32_32x32x16_bf16 chain over the concatenated K = [qh|qh|ql|1 1 1] . [rh|rl|rh|n1 n2 n3] yields
 //     v = |r|^2 + qh.rh + qh.rl + ql.rh        (|r|^2 as three bf16 pieces: exact to 2^-24)
 // with |v - (|r|^2 - 2 q.r)| <= 3.03 * 2^-16 * 2 |q||r| + f32 accumulation error -- the bound knn_refine certifies
-// against.  10 MFMAs of 32 cycles per 32x32 tile at 50 PCs instead of 28 of 64 cycles.
+// against.  10 MFMAs of 32 cycles per 32x32 tile at 50 PCs instead of 28 of 64 cycles.  (The prepared images: knn_prep.hip.)
 //
-// At that rate the matrix pipe is no longer the limit; staging and selection are.  Structure of a workgroup:
+// At that rate the matrix pipe is no longer the limit; staging and selection are.  Structure of a workgroup
+// (knn_bf16_shape.hpp has its numbers and its LDS layout):
 //   * NCONS consumer waves, 32 queries each: query fragments resident in VGPRs; per query a sorted kept list and two
 //     lane-private pending lists in the LDS, their lengths and the working threshold in registers (knn_select.hpp);
 //   * NPROD producer waves stream the reference tiles (fragment-major, 1 KiB coalesced reads, two or three tiles in
@@ -19,6 +20,9 @@
 //     A consumer that is busy merging a candidate list therefore delays nobody until the ring runs dry;
 //   * the consumer loop is software-pipelined: under the dependent MFMA chain of tile t the wave refills its
 //     fragment registers with tile t + 1 and filters tile t - 1; appends and list merges of tile t - 1 follow.
+// The kernel by role: producer_role and write_final_lists are functions of the pass's context; the consumers' sweep is the
+// kernel's body, as lambdas on its locals (MEASUREMENTS.md, "What stayed inline", has why).
+#include "knn_bf16_shape.hpp"
 #include "knn_tier.hpp"
 
 #include <cmath>
@@ -27,171 +31,171 @@ namespace bmx {
 namespace {
 
 using namespace sel;
+using namespace bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) const char* lds_cptr;
+typedef __attribute__((address_space(3))) const f32x4* lds_f4ptr;
 
-// Workgroup shape per (fragment count, list size): NCONS consumer waves of 32 queries, NPROD producer waves (producer p
-// stages tiles p, p + NPROD, ... into ring slot tile % NSLOT), PLN entries per lane-private pending list.
-// 8 + 4 puts two consumers and one producer on every SIMD.  Measured alternatives at 100k x 100k, d = 50 (cycles per
-// tile per consumer wave, 1480 for 8 + 4): 9 + 3 -> 1750, 10 + 2 -> 1940 -- the SIMDs that get a third consumer fall
-// behind and the ring makes everybody else wait for them, so more queries per CU did not pay.
-struct RingShape {
-    int ncons, nprod, pln;
+// What the roles of a workgroup share: where its LDS regions lie, who the wave is, the work item.  The roles take it BY VALUE:
+// taken by reference the producers' tile addresses compile to other code than they do in the kernel's body (one base and
+// immediate offsets instead of an address a fragment; up to two registers more at NS = 13 and 19), by value to the same.  The
+// pass's buffers go to the roles as parameters of their own, __restrict__ as the kernel's.
+template <int NS, int KS>
+struct PassCtx {
+    using S = Bf16Shape<NS, KS>;
+    Bf16Lds<S> lds;
+    int lane, wave;           // (wave: wave-uniform, branches on it are scalar)
+    int qblock, nrng;         // the work item (knn_tier.hpp): its query block, the ranges the block is split into
+    int r_begin, ntiles;      // ... its reference range: first row, 32-row tiles
+    int out_chunk, out_nchunks;  // the list column this item writes, of how many
 };
-__host__ __device__ constexpr RingShape ring_shape(int NS, int KS) {
-    return (NS <= 13 && KS == 24) ? RingShape{8, 4, 12} : RingShape{4, 4, 12};
-}
 
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7F800000u) == 0x7F800000u) return (uint16_t)(u >> 16);  // inf / nan pass through
-    u += 0x7FFFu + ((u >> 16) & 1u);                                   // round to nearest even
-    return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf16_to_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
-
-// logical element L of a prepared row -> position inside the fragment-major reference tile
-__device__ __forceinline__ int64_t frag_pos(int r, int L, int NS) {
-    const int hk = 8 * NS;  // elements per lane half
-    const int h = L / hk, s = (L % hk) >> 3, j = L & 7;
-    return ((((int64_t)(r >> 5) * NS + s) * 64 + h * 32 + (r & 31)) << 3) + j;
-}
-
-// One workgroup prepares one 32-row tile: rows are staged in LDS with coalesced reads, every output element is
-// computed from there, and the tile image (fragment-major for references, row-major for queries -- both contiguous
-// per tile) is written out in 16-byte pieces, consecutive threads writing consecutive pieces.
-__global__ __launch_bounds__(256) void knn_prep_bf16(const double* __restrict__ X, const int32_t* __restrict__ rows,
-                                                     int n, int n_pad, int d, int NS, const double* __restrict__ mean,
-                                                     int is_query, uint16_t* __restrict__ P, double* __restrict__ n2,
-                                                     unsigned long long* __restrict__ max_n2_bits) {
-    extern __shared__ __attribute__((aligned(16))) char smem_pp[];
-    const int K = 16 * NS;
-    float* xs = reinterpret_cast<float*>(smem_pp);                       // [32][d] centred, rounded to f32
-    float* nrm = xs + 32 * d;                                            // [32] f32(|x~|^2)
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * 32;
-    (void)n_pad;
-    // (row, column) of a flat element index without an integer division: e < 32 * 128, so the float quotient is exact
-    const float inv_d = 1.0f / (float)d;
-    for (int e = tid; e < 32 * d; e += 256) {
-        int rr = (int)(((float)e + 0.5f) * inv_d);
-        int c = e - rr * d;
-        if (c < 0) {
-            --rr;
-            c += d;
-        } else if (c >= d) {
-            ++rr;
-            c -= d;
-        }
-        const int r = r0 + rr;
-        float f = 0.f;
-        if (r < n) {
-            const int64_t row = rows ? rows[r] : r;
-            f = (float)(X[row * d + c] - mean[c]);
-        }
-        xs[e] = f;
-    }
-    __syncthreads();
-    // eight threads per row from here on: thread (rr, sub) owns the elements L = sub (mod 8) of row rr
-    const int rr = tid >> 3, sub = tid & 7;
-    const bool live = r0 + rr < n;
-    {
-        double s = 0.0;  // |x~|^2 of the f32-rounded centred row (exact products, FP64 sum; any order will do)
-        for (int c = sub; c < d; c += 8) {
-            const double f = (double)xs[rr * d + c];
-            s += f * f;
-        }
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        s += __shfl_xor(s, 4);
-        if (sub == 0) {
-            nrm[rr] = (float)s;
-            if (live) n2[r0 + rr] = s;
-        }
-        if (!is_query) {
-            // one atomic per wave, spread over 64 words a cache line apart (a single word serialises the whole
-            // launch in the L2's atomic unit: it was the bulk of this kernel's time); fold_max_slots() finishes
-            double m = live ? s : 0.0;
-            for (int o = 8; o < 64; o <<= 1) m = fmax(m, __shfl_xor(m, o));
-            if ((tid & 63) == 0)
-                atomicMax(max_n2_bits + (size_t)(blockIdx.x & 63) * 16, (unsigned long long)__double_as_longlong(m));
-        }
-    }
-    __syncthreads();
-    // 16-byte pieces (8 consecutive elements of a row) straight from the staged rows to global memory: consecutive
-    // threads write consecutive pieces of the tile image (fragment-major for references: k-step, lane half, row;
-    // row-major for queries)
-    uint4* out = reinterpret_cast<uint4*>(P + (int64_t)r0 * K);
-    const int npieces = 32 * 2 * NS;
-    const float inv_pc = 1.0f / (float)(2 * NS);
-    for (int p = tid; p < npieces; p += 256) {
-        int prow, i;  // row of the tile, 8-element chunk of the row
-        if (is_query) {
-            prow = (int)(((float)p + 0.5f) * inv_pc);
-            i = p - prow * 2 * NS;
-            if (i < 0) {
-                --prow;
-                i += 2 * NS;
-            } else if (i >= 2 * NS) {
-                ++prow;
-                i -= 2 * NS;
-            }
-        } else {
-            prow = p & 31;
-            const int ih = p >> 5;  // = 2 * k-step + lane half
-            i = (ih & 1) * NS + (ih >> 1);
-        }
-        const bool plive = r0 + prow < n;
-        const float nf = nrm[prow];  // its three bf16 pieces reproduce the f32 value exactly
-        const uint16_t na = f32_to_bf16(nf);
-        const float nr1 = nf - bf16_to_f32(na);
-        const uint16_t nb = f32_to_bf16(nr1);
-        const uint16_t nc = f32_to_bf16(nr1 - bf16_to_f32(nb));
-        uint32_t w[4];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int L = 8 * i + e;
-            uint16_t v = 0;
-            if (L < 3 * d) {
-                const int blk = (L >= d) + (L >= 2 * d), c = L - blk * d;
-                const float f = xs[prow * d + c];
-                const float g = is_query ? -2.f * f : f;
-                const uint16_t hi = f32_to_bf16(g);
-                const bool want_lo = is_query ? blk == 2 : blk == 1;
-                v = want_lo ? f32_to_bf16(g - bf16_to_f32(hi)) : hi;
-            } else if (L < 3 * d + 3) {
-                const int piece = L - 3 * d;
-                if (is_query)
-                    v = plive ? 0x3F80 : 0;  // 1.0 (padded queries stay all-zero)
-                else if (!plive)
-                    v = piece == 0 ? 0x7F80 : 0;  // +inf: a padded reference never passes a threshold
-                else
-                    v = piece == 0 ? na : (piece == 1 ? nb : nc);
-            }
-            if (e & 1)
-                w[e >> 1] |= (uint32_t)v << 16;
-            else
-                w[e >> 1] = v;
-        }
-        out[p] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// Ring depth: as many staged tiles as the LDS left over by the candidate lists holds (at most 8).  The consumers of a
-// workgroup stall at different times (a compaction costs a couple of tile times); the deeper the ring, the less one
-// consumer's stall holds up the others.
-__host__ __device__ constexpr int ring_slots(int NS, int KS, int NCONS, int PLN) {
-    const int rest = 160 * 1024 - NCONS * 32 * list_pitch(KS, PLN) * 8 - 512;
-    const int n = rest / (NS * 1024);
-    return n > 8 ? 8 : n;
-}
-
-#ifndef BMX_YIELD_TILES
-#define BMX_YIELD_TILES 8
-#endif
+// ---- the cycle stamps of the developer build leave the kernel here (make STAMPS=1; launch() prints them)
 #ifdef BMX_STAMPS
 __device__ unsigned long long bmx_dbg[48];
+__device__ __forceinline__ void stamps_out_producer(const Stamps& st, const int lane, const int p) {
+    if (lane == 0) {
+        atomicAdd(&bmx_dbg[32 + p], st.get(Stamps::PWAIT));
+        atomicAdd(&bmx_dbg[36 + p], st.elapsed());
+    }
+}
+__device__ __forceinline__ void stamps_out_consumer(const Stamps& st, const int lane, const int wave, const int ntiles) {
+    if (lane == 0) {
+        atomicAdd(&bmx_dbg[0], st.elapsed());
+        atomicAdd(&bmx_dbg[1], st.get(Stamps::SPIN));
+        atomicAdd(&bmx_dbg[2], st.get(Stamps::COMP));
+        atomicAdd(&bmx_dbg[3], st.get(Stamps::NSPIN));
+        atomicAdd(&bmx_dbg[4], st.get(Stamps::NFLUSH));
+        atomicAdd(&bmx_dbg[5], st.get(Stamps::NCOMP));
+        atomicAdd(&bmx_dbg[6], st.get(Stamps::EVT));
+        atomicAdd(&bmx_dbg[7], st.get(Stamps::GRP));
+        atomicAdd(&bmx_dbg[8], (unsigned long long)ntiles);
+        atomicAdd(&bmx_dbg[9], 1ull);
+        atomicAdd(&bmx_dbg[10], st.get(Stamps::EVC));
+        atomicAdd(&bmx_dbg[16 + wave], st.get(Stamps::SPIN));
+        atomicAdd(&bmx_dbg[24 + wave], st.get(Stamps::COMP));
+    }
+}
+#else
+__device__ __forceinline__ void stamps_out_producer(const Stamps&, const int, const int) {}
+__device__ __forceinline__ void stamps_out_consumer(const Stamps&, const int, const int, const int) {}
 #endif
 
+// =====================================================================================================================
+// producer waves: reference tiles from global memory into the ring
+// =====================================================================================================================
+template <int NS, int KS, bool SAMPLE>
+__device__ __forceinline__ void producer_role(const PassCtx<NS, KS> cx, const uint16_t* __restrict__ PrF) {
+    using S = Bf16Shape<NS, KS>;
+    constexpr int NCONS = S::NCONS, NPROD = S::NPROD, NSLOT = S::NSLOT, TILE_BYTES = S::TILE_BYTES;
+    const int lane = cx.lane, ntiles = cx.ntiles;
+    int* const ready = cx.lds.ready;
+    int* const done = cx.lds.done;
+    const int p = cx.wave - NCONS;
+    Stamps st;
+    st.begin();
+    f32x4 ra[NS], rb[NS];
+    const f32x4* src = reinterpret_cast<const f32x4*>(PrF) + ((int64_t)(cx.r_begin >> 5) * NS) * 64 + lane;
+    f32x4* ring_l = reinterpret_cast<f32x4*>(cx.lds.ring) + lane;
+    auto load = [&](f32x4(&r)[NS], int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) r[s] = src[((int64_t)t * NS + s) * 64];
+    };
+    // tile t goes to slot t % NSLOT once every consumer has read the tile staged there NSLOT tiles earlier (that
+    // tile may have come from another producer: the consumers' done words order the two).  done[slot][c] is the
+    // number of the last tile consumer c has read from the slot, plus one.
+    auto wait_free = [&](int t, int slot) __attribute__((always_inline)) {
+        if (t < NSLOT) return;
+        const int need = t - NSLOT + 1;
+        const auto s0 = st.now();
+        for (;;) {
+            const int v = lane < NCONS ? lds_load_volatile(&done[slot * NCONS + lane]) : need;
+            if (__builtin_amdgcn_ballot_w64(v < need) == 0) break;
+            __builtin_amdgcn_s_sleep(1);
+        }
+        st.since(Stamps::PWAIT, s0);
+    };
+    auto publish = [&](const f32x4(&r)[NS], int t) __attribute__((always_inline)) {
+        const int slot = t % NSLOT;
+        wait_free(t, slot);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        f32x4* dst = ring_l + slot * (TILE_BYTES / 16);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) dst[s * 64] = r[s];
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        // same wave, in-order LDS queue: the flag lands after the tile
+        if (lane == 0) __hip_atomic_store(&ready[slot], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    // three register sets: the loads of tiles t + 4 and t + 8 are in flight while tile t is handed over
+    f32x4 rc[NS];
+    int t = p;
+    if (t < ntiles) load(ra, t);
+    if (t + NPROD < ntiles) load(rb, t + NPROD);
+    for (; t < ntiles; t += 3 * NPROD) {
+        if (t + 2 * NPROD < ntiles) load(rc, t + 2 * NPROD);
+        publish(ra, t);
+        if (t + NPROD < ntiles) {
+            if (t + 3 * NPROD < ntiles) load(ra, t + 3 * NPROD);
+            publish(rb, t + NPROD);
+        }
+        if (t + 2 * NPROD < ntiles) {
+            if (t + 4 * NPROD < ntiles) load(rb, t + 4 * NPROD);
+            publish(rc, t + 2 * NPROD);
+        }
+    }
+    // two empty tiles past the end: the consumers' loop runs one tile longer than the data (the selection of a
+    // tile happens under the MFMAs of the next one) and always prefetches "tile t + 1", with no last-tile case
+    for (int e = ntiles; e < ntiles + 2; ++e) {
+        if (ntiles > 0 && e % NPROD == p) {
+            const int slot = e % NSLOT;
+            wait_free(e, slot);
+            if (lane == 0) __hip_atomic_store(&ready[slot], e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    if constexpr (!SAMPLE) stamps_out_producer(st, lane, p);
+}
+
+// =====================================================================================================================
+// the end of a consumer's full pass: its 32 lists, compacted, to global memory
+// =====================================================================================================================
+template <int NS, int KS>
+__device__ __forceinline__ void write_final_lists(const PassCtx<NS, KS> cx, int& mycnt, int& nk, float& tau,
+                                                  int32_t* __restrict__ cand, float* __restrict__ cand_v,
+                                                  float* __restrict__ tau_out) {
+    using S = Bf16Shape<NS, KS>;
+    const int lane = cx.lane, wave = cx.wave, nrng = cx.nrng, out_chunk = cx.out_chunk, out_nchunks = cx.out_nchunks;
+    unsigned long long* const buf = cx.lds.lists;
+    for (int jj = 0; jj < 32; ++jj) compact_regs<KS, S::PLN>(buf, wave * 32 + jj, jj, lane, mycnt, nk, tau);
+    for (int jj = 0; jj < 32; ++jj) {
+        const int s = wave * 32 + jj;
+        const int qq = cx.qblock * S::NQ + s;
+        const int n = __builtin_amdgcn_readlane(nk, jj);
+        // what this range rejected was rejected against thresholds >= the final working threshold of its lane pair;
+        // kept entries at or above that threshold are as good as rejected (another range holds KS better ones), so
+        // they are dropped here and the refine kernel only sees the few that matter
+        const float w0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(tau), jj));
+        const float w1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(tau), jj + 32));
+        const float eff = w0 < w1 ? w0 : w1;
+        if (lane < KS) {
+            const unsigned long long key = buf[s * S::PITCH + lane];
+            const float val = __uint_as_float((uint32_t)(key >> 32));
+            const bool keep = lane < n && (val < eff || nrng == 1);
+            cand[((int64_t)qq * out_nchunks + out_chunk) * KS + lane] = keep ? (int32_t)(uint32_t)key : -1;
+            if (cand_v) cand_v[((int64_t)qq * out_nchunks + out_chunk) * KS + lane] = val;
+        }
+        if (lane == 0) tau_out[(int64_t)qq * out_nchunks + out_chunk] = eff;
+        if (nrng == 1) {  // a whole-reference item owns every list column of its queries: the others stay empty
+            for (int c = 1; c < out_nchunks; ++c) {
+                if (lane < KS) cand[((int64_t)qq * out_nchunks + out_chunk + c) * KS + lane] = -1;
+                if (lane == 0) tau_out[(int64_t)qq * out_nchunks + out_chunk + c] = __builtin_inff();
+            }
+        }
+    }
+}
+
+// =====================================================================================================================
+// the kernel; its body is the consumer waves' sweep
+// =====================================================================================================================
 // SAMPLE = true: threshold estimation only, entirely in registers and branch-free.  Each (tile, lane) contributes the
 // minimum of its 16 values as ONE candidate; a lane keeps the KS/2 smallest of its candidates in a sorted register
 // list (one min/max pair per entry and tile, issued in the gaps of the MFMA chain).  The two lanes of a query thus
@@ -203,23 +207,20 @@ __device__ unsigned long long bmx_dbg[48];
 // range benefits from what the others have already found and extra ranges cost no extra selection work.  Each
 // range's threshold is an upper bound of the KS-th nearest reference overall, hence so is their minimum; a stale
 // read only leaves the filter looser, never wrong.
-template <int NS, int KS, int NCONS, int NPROD, int PL, bool SAMPLE>
-__global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
+template <int NS, int KS, bool SAMPLE>
+__global__ __launch_bounds__((Bf16Shape<NS, KS>::NWAVES * 64)) void knn_topk_bf16(
     const uint16_t* __restrict__ Pq, const uint16_t* __restrict__ PrF, int first_begin, int range_len, int r_limit,
     int n_full, int nranges, int out_chunk0, int out_nchunks, uint32_t* __restrict__ tau_g, int32_t* __restrict__ cand,
     float* __restrict__ cand_v, float* __restrict__ tau_out) {
-    constexpr int CAP = KS + 2 * PL;
-    constexpr int PITCH = list_pitch(KS, PL);
-    constexpr int NQ = NCONS * 32;
-    constexpr int TILE_BYTES = NS * 1024;
-    constexpr int NSLOT = ring_slots(NS, KS, NCONS, PL);
-    static_assert(CAP <= 64, "one candidate per lane during compaction");
+    using S = Bf16Shape<NS, KS>;
+    constexpr int NCONS = S::NCONS, PL = S::PLN, PITCH = S::PITCH, NQ = S::NQ, TILE_BYTES = S::TILE_BYTES, NSLOT = S::NSLOT;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* ring = smem;                                                                        // [NSLOT][TILE_BYTES]
-    unsigned long long* buf = reinterpret_cast<unsigned long long*>(smem + NSLOT * TILE_BYTES);  // [NQ][CAP]
-    int* ready = reinterpret_cast<int*>(buf + NQ * PITCH);                                     // [NSLOT]
-    int* done = ready + NSLOT;                                                                // [NSLOT][NCONS]
+    const Bf16Lds<S> lds = Bf16Lds<S>::carve(smem);
+    char* const ring = lds.ring;
+    unsigned long long* const buf = lds.lists;
+    int* const ready = lds.ready;
+    int* const done = lds.done;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: branches on it are scalar
@@ -228,87 +229,12 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
     const int qblock = wi.qblock, rng = wi.rng, nrng = wi.nrng, r_begin = wi.r_begin, r_end = wi.r_end;
     const int ntiles = (r_end - r_begin) >> 5;
     const int out_chunk = out_chunk0 + rng;
-    if (tid < NSLOT * (1 + NCONS)) ready[tid] = 0;  // ready[] and done[] are contiguous
+    if (tid < Bf16Lds<S>::HANDOVER_WORDS) lds.handover()[tid] = 0;
     __syncthreads();
 
+    const PassCtx<NS, KS> cx{lds, lane, wave, qblock, nrng, r_begin, ntiles, out_chunk, out_nchunks};
     if (wave >= NCONS) {
-        // ------------------------------------------------------------------ producer
-        const int p = wave - NCONS;
-        f32x4 ra[NS], rb[NS];
-        const f32x4* src = reinterpret_cast<const f32x4*>(PrF) + ((int64_t)(r_begin >> 5) * NS) * 64 + lane;
-        f32x4* ring_l = reinterpret_cast<f32x4*>(ring) + lane;
-        auto load = [&](f32x4 (&r)[NS], int t) {
-#pragma unroll
-            for (int s = 0; s < NS; ++s) r[s] = src[((int64_t)t * NS + s) * 64];
-        };
-        // tile t goes to slot t % NSLOT once every consumer has read the tile staged there NSLOT tiles earlier (that
-        // tile may have come from another producer: the consumers' done words order the two).  done[slot][c] is the
-        // number of the last tile consumer c has read from the slot, plus one.
-#ifdef BMX_STAMPS
-        unsigned long long dbg_pw = 0, dbg_pt0 = STAMP();
-#endif
-        auto wait_free = [&](int t, int slot) {
-            if (t < NSLOT) return;
-            const int need = t - NSLOT + 1;
-#ifdef BMX_STAMPS
-            const unsigned long long s0 = STAMP();
-            for (;;) {
-                const int v = lane < NCONS ? lds_load_volatile(&done[slot * NCONS + lane]) : need;
-                if (__builtin_amdgcn_ballot_w64(v < need) == 0) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            dbg_pw += STAMP() - s0;
-            return;
-#endif
-            for (;;) {
-                const int v = lane < NCONS ? lds_load_volatile(&done[slot * NCONS + lane]) : need;
-                if (__builtin_amdgcn_ballot_w64(v < need) == 0) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-        };
-        auto publish = [&](const f32x4 (&r)[NS], int t) {
-            const int slot = t % NSLOT;
-            wait_free(t, slot);
-            __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            f32x4* dst = ring_l + slot * (TILE_BYTES / 16);
-#pragma unroll
-            for (int s = 0; s < NS; ++s) dst[s * 64] = r[s];
-            __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            // same wave, in-order LDS queue: the flag lands after the tile
-            if (lane == 0) __hip_atomic_store(&ready[slot], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        };
-        // three register sets: the loads of tiles t + 4 and t + 8 are in flight while tile t is handed over
-        f32x4 rc[NS];
-        int t = p;
-        if (t < ntiles) load(ra, t);
-        if (t + NPROD < ntiles) load(rb, t + NPROD);
-        for (; t < ntiles; t += 3 * NPROD) {
-            if (t + 2 * NPROD < ntiles) load(rc, t + 2 * NPROD);
-            publish(ra, t);
-            if (t + NPROD < ntiles) {
-                if (t + 3 * NPROD < ntiles) load(ra, t + 3 * NPROD);
-                publish(rb, t + NPROD);
-            }
-            if (t + 2 * NPROD < ntiles) {
-                if (t + 4 * NPROD < ntiles) load(rb, t + 4 * NPROD);
-                publish(rc, t + 2 * NPROD);
-            }
-        }
-        // two empty tiles past the end: the consumers' loop runs one tile longer than the data (the selection of a
-        // tile happens under the MFMAs of the next one) and always prefetches "tile t + 1", with no last-tile case
-        for (int e = ntiles; e < ntiles + 2; ++e) {
-            if (ntiles > 0 && e % NPROD == p) {
-                const int slot = e % NSLOT;
-                wait_free(e, slot);
-                if (lane == 0) __hip_atomic_store(&ready[slot], e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-#ifdef BMX_STAMPS
-        if (!SAMPLE && lane == 0) {
-            atomicAdd(&bmx_dbg[32 + p], dbg_pw);
-            atomicAdd(&bmx_dbg[36 + p], STAMP() - dbg_pt0);
-        }
-#endif
+        producer_role<NS, KS, SAMPLE>(cx, PrF);
         return;
     }
 
@@ -329,10 +255,8 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
 
     unsigned long long* pend = buf + qs * PITCH + KS + h * PL;
     int mycnt = 0;
-#ifdef BMX_STAMPS
-    unsigned long long dbg_spin = 0, dbg_flush = 0, dbg_nspin = 0, dbg_nflush = 0, dbg_ncomp = 0, dbg_evt = 0, dbg_grp = 0, dbg_evc = 0;
-    const unsigned long long dbg_t0 = STAMP();
-#endif
+    Stamps st;
+    st.begin();
 
     // Tile hand-over.  Tile t + 1 (the producers stage two empty tiles past the end, so there always is one) is read
     // into the fragment registers while tile t computes, each register right after the MFMA that consumed it.  Its
@@ -348,35 +272,24 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
     int seen = 0;
     int slot_n = 0;  // slot of the tile to read next
     int yield_tiles = 0;
-    constexpr int YIELD = BMX_YIELD_TILES;
-    auto spin_until_staged = [&](int tile) {
-#ifdef BMX_STAMPS
+    auto spin_until_staged = [&](int tile) __attribute__((always_inline)) {
         if (__builtin_amdgcn_readfirstlane(seen) < tile + 1) {
-            yield_tiles = YIELD;
-            const unsigned long long s0 = STAMP();
-            ++dbg_nspin;
-            while (seen < tile + 1) {
-                __builtin_amdgcn_s_sleep(1);
-                seen = lds_load_volatile(&ready[slot_n]);
-            }
-            dbg_spin += STAMP() - s0;
-        }
-#else
-        if (__builtin_amdgcn_readfirstlane(seen) < tile + 1) {
-            yield_tiles = YIELD;
+            yield_tiles = YIELD_TILES;
+            const auto s0 = st.now();
+            st.count(Stamps::NSPIN);
             do {
                 __builtin_amdgcn_s_sleep(1);
                 seen = lds_load_volatile(&ready[slot_n]);
             } while (seen < tile + 1);
+            st.since(Stamps::SPIN, s0);
         }
-#endif
     };
-    auto read_tile = [&](f32x4 (&a)[NS]) {
+    auto read_tile = [&](f32x4(&a)[NS]) __attribute__((always_inline)) {
         const f32x4* tp = reinterpret_cast<const f32x4*>(ring + slot_n * TILE_BYTES) + lane;
 #pragma unroll
         for (int s = 0; s < NS; ++s) a[s] = tp[s * 64];
     };
-    auto hand_back = [&](int tile) {
+    auto hand_back = [&](int tile) __attribute__((always_inline)) {
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
         if (lane == 0)
             __hip_atomic_store(&done[slot_n * NCONS + wave], tile + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -392,7 +305,7 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
     uint32_t best[SAMPLE ? KS / 2 : 1];
 #pragma unroll
     for (int i = 0; i < (SAMPLE ? KS / 2 : 1); ++i) best[i] = 0xFF800000u;  // image of +inf
-    auto step = [&](f32x16& cur, const f32x16& prev, const int t, const int phase) {
+    auto step = [&](f32x16& cur, const f32x16& prev, const int t) __attribute__((always_inline)) {
         // Each SIMD hosts consumers w and w + 4; instruction arbitration goes by priority, then age, so at equal
         // priority the younger half (w >= 4) loses every contested slot, falls behind, and the older half waits for
         // it at the ring (measured: 290 vs 50 cycles of ring wait per tile).  A consumer that had to wait for the
@@ -406,8 +319,6 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
         spin_until_staged(t + 1);
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        typedef __attribute__((address_space(3))) const char* lds_cptr;
-        typedef __attribute__((address_space(3))) const f32x4* lds_f4ptr;
         lds_cptr tbase = (lds_cptr)ring + (slot_n * TILE_BYTES + lane * 16);
         asm volatile("" : "+v"(tbase));     // the address is formed here, ...
         __builtin_amdgcn_sched_barrier(0);  // ... outside the interleaved block below
@@ -456,19 +367,15 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
 
         const int r0 = r_begin + ((t - 1) << 5);  // the tile whose products are in `prev`
         if ((gmask[0] | gmask[1] | gmask[2] | gmask[3]) == 0) return;
-#ifdef BMX_STAMPS
-        ++dbg_evt;
-        const unsigned long long dbg_e0 = STAMP();
-#endif
-        auto flush_full = [&]() {
+        st.count(Stamps::EVT);
+        const auto e0 = st.now();
+        auto flush_full = [&]() __attribute__((always_inline)) {
             unsigned long long fm = __builtin_amdgcn_ballot_w64(mycnt > PL - 4);  // keep 4 slots free
             if (fm) {
-#ifdef BMX_STAMPS
-                const unsigned long long s0 = STAMP();
-                ++dbg_nflush;
-                dbg_ncomp += __builtin_popcountll((fm | (fm >> 32)) & 0xFFFFFFFFull);
-#endif
+                const auto s0 = st.now();
+                st.count(Stamps::NFLUSH);
                 fm = (fm | (fm >> 32)) & 0xFFFFFFFFull;
+                st.add(Stamps::NCOMP, (unsigned long long)__builtin_popcountll(fm));
                 while (fm) {
                     const int jj = __builtin_ctzll(fm);
                     fm &= fm - 1;
@@ -479,18 +386,14 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
                     // the periodic refresh above)
                     if (shared_tau && h == 0) atomicMin(&tau_g[q], f32_orderable(tau));
                 }
-#ifdef BMX_STAMPS
-                dbg_flush += STAMP() - s0;
-#endif
+                st.since(Stamps::COMP, s0);
             }
         };
         {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (gmask[u] == 0) continue;
-#ifdef BMX_STAMPS
-                ++dbg_grp;
-#endif
+                st.count(Stamps::GRP);
                 // a pending list keeps 4 free slots at this point, so the group's four values are appended in straight
                 // line code: a lane whose value does not pass writes it to the list's last slot instead, which stays
                 // unused as long as anything fails (at most 3 real entries land in the 4 free slots then)
@@ -507,9 +410,7 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
                 flush_full();
             }
         }
-#ifdef BMX_STAMPS
-        dbg_evc += STAMP() - dbg_e0;
-#endif
+        st.since(Stamps::EVC, e0);
     };
 
     f32x16 accA, accB;
@@ -532,86 +433,36 @@ __global__ __launch_bounds__((NCONS + NPROD) * 64) void knn_topk_bf16(
                         tau_fetch = __hip_atomic_load(&tau_g[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
-            step(accA, accB, t2, 0);
-            if (t2 + 1 <= ntiles) step(accB, accA, t2 + 1, 1);
+            step(accA, accB, t2);
+            if (t2 + 1 <= ntiles) step(accB, accA, t2 + 1);
         }
     }
 
-#ifdef BMX_STAMPS
-    if (!SAMPLE && lane == 0) {
-        atomicAdd(&bmx_dbg[0], STAMP() - dbg_t0);
-        atomicAdd(&bmx_dbg[1], dbg_spin);
-        atomicAdd(&bmx_dbg[2], dbg_flush);
-        atomicAdd(&bmx_dbg[3], dbg_nspin);
-        atomicAdd(&bmx_dbg[4], dbg_nflush);
-        atomicAdd(&bmx_dbg[5], dbg_ncomp);
-        atomicAdd(&bmx_dbg[6], dbg_evt);
-        atomicAdd(&bmx_dbg[7], dbg_grp);
-        atomicAdd(&bmx_dbg[8], (unsigned long long)ntiles);
-        atomicAdd(&bmx_dbg[9], 1ull);
-        atomicAdd(&bmx_dbg[10], dbg_evc);
-        atomicAdd(&bmx_dbg[16 + wave], dbg_spin);
-        atomicAdd(&bmx_dbg[24 + wave], dbg_flush);
-    }
-#endif
     if constexpr (SAMPLE) {
         const uint32_t mine = best[KS / 2 - 1], other = __shfl_xor(mine, 32);
         if (h == 0) tau_g[q] = max(mine, other);
         return;
     }
-    for (int jj = 0; jj < 32; ++jj) compact_regs<KS, PL>(buf, wave * 32 + jj, jj, lane, mycnt, nk, tau);
-    for (int jj = 0; jj < 32; ++jj) {
-        const int s = wave * 32 + jj;
-        const int qq = qblock * NQ + s;
-        const int n = __builtin_amdgcn_readlane(nk, jj);
-        // what this range rejected was rejected against thresholds >= the final working threshold of its lane pair;
-        // kept entries at or above that threshold are as good as rejected (another range holds KS better ones), so
-        // they are dropped here and the refine kernel only sees the few that matter
-        const float w0 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(tau), jj));
-        const float w1 = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(tau), jj + 32));
-        const float eff = w0 < w1 ? w0 : w1;
-        if (lane < KS) {
-            const unsigned long long key = buf[s * PITCH + lane];
-            const float val = __uint_as_float((uint32_t)(key >> 32));
-            const bool keep = lane < n && (val < eff || nrng == 1);
-            cand[((int64_t)qq * out_nchunks + out_chunk) * KS + lane] = keep ? (int32_t)(uint32_t)key : -1;
-            if (cand_v) cand_v[((int64_t)qq * out_nchunks + out_chunk) * KS + lane] = val;
-        }
-        if (lane == 0) tau_out[(int64_t)qq * out_nchunks + out_chunk] = eff;
-        if (nrng == 1) {  // a whole-reference item owns every list column of its queries: the others stay empty
-            for (int c = 1; c < out_nchunks; ++c) {
-                if (lane < KS) cand[((int64_t)qq * out_nchunks + out_chunk + c) * KS + lane] = -1;
-                if (lane == 0) tau_out[(int64_t)qq * out_nchunks + out_chunk + c] = __builtin_inff();
-            }
-        }
-    }
+    stamps_out_consumer(st, lane, wave, ntiles);
+    write_final_lists(cx, mycnt, nk, tau, cand, cand_v, tau_out);
 }
 
 template <int NS, int KS>
 void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
-    constexpr RingShape SH = ring_shape(NS, KS);
-    constexpr int NCONS = SH.ncons, NPROD = SH.nprod, PLN = SH.pln;
-    constexpr size_t lds = (size_t)ring_slots(NS, KS, NCONS, PLN) * NS * 1024 +
-                           (size_t)NCONS * 32 * list_pitch(KS, PLN) * 8 + 512;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&knn_topk_bf16<NS, KS, NCONS, NPROD, PLN, false>), lds);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&knn_topk_bf16<NS, KS, NCONS, NPROD, PLN, true>), lds);
+    using S = Bf16Shape<NS, KS>;
+    constexpr size_t lds = S::lds_bytes;
+    const auto full = &knn_topk_bf16<NS, KS, false>, sample = &knn_topk_bf16<NS, KS, true>;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(full), lds);
+    ensure_dynamic_lds(reinterpret_cast<const void*>(sample), lds);
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
     if (ws.profile) {
         ev = ws.next_events(L.sample ? 0 : 2);
         BMX_HIP(hipEventRecord(ev.first, stream));
     }
     const int items = L.n_full + (L.nqb - L.n_full) * L.nranges;
-    if (L.sample)
-        hipLaunchKernelGGL((knn_topk_bf16<NS, KS, NCONS, NPROD, PLN, true>), dim3(items), dim3((NCONS + NPROD) * 64),
-                           lds, stream, L.pq, L.pr, L.first_begin, L.range_len, L.r_limit, L.n_full, L.nranges,
-                           L.out_chunk0, L.out_nchunks,
-                           L.tau_g, L.cand, L.cand_v, L.tau);
-    else
-        hipLaunchKernelGGL((knn_topk_bf16<NS, KS, NCONS, NPROD, PLN, false>), dim3(items), dim3((NCONS + NPROD) * 64),
-                           lds, stream, L.pq, L.pr, L.first_begin, L.range_len, L.r_limit, L.n_full, L.nranges,
-                           L.out_chunk0, L.out_nchunks,
-                           L.tau_g, L.cand, L.cand_v, L.tau);
+    const auto pass = L.sample ? sample : full;
+    hipLaunchKernelGGL(pass, dim3(items), dim3(S::NWAVES * 64), lds, stream, L.pq, L.pr, L.first_begin, L.range_len, L.r_limit,
+                       L.n_full, L.nranges, L.out_chunk0, L.out_nchunks, L.tau_g, L.cand, L.cand_v, L.tau);
     BMX_LAUNCH_CHECK();
     if (ws.profile) BMX_HIP(hipEventRecord(ev.second, stream));
 #ifdef BMX_STAMPS
@@ -623,11 +474,11 @@ void launch(hipStream_t stream, KnnWorkspace& ws, const PassLaunch& L) {
         fprintf(stderr, "[stamps] waves=%.0f tiles/wave=%.0f cyc/tile=%.0f spin/tile=%.0f flush/tile=%.0f nspin/tile=%.3f nflush/tile=%.3f ncomp/tile=%.3f evt/tile=%.3f grp/tile=%.3f cyc/flush=%.0f evpath/tile=%.0f\n",
                 w, nt / w, h[0] / nt, h[1] / nt, h[2] / nt, h[3] / nt, h[4] / nt, h[5] / nt, h[6] / nt, h[7] / nt, h[4] ? (double)h[2] / h[4] : 0.0, h[10] / nt);
         fprintf(stderr, "[stamps] spin/tile by consumer:");
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %.0f", h[16 + i] / (nt / 8));
+        for (int i = 0; i < S::NCONS; ++i) fprintf(stderr, " %.0f", h[16 + i] / (nt / S::NCONS));
         fprintf(stderr, "  flush/tile:");
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " %.0f", h[24 + i] / (nt / 8));
+        for (int i = 0; i < S::NCONS; ++i) fprintf(stderr, " %.0f", h[24 + i] / (nt / S::NCONS));
         fprintf(stderr, "  producer waiting fraction:");
-        for (int i = 0; i < 4; ++i) fprintf(stderr, " %.2f", h[36 + i] ? (double)h[32 + i] / h[36 + i] : 0.0);
+        for (int i = 0; i < S::NPROD; ++i) fprintf(stderr, " %.2f", h[36 + i] ? (double)h[32 + i] / h[36 + i] : 0.0);
         fprintf(stderr, "\n");
         unsigned long long z[48] = {0};
         BMX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(bmx_dbg), z, sizeof(z)));
@@ -645,26 +496,6 @@ int bf16_pick_ns(int d) {
 }
 
 int bf16_ncons(int NS, int KS) { return ring_shape(NS, KS).ncons; }
-
-__global__ void fold_max_slots(const unsigned long long* __restrict__ slots, unsigned long long* __restrict__ out) {
-    double m = __longlong_as_double((long long)slots[(size_t)threadIdx.x * 16]);
-    for (int o = 1; o < 64; o <<= 1) m = fmax(m, __shfl_xor(m, o));
-    if (threadIdx.x == 0) atomicMax(out, (unsigned long long)__double_as_longlong(m));
-}
-
-void bf16_prep(hipStream_t stream, const double* X, const int32_t* rows, int n, int n_pad, int d, int NS,
-               const double* mean, int is_query, uint16_t* P, double* n2, unsigned long long* maxbits,
-               unsigned long long* slots) {
-    const size_t lds = (size_t)32 * d * 4 + 128 + 16;
-    if (!is_query) BMX_HIP(hipMemsetAsync(slots, 0, 64 * 16 * sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(knn_prep_bf16, dim3(n_pad / 32), dim3(256), lds, stream, X, rows, n, n_pad, d, NS, mean, is_query,
-                       P, n2, slots);
-    BMX_LAUNCH_CHECK();
-    if (!is_query) {
-        hipLaunchKernelGGL(fold_max_slots, dim3(1), dim3(64), 0, stream, slots, maxbits);
-        BMX_LAUNCH_CHECK();
-    }
-}
 
 bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L) {
 #define BMX_CASE(N)                        \

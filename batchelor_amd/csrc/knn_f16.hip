@@ -10,7 +10,7 @@
 // with |v' - exact| <= 2^-9 (1 + 2^-12) |q'||r'| + f32 accumulation terms: 4 MFMAs per 32 x 32 tile at 50 PCs
 // (K = 64) against 10 for the split-bf16 pass (K = 160).  At 50 PCs on 100 000 reference cells the bound is about
 // 0.05 against a gap of 0.35 between the 20th and the 32nd neighbour, so with KS = 32 kept candidates practically
-// every query is certified.  (The prepared images: knn_f16_prep.hip.  The same tile as four 16 x 16 blocks of
+// every query is certified.  (The prepared images: knn_prep.hip.  The same tile as four 16 x 16 blocks of
 // v_mfma_f32_16x16x32_f16, the kernel's MS = 1: at knn_topk_f16 below; what follows describes MS = 0.)
 //
 // With the matrix work that cheap, what happens around it sets the pace, so a workgroup (one per CU) splits it over
@@ -658,7 +658,7 @@ __device__ __forceinline__ void consumer_epilogue(const PassCtx<NS, KS>& cx, Sta
 // (even NS), four 16 x 16 blocks per tile -- reference half a, query half b, NS / 2 MFMAs each: the same pipe time and as many
 // accumulator registers -- and a lane holds values of TWO queries, 16 b + (lane & 15), of each the references
 // 16 a + 4 (lane >> 4) + i of both a.  The prepared reference image comes in the fragment order of the shape
-// (knn_f16_prep.hip); ring, hand-over, queues, service waves and lists are the same for both.  knn_f16_shape.hpp
+// (knn_prep.hip); ring, hand-over, queues, service waves and lists are the same for both.  knn_f16_shape.hpp
 // (mfma_shape_for) has which shape runs where.
 template <int NS, int KS, int LCAP, bool SAMPLE, int MS>
 __global__ __launch_bounds__((F16Shape<NS, KS>::NWAVES * 64)) void knn_topk_f16(

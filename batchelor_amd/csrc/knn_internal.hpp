@@ -1,11 +1,12 @@
 // What the units of the exact kNN call of one another.  Included by knn.hip, knn_refine.hip, knn_exact.hip, knn_large_k.hip
-// and the two candidate tiers (knn_f16.hip, knn_f16_prep.hip, knn_bf16.hip) only: the rest of the library sees knn_device (bmx_common.hpp).
+// and the two candidate tiers (knn_f16.hip, knn_bf16.hip, knn_prep.hip) only: the rest of the library sees knn_device (bmx_common.hpp).
 //   knn.hip          candidate_tiers, candidate_pass, search_tiers (the tier cascade), knn_device, read_count
 //   knn_plan.hpp     the shape of a candidate pass, host only
 //   knn_f16.hip      tier 1: knn_topk_f16 (producer and service roles as functions, the consumer sweep in its body), launcher
 //   knn_f16_shape.hpp  ... the shape of its workgroup and its LDS layout (host + device, no HIP header), its tunables
-//   knn_f16_prep.hip ... its prep kernels
-//   knn_bf16.hip     tier 2: knn_topk_bf16 and its prep
+//   knn_bf16.hip     tier 2: knn_topk_bf16 (producer role and final lists as functions, the consumer sweep in its body), launcher
+//   knn_bf16_shape.hpp ... the shape of its workgroup and its LDS layout (host + device, no HIP header), its tunables
+//   knn_prep.hip     the prep kernels of both tiers: the steps of a tile once, a number format per tier
 //   knn_tier.hpp     what the two tiers share on the device: work-item decode, LDS word loads, stamps
 //   knn_refine.hip   the FP64 re-rank and certificate behind either tier
 //   knn_exact.hip    the bounded FP64 sweep, the full FP64 scan, exact_search
@@ -36,14 +37,14 @@ struct PassLaunch {
     const uint32_t* tau_seed = nullptr;  // fp16 tier, sample pass of a seeded search: tau_g = min(sampled, tau_seed)
     int shape = 0;          // fp16 tier: MFMA shape of the sweep (f16_pick_shape), the one pr was prepared for
 };
-// split-bf16 candidate pass (knn_bf16.hip)
+// split-bf16 candidate pass (knn_bf16.hip; bf16_prep: knn_prep.hip)
 int bf16_pick_ns(int d);         // MFMA k-steps (16 bf16 each) for 3 d + 3 columns; 0 = unsupported
 int bf16_ncons(int NS, int KS);  // consumer waves (32 queries each) per workgroup
 void bf16_prep(hipStream_t stream, const double* X, const int32_t* rows, int n, int n_pad, int d, int NS,
                const double* mean, int is_query, uint16_t* P, double* n2, unsigned long long* maxbits,
                unsigned long long* slots);  // slots: 64 x 16 words of scratch for the reference-norm maximum
 bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L);
-// fp16 candidate pass (knn_f16.hip; f16_prep_all: knn_f16_prep.hip)
+// fp16 candidate pass (knn_f16.hip; f16_prep_all: knn_prep.hip)
 int f16_pick_ns(int d, int KS);
 int f16_rows_per_slot(int NS, int KS);  // reference rows a ring slot of the fp16 tier holds (ranges are multiples of it)
 int f16_pick_shape(int NS, int KS);     // MFMA shape of the sweep: 0 = 32x32x16, 1 = 16x16x32 (table, or the "mfma_shape" hook)

@@ -1,8 +1,11 @@
-// Selection machinery shared by the MFMA top-k kernels (f32 and split-bf16 candidate passes).
+// What the candidate passes of the exact kNN (fp16 and split bf16), their prep kernels and knn_refine share: the orderable
+// image of an f32, the error bound of a pass, and the candidate lists of the split-bf16 pass.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "knn_bf16_shape.hpp"
 
 namespace bmx {
 namespace sel {
@@ -26,7 +29,7 @@ struct PassEps {
     int scaled;  // fp16 tier: coordinates times the power of two pass_scale(max |r|^2)
 };
 
-// power-of-two scale that puts the largest reference norm into (24, 48]; 1 for degenerate input (= f16_scale, knn_f16.hip)
+// power-of-two scale that puts the largest reference norm into (24, 48]; 1 for degenerate input
 __host__ __device__ __forceinline__ double pass_scale(double max_n2) {
     const double rm = sqrt(max_n2);
     if (!(rm > 1e-150) || !(rm < 1e150)) return 1.0;
@@ -88,38 +91,7 @@ __device__ __forceinline__ uint32_t pass_seed_tau(double seed_d2, double qn2, do
 // followed by two lane-private pending lists of PL entries each: a lane appends with a plain ds_write (no atomics, no
 // returned value to wait for).  When a pending list fills, one wave merges kept + both pending lists by rank-counting
 // over the unique 64-bit keys (orderable value << 32 | reference index), keeps the KS smallest and tightens tau.
-constexpr int PL = 12;
-// Row pitch of a query's list in 8-byte entries (register-state variant): one more than the capacity, so that the
-// lists of neighbouring queries start 2 banks apart and the appends of a wave's lanes do not pile up on one bank pair.
-__host__ __device__ constexpr int list_pitch(int KS, int PLN) { return KS + 2 * PLN + 1; }
-
-template <int KS>
-__device__ __forceinline__ void compact_slot(unsigned long long* buf, int* kcnt, float* tau_s, int slot, int jj,
-                                             int lane, int& mycnt) {
-    constexpr int CAP = KS + 2 * PL;
-    const int nk = kcnt[slot];
-    const int n0 = __builtin_amdgcn_readlane(mycnt, jj);
-    const int n1 = __builtin_amdgcn_readlane(mycnt, jj + 32);
-    const int n = nk + n0 + n1;
-    unsigned long long* b = buf + slot * CAP;
-    int src = lane;  // kept entries sit at [0, nk)
-    if (lane >= nk) src = lane < nk + n0 ? KS + (lane - nk) : KS + PL + (lane - nk - n0);
-    const unsigned long long key = lane < n ? b[src] : ~0ull;
-    const uint32_t klo = (uint32_t)key, khi = (uint32_t)(key >> 32);
-    int rank = 0;
-    for (int f = 0; f < n; ++f) {
-        const uint32_t flo = __builtin_amdgcn_readlane(klo, f);
-        const uint32_t fhi = __builtin_amdgcn_readlane(khi, f);
-        const unsigned long long fk = ((unsigned long long)fhi << 32) | flo;
-        rank += fk < key ? 1 : 0;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // every lane holds its key before slots are rewritten
-    if (lane < n && rank < KS) b[rank] = key;
-    if (n >= KS && lane < n && rank == KS - 1) tau_s[slot] = orderable_f32(khi);
-    if (lane == 0) kcnt[slot] = n < KS ? n : KS;
-    if (lane == jj || lane == jj + 32) mycnt = 0;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
+// (The row pitch of a query's list, list_pitch, is in knn_bf16_shape.hpp: the workgroup's shape needs it on the host.)
 
 // Register-state variant used by the split-bf16 ring kernel: the number of kept entries (nk) and the working
 // threshold (tau) of a query live in the registers of the two lanes that own it, so a compaction makes ONE LDS round

@@ -38,7 +38,7 @@ __device__ __forceinline__ int mbcnt64(unsigned long long m) {
 // st.now(); ... st.since(Stamps::COMP, t0).  In the product build the type has no state and every member is empty, so
 // nothing of it reaches the ISA; under BMX_STAMPS it holds the counters and now() reads the cycle counter.
 struct Stamps {
-    enum Counter { NCOMP, COMP, ROUNDS, DRAIN, NDRAIN, IDLE, SPIN, EVT, GRP, EVC, QWAIT, NCOUNTERS };
+    enum Counter { NCOMP, COMP, ROUNDS, DRAIN, NDRAIN, IDLE, SPIN, EVT, GRP, EVC, QWAIT, NSPIN, NFLUSH, PWAIT, NCOUNTERS };
 #ifdef BMX_STAMPS
     unsigned long long v[NCOUNTERS] = {};
     unsigned long long t0 = 0;
@@ -68,9 +68,6 @@ struct Stamps {
     __device__ __forceinline__ void count(Counter c) { add(c, 1ull); }
     __device__ __forceinline__ void since(Counter c, unsigned long long from) { add(c, now() - from); }
 };
-#ifdef BMX_STAMPS
-#define STAMP() __builtin_readcyclecounter()
-#endif
 
 }  // namespace
 }  // namespace bmx

@@ -3,12 +3,12 @@ tests/test_cpu_knn_scale_cases.py, which holds them to what the GPU tests assume
 
 What the cases pin, in batchelor_amd/csrc (the certificate `kth < tmin / s^2 + |q~|^2 - eps` of knn_refine.hip and everything
 that feeds it):
-  power-of-two scales   f16_scale / pass_scale (knn_f16_prep.hip, knn_select.hpp): s is a power of two, so the fp16 images of
+  power-of-two scales   pass_scale (knn_select.hpp): s is a power of two, so the fp16 images of
                         2^e X are those of X bit for bit, and every term of the certificate scales by exactly 2^(2e)
   general position      the same with mantissas that change; an offset that the centring (candidate_pass, knn.hip) must absorb
-  far queries           the NaN norm of a query whose -2 q' s leaves the fp16 range (prep_rows<1>)
+  far queries           the NaN norm of a query whose -2 q' s leaves the fp16 range (prep_rows_f16<1>)
   one far reference     eps_den: the ordinary cells' scaled coordinates are fp16 subnormals
-  degenerate norms      the scale = 1 branch of f16_scale (largest centred norm 0, below 1e-150, above 1e150)
+  degenerate norms      the scale = 1 branch of pass_scale (largest centred norm 0, below 1e-150, above 1e150)
   two clusters          the exponent window of the unscaled split-bf16 tier (pass_window, knn_select.hpp)"""
 import numpy as np
 

@@ -109,7 +109,7 @@ def test_equal_references_take_the_unit_scale_branch(factor):
     print(f"equal references x {factor:g}: largest centred norm {rm:g}")
     if factor == 1.0:
         assert rm == 0.0
-    assert not (rm > 1e-150) or not (rm < 1e150)  # f16_scale returns 1
+    assert not (rm > 1e-150) or not (rm < 1e150)  # pass_scale returns 1
     # every distance of a query is a tie: the rows are 1 .. k
     assert np.isfinite(X).all() and np.isfinite(Q).all()
 

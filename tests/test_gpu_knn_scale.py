@@ -82,7 +82,7 @@ def _scaled_rows(oracle, name, k, e):
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("k", [20, 36])
 def test_powers_of_two_tier1(oracle, nb, dev, k, shape):
-    """f16_scale's exponent, s2inv applied as 1 / s^2, the margins in scaled units: the rows of 2^e X are those of X, and
+    """pass_scale's exponent, s2inv applied as 1 / s^2, the margins in scaled units: the rows of 2^e X are those of X, and
     exactly as many queries leave the fp16 tier as at e = 0 (where test_gpu_knn_f16_mfma_shape.py's 5 % cap applies)."""
     dev("mfma_shape", shape)
     X, Q, rows = _scaled_rows(oracle, "base", k, 0)
@@ -200,7 +200,7 @@ def test_two_clusters_beyond_the_window_of_the_unscaled_tier(oracle, nb, dev, e,
 @pytest.mark.parametrize("k", [1, 20])
 def test_far_queries(oracle, nb, dev, k, shape):
     """A query whose -2 q' s leaves the fp16 range gets a NaN norm and fails the certificate whatever the pass collects
-    (prep_rows<1>, knn_f16_prep.hip); its neighbours in the wave, in the lane (16x16x32: queries j and j + 16) and in the
+    (prep_rows_f16<1>, knn_prep.hip); its neighbours in the wave, in the lane (16x16x32: queries j and j + 16) and in the
     workgroup must not notice.  d = 50 has two tiers, so "knn_tier2_queries" moves by exactly the number that left the fp16
     tier: at ratios beyond 32752 / 24 that is at least the moved queries."""
     dev("mfma_shape", shape)
@@ -249,7 +249,7 @@ def test_one_far_reference(oracle, nb, dev, row, e):
 # ---- case 7: degenerate norms ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("factor", C.DEGENERATE_FACTORS)
 def test_equal_references(oracle, nb, factor):
-    """500 references all equal to one row: the largest centred norm is 0 (at 1e170: beyond 1e150), f16_scale's scale = 1
+    """500 references all equal to one row: the largest centred norm is 0 (at 1e170: beyond 1e150), pass_scale's scale = 1
     branch.  Every distance of a query is a tie, and ties go to the lower row."""
     X, Q = C.equal_references(factor)
     for k in (1, 20):
