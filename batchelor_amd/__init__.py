@@ -4,7 +4,7 @@ Host side mirrors the reference's R functions (same names, arguments, 1-based co
 arithmetic runs in hand-written HIP kernels for gfx950 behind the C ABI of include/batchelor_mi355x.h.
 """
 from ._lib import BatchelorMI355XError, device_count  # noqa: F401
-from .neighbors import find_knn, query_knn  # noqa: F401
+from .neighbors import SnnGraph, find_knn, make_snn_graph, neighbors_to_snn_graph, query_knn  # noqa: F401
 from .reduced_mnn import MnnEngine, MnnResult, divideIntoBatches, reducedMNN  # noqa: F401
 from .natives import (adjust_shift_variance, find_mutual_nn, find_mutual_nns, smooth_gaussian_kernel)  # noqa: F401
 from .multi_batch_pca import (DevicePCA, DevicePCAGenes, DeviceSparsePCA, cosineNorm, multiBatchPCA,  # noqa: F401

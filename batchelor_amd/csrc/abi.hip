@@ -16,6 +16,8 @@
 #include <thread>
 #include <vector>
 
+#include <sys/mman.h>
+
 #include "bmx_common.hpp"
 #include "bmx_ops.hpp"
 #include "engine.hpp"
@@ -168,6 +170,18 @@ T* malloc_arr(size_t n) {
     return p;
 }
 
+// An edge array (hundreds of MB at 100 000 cells): aligned and advised for huge pages where the system grants them, so that
+// the first touch of fresh memory by the download is hundreds of page faults, not hundreds of thousands.  free() releases it.
+template <class T>
+T* malloc_edges(size_t n) {
+    const size_t bytes = n * sizeof(T), huge = (size_t)2 << 20;
+    if (bytes < 4 * huge) return malloc_arr<T>(n);
+    void* p = nullptr;
+    if (posix_memalign(&p, huge, bytes) != 0) throw std::bad_alloc();
+    (void)madvise(p, bytes, MADV_HUGEPAGE);
+    return static_cast<T*>(p);
+}
+
 template <class T>
 T* download_malloc(const T* dev, size_t n, hipStream_t s) {
     T* p = malloc_arr<T>(n);
@@ -264,6 +278,7 @@ int32_t bmx_dev_set(const char* name, int32_t value) {
     else if (n == "asv_chunk") k.asv_chunk = value;
     else if (n == "asv_strict") k.asv_strict = value;
     else if (n == "mfma_shape") k.mfma_shape = value;
+    else if (n == "snn_lds_candidates") k.snn_lds_candidates = value;
     else if (n == "reset") k = bmx::DevKnobs();
     else {
         g_last_error = "bmx_dev_set: unknown knob '" + n + "'";
@@ -302,6 +317,11 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = !g_prim ? 0 : (n == "knn_exact_fallbacks" ? g_prim->knn_ws_.exact_total : g_prim->knn_ws_.tier2_total);
         } else if (n == "knn_mfma_shape") {
             *value = g_prim ? g_prim->knn_ws_.last_mfma_shape : -1;  // of that engine's last fp16 full pass (-1: none yet)
+        } else if (n == "snn_spilled_cells" || n == "snn_graph_us") {
+            // of this thread's last SNN graph: cells that took more than one LDS window, the graph kernels' time by HIP events
+            int64_t st[2];
+            bmx::snn_stats_read(st);
+            *value = st[n == "snn_spilled_cells" ? 0 : 1];
         } else if (n == "asv_tally_reset") {
             bmx::asv_tally_read(t, true);
             *value = 0;
@@ -381,6 +401,100 @@ int32_t bmx_find_knn(const double* X, int32_t n, int32_t d, int32_t k, const int
         double* pd = dD.reserve((size_t)nq * k);
         bmx::knn_drop_self(s, pi1, pd1, pr, nq, k, pi, pd);
         knn_lists_to_caller(e, pi, pd, nq, k, index, distance);  // (waits for the stream: `rows` may go)
+    });
+}
+
+namespace {
+
+// what both SNN entry points refuse before any device is asked for
+void snn_check_args(int64_t n, int k, int type, int32_t** first, int32_t** second, double** weight, int64_t* m) {
+    if (!first || !second || !weight || !m) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: null output");
+    if (n < 0) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: negative dimension");
+    if (type < 0 || type > 2) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: 'type' must be 0 (rank), 1 (number) or 2 (jaccard)");
+    if (n > 1 && (k < 1 || k > std::min<int64_t>(n - 1, bmx::SNN_MAX_K)))
+        throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: 'k' must be between 1 and min(n - 1, 128)");
+    if (n > 1 && n * k > (int64_t)INT32_MAX - 1) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: n * k must be below 2^31");
+}
+
+// the graph of the lists pi [n][k] (device, 0-based) into malloc'ed arrays
+void snn_graph_to_caller(bmx::Engine& e, const int32_t* pi, int n, int k, int type, int32_t** first, int32_t** second,
+                         double** weight, int64_t* m) {
+    hipStream_t s = e.stream();
+    bmx::DevBuf<int32_t> dF, dS;
+    bmx::DevBuf<double> dW;
+    const int64_t edges = bmx::snn_graph_device(s, e.scan_ws_, pi, n, k, type, dF, dS, dW);
+    int32_t* f = nullptr;
+    int32_t* sc = nullptr;
+    double* w = nullptr;
+    try {
+        f = malloc_edges<int32_t>((size_t)edges);
+        sc = malloc_edges<int32_t>((size_t)edges);
+        w = malloc_edges<double>((size_t)edges);
+        if (edges) {
+            bmx::download_pageable(f, dF.p, (size_t)edges * sizeof(int32_t), s);
+            bmx::download_pageable(sc, dS.p, (size_t)edges * sizeof(int32_t), s);
+            bmx::download_pageable(w, dW.p, (size_t)edges * sizeof(double), s);
+            BMX_HIP(hipStreamSynchronize(s));
+        }
+    } catch (...) {
+        std::free(f);
+        std::free(sc);
+        std::free(w);
+        throw;
+    }
+    *first = f;
+    *second = sc;
+    *weight = w;
+    *m = edges;
+}
+
+void snn_empty_graph(int32_t** first, int32_t** second, double** weight, int64_t* m) {
+    *first = malloc_arr<int32_t>(0);
+    *second = malloc_arr<int32_t>(0);
+    *weight = malloc_arr<double>(0);
+    *m = 0;
+}
+
+}  // namespace
+
+int32_t bmx_snn_graph(const int32_t* index, int32_t n, int32_t k, int32_t type, int32_t** first, int32_t** second,
+                      double** weight, int64_t* m) {
+    return guarded([&] {
+        snn_check_args(n, k, type, first, second, weight, m);
+        if (n <= 1) return snn_empty_graph(first, second, weight, m);
+        if (!index) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: null 'index'");
+        bmx::Engine& e = prim(1);
+        bmx::CacheScope cache_scope(e.cache());
+        hipStream_t s = e.stream();
+        bmx::DevBuf<int32_t> dC, dI;
+        const int32_t* pc = upload(dC, index, (size_t)n * k, s);
+        int32_t* pi = dI.reserve((size_t)n * k);
+        bmx::snn_index_from_r_layout(s, pc, n, k, pi);
+        snn_graph_to_caller(e, pi, n, k, type, first, second, weight, m);  // (waits for the stream: `index` may go)
+    });
+}
+
+int32_t bmx_make_snn_graph(const double* X, int32_t n, int32_t d, int32_t k, int32_t type, int32_t** first, int32_t** second,
+                           double** weight, int64_t* m) {
+    return guarded([&] {
+        snn_check_args(n, k, type, first, second, weight, m);
+        if (d <= 0) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: 'X' has no columns");
+        if (n <= 1) return snn_empty_graph(first, second, weight, m);
+        if (!X) throw bmx::Error(BMX_ERR_ARG, "makeSNNGraph: null 'X'");
+        bmx::Engine& e = prim(d);
+        bmx::CacheScope cache_scope(e.cache());
+        hipStream_t s = e.stream();
+        bmx::DevBuf<double> t1, dX, dD1;
+        bmx::DevBuf<int32_t> dI1, dI;
+        const double* px = upload_rm(t1, dX, X, n, d, s);
+        // findKNN's search (k + 1, then the row itself out of its list); the lists stay where they are for the graph
+        int32_t* pi1 = dI1.reserve((size_t)n * (k + 1));
+        double* pd1 = dD1.reserve((size_t)n * (k + 1));
+        e.knn(px, nullptr, n, px, nullptr, n, k + 1, pi1, pd1);
+        int32_t* pi = dI.reserve((size_t)n * k);
+        bmx::knn_drop_self(s, pi1, nullptr, nullptr, n, k, pi, nullptr);
+        snn_graph_to_caller(e, pi, n, k, type, first, second, weight, m);
+        g_last_fallbacks = e.knn_ws_.last_exact;
     });
 }
 

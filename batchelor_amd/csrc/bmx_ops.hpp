@@ -162,6 +162,21 @@ void transpose_rm_to_cm(hipStream_t stream, const double* rm, int n, int d, doub
 void knn_drop_self(hipStream_t stream, const int32_t* idx_in, const double* dist_in, const int32_t* q_rows, int nq, int k,
                    int32_t* idx_out, double* dist_out);
 
+// ---- makeSNNGraph (snn_graph.hip) ---------------------------------------------------------------------
+// The shared-nearest-neighbour graph of idx [n][k] (0-based, each row's k nearest OTHER rows; device): its edges (a, b), a > b,
+// 1-based, ascending a then b, into first / second / weight (device, grown here); returns their number.  type 0 / 1 / 2: rank /
+// number / jaccard weights.  The caller has checked 1 <= k <= min(n - 1, SNN_MAX_K) and n * k < 2^31 (n <= 1: no edge, k is not
+// looked at); an entry outside [0, n), a row that lists itself or a row twice: Error(BMX_ERR_ARG).  Waits for the stream (twice:
+// the input's flag word, the number of edges).
+constexpr int SNN_MAX_K = 128;
+int64_t snn_graph_device(hipStream_t stream, ScanWorkspace& ws, const int32_t* idx, int n, int k, int type, DevBuf<int32_t>& first,
+                         DevBuf<int32_t>& second, DevBuf<double>& weight);
+// rm [n][k] 0-based = cm [n x k] column-major 1-based (values are not judged: snn_graph_device does that)
+void snn_index_from_r_layout(hipStream_t stream, const int32_t* cm, int n, int k, int32_t* rm);
+// of this thread's last snn_graph_device: {cells whose candidates took more than one LDS window, microseconds between the HIP
+// events around its kernels}
+void snn_stats_read(int64_t out[2]);
+
 // ---- upstream of the engine (prepca.hip): cosineNorm + PCA projection, x is genes x cells column-major ----------
 void cosine_l2_device(hipStream_t stream, const double* x, int G, int n, double* l2);
 // out[c] = l2 of cell c over the 0-based genes listed (genes0 null: over all G), c in [0, n); inverse: 1 / pmax(1e-8, l2)

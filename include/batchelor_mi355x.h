@@ -112,6 +112,21 @@ int32_t bmx_query_knn(const double* X, int32_t nx, const double* query, int32_t 
 int32_t bmx_find_knn(const double* X, int32_t n, int32_t d, int32_t k, const int32_t* subset, int32_t n_subset,
                      int32_t* index, double* distance);
 
+/* makeSNNGraph from an index: the shared-nearest-neighbour graph of index [n x k] (column-major, 1-based: each row's k nearest
+ * OTHER rows, distinct, never the row itself -- what bmx_find_knn returns).  With L(c) = (c, index[c,1..k]) at ranks 0..k, cells
+ * a > b share an edge exactly when L(a) and L(b) have a cell in common (S = their common cells).  type 0 "rank": weight
+ * max(k - r / 2, 1e-6), r = the smallest rank_a(s) + rank_b(s) over S; 1 "number": |S|; 2 "jaccard": |S| / (2 (k + 1) - |S|).
+ * *first > *second (1-based), ascending first then second, *weight, *m edges; the arrays are malloc'ed (bmx_free).  The same
+ * input gives the same bytes.  1 <= k <= min(n - 1, 128), n * k < 2^31; n = 0 or 1: no edge (k is not looked at).  BMX_ERR_ARG
+ * with a message for those, for an entry outside 1..n, a row that lists itself and a row that lists a row twice (found on
+ * the device). */
+int32_t bmx_snn_graph(const int32_t* index, int32_t n, int32_t k, int32_t type, int32_t** first, int32_t** second,
+                      double** weight, int64_t* m);
+/* makeSNNGraph(X, k): X as in bmx_find_knn goes to the device once, bmx_find_knn's search finds every row's k nearest other
+ * rows, and the graph of bmx_snn_graph is built from the lists where they lie in device memory. */
+int32_t bmx_make_snn_graph(const double* X, int32_t n, int32_t d, int32_t k, int32_t type, int32_t** first, int32_t** second,
+                           double** weight, int64_t* m);
+
 /* findMutualNN(data1, data2, k1, k2) -> first / second, 1-based, malloc'ed (bmx_free). */
 int32_t bmx_find_mutual_nn(const double* data1, int32_t n1, const double* data2, int32_t n2, int32_t d, int32_t k1,
                            int32_t k2, int32_t** first, int32_t** second, int64_t* npairs);
@@ -138,6 +153,8 @@ void bmx_set_force_exact_knn(int32_t on);
  * "asv_strict" (-1 = every adjust_shift_variance call is strict where its caller says so, the default; 1 = every call is
  * strict: times strict mode on a workload whose driver has no switch for it), "mfma_shape" (fp16 tier: the MFMA shape of the
  * candidate sweep, 0 = 32x32x16, 1 = 16x16x32 where the row width has it; -1 = the library's table, the default),
+ * "snn_lds_candidates" (SNN graph: candidates of a cell that one LDS window holds; 0 = 2048, the default; at least k + 1 and at
+ * most 4096 are used; cells with more take several windows and give the same edges),
  * "reset" (all back to their defaults).
  * Unknown name: BMX_ERR_ARG. */
 int32_t bmx_dev_set(const char* name, int32_t value);
@@ -154,7 +171,9 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * keeps in the LDS).  Of the searches of this thread's single-primitive entry points (bmx_query_knn, bmx_find_knn, bmx_find_mutual_nn ...),
  * added up since the thread's first: "knn_exact_fallbacks" (queries finished by the FP64 paths) and "knn_tier2_queries" (queries
  * the first candidate tier handed to the second) -- what bmx_engine_profile_detail reports of an engine; "knn_mfma_shape"
- * (the MFMA shape the last fp16 candidate pass of those searches ran with: 0 = 32x32x16, 1 = 16x16x32, -1 = none yet). */
+ * (the MFMA shape the last fp16 candidate pass of those searches ran with: 0 = 32x32x16, 1 = 16x16x32, -1 = none yet).
+ * Of this thread's last bmx_snn_graph / bmx_make_snn_graph: "snn_spilled_cells" (cells whose candidates took more than one LDS
+ * window), "snn_graph_us" (microseconds between HIP events around the graph's kernels, the search excluded). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
 /* "asv_modes" (after bmx_dev_set "asv_modes" = n): which way each of the first n cells of the LAST tiled adjust_shift_variance
  * call went -- 0 the histogram quantile (a well-conditioned cell), 1 re-run in the reference's order of operations, 2
