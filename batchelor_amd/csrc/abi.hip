@@ -278,6 +278,7 @@ int32_t bmx_dev_set(const char* name, int32_t value) {
     else if (n == "asv_chunk") k.asv_chunk = value;
     else if (n == "asv_strict") k.asv_strict = value;
     else if (n == "mfma_shape") k.mfma_shape = value;
+    else if (n == "ref_order") k.ref_order = value;
     else if (n == "snn_lds_candidates") k.snn_lds_candidates = value;
     else if (n == "reset") k = bmx::DevKnobs();
     else {
@@ -317,6 +318,11 @@ int32_t bmx_dev_get(const char* name, int64_t* value) {
             *value = !g_prim ? 0 : (n == "knn_exact_fallbacks" ? g_prim->knn_ws_.exact_total : g_prim->knn_ws_.tier2_total);
         } else if (n == "knn_mfma_shape") {
             *value = g_prim ? g_prim->knn_ws_.last_mfma_shape : -1;  // of that engine's last fp16 full pass (-1: none yet)
+        } else if (n == "knn_ordered_searches" || n == "knn_unordered_searches") {
+            // candidate passes of this process (engines and single primitives alike) whose reference image was in key order / was not
+            int64_t oc[2];
+            bmx::knn_order_counts(oc);
+            *value = oc[n == "knn_ordered_searches" ? 0 : 1];
         } else if (n == "snn_spilled_cells" || n == "snn_graph_us") {
             // of this thread's last SNN graph: cells that took more than one LDS window, the graph kernels' time by HIP events
             int64_t st[2];

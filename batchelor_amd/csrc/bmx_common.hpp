@@ -313,6 +313,12 @@ struct KnnWorkspace {
     DevBuf<uint32_t> tau_seed;     // [nq] seeded search: each query's seed threshold in the pass's units (orderable image)
     bool slots_clean = false;      // maxslots is zero (knn_refine leaves it so behind an fp16 search)
     DevBuf<unsigned long long> maxslots;  // 64 x 16 words: per-slot maxima of the reference norms (prep kernels)
+    // ordered references of an fp16 search (knn_order.hpp): the rows' keys, the sort's scratch, the image's two index arrays
+    DevBuf<float> ord_key;
+    DevBuf<uint32_t> ord_scratch;
+    DevBuf<int32_t> img_src, img_pos;
+    DevBuf<double> qcentre;        // [d] strided-sample mean of the queries, where the caller of knn_device gave no centre of them
+    bool qcentre_auto = false;     // set by knn_device around its cascade: an fp16 pass without a query centre may compute that mean
     // per candidate tier: [count + 1] compact list of the queries it could not certify (+ counter in word 0), their
     // k-th candidate distances, and the scratch of the sub-search the next tier runs on them
     DevBuf<int32_t> flagged_t[2], sub_rows[2], sub_idx[2];
@@ -426,9 +432,14 @@ struct KnnWorkspace {
 // certified by the first tier, +inf otherwise -- what lets the mutual-pair probe reject a candidate without reading the row.
 // centre (nullable, [d] device): a point near the middle of the reference rows (the prepared images are taken relative to
 // it: any vector is valid, a good one keeps the error bound tight); null: the mean of a strided sample is computed here.
+// qcentre (nullable, [d] device): a point near the middle of the QUERY rows; the fp16 tier sweeps the references nearest to
+// it first (knn_order.hpp: any vector is valid, the results do not depend on it); null: the mean of a strided sample of the
+// queries is computed here where the order is wanted.
 void knn_device(hipStream_t stream, KnnWorkspace& ws, const double* X, const int32_t* ref_rows, int nr,
                 const double* Q, const int32_t* q_rows, int d, int k, int32_t* idx_out, double* dist_out,
                 int q_begin, int q_end, const float* seed_d2 = nullptr, const double* centre = nullptr,
-                double* kth_out = nullptr);
+                double* kth_out = nullptr, const double* qcentre = nullptr);
+// searches (candidate passes) of this process that ran with ordered references, and that ran without: [ordered, unordered]
+void knn_order_counts(int64_t out[2]);
 
 }  // namespace bmx

@@ -214,7 +214,8 @@ void Engine::upload(int nbatches, int d, const double* const* data, const int32_
 }
 
 void Engine::knn(const double* X, const int32_t* ref_rows, int nr, const double* Q, const int32_t* q_rows, int nq,
-                 int k, int32_t* idx, double* dist, const float* seed_d2, const double* centre, double* kth, bool gather) {
+                 int k, int32_t* idx, double* dist, const float* seed_d2, const double* centre, double* kth, bool gather,
+                 const double* qcentre) {
     // query rows are split over ranks; the padded per-rank slices are contiguous, so the all-gather is in place
     int64_t b = 0, e = nq;
     bmx_shard_range_impl(nq, rank_, world_, &b, &e);
@@ -223,7 +224,7 @@ void Engine::knn(const double* X, const int32_t* ref_rows, int nr, const double*
     queued_work_s_ += 2e-10 * (double)nq * (double)nr * (double)d_ / 50.0;
     knn_ws_.wd_budget_s = wd_base_s_ > 0.0 ? wd_base_s_ + queued_work_s_ : 0.0;
     try {
-        knn_device(stream_, knn_ws_, X, ref_rows, nr, Q, q_rows, d_, k, idx, dist, (int)b, (int)e, seed_d2, centre, kth);
+        knn_device(stream_, knn_ws_, X, ref_rows, nr, Q, q_rows, d_, k, idx, dist, (int)b, (int)e, seed_d2, centre, kth, qcentre);
     } catch (const WatchdogTimeout&) {  // (the search's own waits go through knn_ws_.sync, not through wait())
         mark_dead();
         throw;
@@ -320,7 +321,8 @@ Engine::MnnOut Engine::find_mnn(const Node& left, const Node& right, int k, doub
     int32_t* idxRL = idxRL_.reserve((size_t)perR * o.k1);
     // 1. every right cell's neighbours in LEFT, with their distances
     double* distRL = distRL_.reserve((size_t)perR * o.k1);
-    knn(left.data.p, lrows, nL, right.data.p, rrows, nR, o.k1, idxRL, distRL, nullptr, mu_left);
+    // (the other node's mean as the centre of the queries: the fp16 tier sweeps the references nearest to it first)
+    knn(left.data.p, lrows, nL, right.data.p, rrows, nR, o.k1, idxRL, distRL, nullptr, mu_left, nullptr, true, mu_right);
     // 2. a pair needs its left cell in some right cell's list, so only those left cells are searched in RIGHT (with a
     //    growing merged reference most left cells are in nobody's list).  The result is the same set of pairs.
     const size_t stamp_cap = stampL_.cap;
@@ -357,7 +359,8 @@ Engine::MnnOut Engine::find_mnn(const Node& left, const Node& right, int k, doub
     const int64_t perL = bmx_shard_rows_per_rank(nsel, world_) * (int64_t)world_;
     int32_t* idxLR = idxLR_.reserve((size_t)std::max<int64_t>(1, perL) * o.k2);
     double* kthL = kthL_.reserve((size_t)std::max<int64_t>(1, perL));
-    knn(right.data.p, rrows, nR, left.data.p, qsel, nsel, o.k2, idxLR, nullptr, seed, mu_right, kthL);
+    // (the mean of the whole left node stands for the selected cells: the order is a heuristic, it only has to be cheap)
+    knn(right.data.p, rrows, nR, left.data.p, qsel, nsel, o.k2, idxLR, nullptr, seed, mu_right, kthL, true, mu_left);
     int32_t* cntL = o.k2 > 64 ? cntL_.reserve(std::max(1, nsel)) : nullptr;
     int32_t* offL = offL_.reserve((size_t)nsel + 1);
     int32_t* partR = partR_.reserve((size_t)nR * o.k1);

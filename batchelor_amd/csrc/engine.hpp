@@ -108,7 +108,7 @@ class Engine {
     // single primitives (also used by the host-pointer parity entry points)
     void knn(const double* X, const int32_t* ref_rows, int nr, const double* Q, const int32_t* q_rows, int nq, int k,
              int32_t* idx, double* dist, const float* seed_d2 = nullptr, const double* centre = nullptr,
-             double* kth = nullptr, bool gather = true);
+             double* kth = nullptr, bool gather = true, const double* qcentre = nullptr);
     struct MnnOut {
         int64_t P = 0;
         int U = 0;

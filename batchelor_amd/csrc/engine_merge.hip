@@ -360,7 +360,8 @@ void Engine::merge_correct(MergeCtx& c) {
     // (testing hook "exchange_always": a single rank with a transport takes this way too, an all-gather of one)
     const bool rows_sharded = !p.var_adj && transport_in_play();
     c.sec.reset();
-    knn(right.data.p, srows, mo.U, right.data.p, nullptr, right.n, safe_k, idxT, distT, nullptr, c.mu_r, nullptr, !rows_sharded);
+    knn(right.data.p, srows, mo.U, right.data.p, nullptr, right.n, safe_k, idxT, distT, nullptr, c.mu_r, nullptr, !rows_sharded,
+        c.mu_r);
     c.sec = std::make_unique<Section>(this);  // streaming section 3: tricube apply, rbind
     if (rows_sharded)
         apply_rows_sharded(c, safe_k);

@@ -38,7 +38,8 @@ struct DevKnobs {
     int asv_chunk = 0;        // wide form: at most this many cells a chunk (0: as many as 1 GiB of scratch holds); the strict pass's chunks likewise
     int asv_strict = -1;      // adjust_shift_variance: 1 = every call is strict (var_adj_strict), -1: as the call says
     int mfma_shape = -1;      // fp16 tier: MFMA shape of the sweep, 0 = 32x32x16, 1 = 16x16x32 where it exists (-1: the table's)
-    int snn_lds_candidates = 0;  // SNN graph: candidates of a cell one LDS window holds (0: default 2048; at least k + 1, at most 4096)
+    int ref_order = -1;       // fp16 tier: reference image in key order (knn_order.hpp): -1 the default rule (knn.hip), 0 never, 1 wherever it is possible
+    int snn_lds_candidates = 0; // SNN graph: candidates of a cell one LDS window holds (0: default 2048; at least k + 1, at most 4096)
 };
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -34,6 +34,8 @@ namespace {
 
 using namespace sel;
 
+std::atomic<int64_t> g_order_counts[2];  // candidate passes of the process with ordered references, without
+
 // ---------------------------------------------------------------------------------------------------
 // column sums over a row list (two deterministic stages)
 // ---------------------------------------------------------------------------------------------------
@@ -130,6 +132,19 @@ __global__ void tau_apply_kernel(const uint32_t* __restrict__ rec, int nq, uint3
     if (q < nq) tau_g[q] = min(tau_g[q], rec[q]);
 }
 
+// out[d] = the mean of a strided sample of at most 16k of the rows (X, rows)[0, n)
+void strided_mean(hipStream_t stream, KnnWorkspace& ws, const double* X, const int32_t* rows, int n, int d, double* out) {
+    const int cstride = std::max(1, n / 16384);
+    const int ncs = cdiv(n, cstride);
+    const int rpb = 256;
+    const int nb = cdiv(ncs, rpb);
+    double* red = ws.red.reserve((size_t)nb * d);
+    hipLaunchKernelGGL(colsum_partial, dim3(nb), dim3(256), 0, stream, X, rows, ncs, d, rpb, cstride, red);
+    BMX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(colsum_final, dim3(cdiv(d, 64)), dim3(64), 0, stream, red, nb, d, 1.0 / ncs, out);
+    BMX_LAUNCH_CHECK();
+}
+
 // the error constants of a tier's pass (knn_select.hpp: pass_eps)
 PassEps tier_pass_eps(const Tier& T, int d) {
     PassEps pe;
@@ -151,6 +166,11 @@ PassEps tier_pass_eps(const Tier& T, int d) {
 
 }  // namespace
 
+void knn_order_counts(int64_t out[2]) {
+    out[0] = g_order_counts[0].load();
+    out[1] = g_order_counts[1].load();
+}
+
 int candidate_tiers(int d, int k, int nr, Tier out[2]) {
     const int only = dev_knobs().knn_tier;  // testing hook: 1 / 2 = that tier only, 3 = exact scan only
     int n = 0;
@@ -169,13 +189,27 @@ namespace {
 // are listed in `flagged` (count in flagged[0]) with their k-th candidate distance in flag_bound.
 void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const double* X, const int32_t* ref_rows, int nr,
                     const double* Qs, const int32_t* qrs, int nq, int d, int k, int32_t* io, double* dout,
-                    int32_t* flagged, double* flag_bound, const float* seed_d2, const double* centre, double* kth_out) {
+                    int32_t* flagged, double* flag_bound, const float* seed_d2, const double* centre, double* kth_out,
+                    const double* qcentre) {
     const int NS = T.NS, KS = T.KS;
     ws.last_variant = T.id == 1 ? 3 : 2;
     // 1. the plan.  Queries per workgroup: 8 consumer waves of 32 in the fp16 kernel; 8 or 4 (long rows, long lists) in the
     // bf16 kernel.  (The fp16 ring hands two or four tiles over at a time; a bf16 range is a multiple of 32 rows.)
-    const PassPlan plan = plan_candidate_pass(T.id, NS, KS, T.id == 1 ? 256 : 32 * bf16_ncons(NS, KS),
-                                              T.id == 1 ? f16_rows_per_slot(NS, KS) : 32, nq, nr, seed_d2 != nullptr, dev_knobs());
+    const int unit = T.id == 1 ? 256 : 32 * bf16_ncons(NS, KS), rows_per_slot = T.id == 1 ? f16_rows_per_slot(NS, KS) : 32;
+    PassPlan plan = plan_candidate_pass(T.id, NS, KS, unit, rows_per_slot, nq, nr, seed_d2 != nullptr, dev_knobs());
+    // Ordered references (knn_order.hpp; testing hook "ref_order": 0 never, 1 wherever it is possible): the fp16 tier, with a
+    // centre of the queries, where the search has a threshold sample -- the sample is what the order serves first
+    const int ord_knob = dev_knobs().ref_order;
+    // (the one statement of the rule.  Without a centre from the caller, knn_device allows the mean of a strided sample of at
+    // most 16k of the queries, as for the references' centre: two small launches, made only where the order is used)
+    const bool ordered = T.id == 1 && (qcentre || ws.qcentre_auto) && ord_knob != 0 && (ord_knob == 1 || plan.S > 0);
+    if (ordered && !qcentre) {
+        double* qc = ws.qcentre.reserve(d);
+        strided_mean(stream, ws, Qs, qrs, nq, d, qc);
+        qcentre = qc;
+    }
+    if (ordered) plan = plan_candidate_pass(T.id, NS, KS, unit, rows_per_slot, nq, nr, seed_d2 != nullptr, dev_knobs(), true);
+    ++g_order_counts[ordered ? 0 : 1];
     const int nq_pad = plan.nq_pad, nqb = plan.nqb, S = plan.S, C = plan.C, chunk_len = plan.chunk_len, nr_pad = plan.nr_pad;
     const int nchunks = C;
     if (debug_prints())
@@ -200,15 +234,7 @@ void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const d
     // near the mean keeps it tight -- the mean of a strided sample of <= 16k rows costs next to nothing
     // (the merge engine already holds the column mean of the reference's node and hands it in: nothing to compute)
     if (!centre) {
-        const int cstride = std::max(1, nr / 16384);
-        const int ncs = cdiv(nr, cstride);
-        const int rpb = 256;
-        const int nb = cdiv(ncs, rpb);
-        double* red = ws.red.reserve((size_t)nb * d);
-        hipLaunchKernelGGL(colsum_partial, dim3(nb), dim3(256), 0, stream, X, ref_rows, ncs, d, rpb, cstride, red);
-        BMX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(colsum_final, dim3(cdiv(d, 64)), dim3(64), 0, stream, red, nb, d, 1.0 / ncs, mean);
-        BMX_LAUNCH_CHECK();
+        strided_mean(stream, ws, X, ref_rows, nr, d, mean);
         centre = mean;
     }
     const PassEps pe = tier_pass_eps(T, d);
@@ -221,6 +247,7 @@ void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const d
     };
     bool ok = true;
     unsigned long long* zero_slots = nullptr;
+    const int32_t* img_pos = nullptr;  // ordered references: the pass lists image rows, the re-rank turns them into positions
     if (T.id == 1) {
         // fp16 tier: references (norms, then image) and queries (image, norm, margin, seed threshold) in TWO launches; the
         // slot maxima are folded by the second one, which also resets the flagged-query counter (knn_f16.hip)
@@ -229,9 +256,14 @@ void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const d
         uint32_t* tau_seed = seed_d2 ? ws.tau_seed.reserve(nq_pad) : nullptr;
         // without a sample pass the thresholds start at the seed (or at +inf): prep writes them
         L.shape = f16_pick_shape(NS, KS);  // (the reference image is laid out for the MFMA shape of the sweep)
+        RefOrder ord{};
+        if (ordered)
+            ord = RefOrder{qcentre, ws.ord_key.reserve(nr), ws.ord_scratch.reserve(ref_order_scratch_words(nr)),
+                           ws.img_src.reserve(nr), ws.img_pos.reserve(nr)};
+        img_pos = ord.img_pos;
         f16_prep_all(stream, X, ref_rows, nr, nr_pad, Qs, qrs, nq, nq_pad, d, NS, L.shape, centre, reinterpret_cast<uint16_t*>(pr),
                      reinterpret_cast<uint16_t*>(pq), rn2, qn2, maxbits, slots, flagged, margin, pe, seed_d2, tau_seed,
-                     S == 0 || plan.CS > 1 ? tau_g : nullptr);
+                     S == 0 || plan.CS > 1 ? tau_g : nullptr, ordered ? &ord : nullptr);
         if (margin) {
             L.margin = margin;
             L.k = k;
@@ -288,7 +320,7 @@ void candidate_pass(hipStream_t stream, KnnWorkspace& ws, const Tier& T, const d
     }
     if (replay) ++ws.replay_idx;
     if (!ok) throw Error(BMX_ERR_ARG, "kNN: unsupported padded dimension");
-    refine_launch(stream, ws, plan, KS, pe, PassLists{cand, cand_v, tau, qn2, maxbits}, X, ref_rows, Qs, qrs, nq, d, k, seed_d2,
+    refine_launch(stream, ws, plan, KS, pe, PassLists{cand, cand_v, tau, qn2, maxbits, img_pos}, X, ref_rows, Qs, qrs, nq, d, k, seed_d2,
                   io, dout, flagged, flag_bound, zero_slots, kth_out);
     if (zero_slots) ws.slots_clean = true;
     if (debug_prints()) {
@@ -344,7 +376,7 @@ int read_count(hipStream_t stream, KnnWorkspace& ws, const int32_t* dev) {
 
 void search_tiers(hipStream_t stream, KnnWorkspace& ws, const Tier* tiers, int ntiers, int t, const double* X,
                   const int32_t* ref_rows, int nr, const double* Qs, const int32_t* qrs, int nq, int d, int k, int32_t* io,
-                  double* dout, const float* seed_d2, const double* centre, double* kth_out) {
+                  double* dout, const float* seed_d2, const double* centre, double* kth_out, const double* qcentre) {
     if (t >= ntiers) {
         exact_search(stream, ws, X, ref_rows, nr, Qs, qrs, d, k, io, dout, nullptr, nullptr, nq);
         return;
@@ -355,7 +387,7 @@ void search_tiers(hipStream_t stream, KnnWorkspace& ws, const Tier* tiers, int n
     // (kth_out: the first tier's re-rank writes it for the rows it certifies; a row any later tier or the exact sweep rewrites
     // keeps +inf there, which only costs the intersection's probe a row read)
     candidate_pass(stream, ws, tiers[t], X, ref_rows, nr, Qs, qrs, nq, d, k, io, dout, flagged, bound, seed_d2, centre,
-                   t == 0 ? kth_out : nullptr);
+                   t == 0 ? kth_out : nullptr, qcentre);
     if (ws.optimistic && t == 0) {
         // Optimistic run (the merge engine): no read-back inside a search.  Practically every query is certified by the
         // first tier (config 3: 1-6 of 3 million per step are not), so the bounded FP64 sweep for the few that are not is
@@ -390,7 +422,8 @@ void search_tiers(hipStream_t stream, KnnWorkspace& ws, const Tier* tiers, int n
 }
 
 void knn_device(hipStream_t stream, KnnWorkspace& ws, const double* X, const int32_t* ref_rows, int nr,
-                const double* Q, const int32_t* q_rows, int d, int k, int32_t* idx_out, double* dist_out, int q_begin, int q_end, const float* seed_d2, const double* centre, double* kth_out) {
+                const double* Q, const int32_t* q_rows, int d, int k, int32_t* idx_out, double* dist_out, int q_begin, int q_end, const float* seed_d2, const double* centre, double* kth_out,
+                const double* qcentre) {
     const int nq = q_end - q_begin;
     if (nq <= 0 || k <= 0) return;
     if (k > nr) throw Error(BMX_ERR_ARG, "kNN: k exceeds the number of reference cells");
@@ -420,8 +453,15 @@ void knn_device(hipStream_t stream, KnnWorkspace& ws, const double* X, const int
         ws.exact_total += ws.last_exact;
         return;
     }
+    // (a caller without a centre of the queries: the fp16 pass that wants the order takes the strided-sample mean of its
+    // queries itself -- candidate_pass has the one statement of the rule; the partitions of the large-k search above do not)
+    struct AutoCentre {
+        KnnWorkspace& w;
+        explicit AutoCentre(KnnWorkspace& ws_) : w(ws_) { w.qcentre_auto = true; }
+        ~AutoCentre() { w.qcentre_auto = false; }
+    } auto_centre(ws);
     search_tiers(stream, ws, tiers, ntiers, 0, X, ref_rows, nr, Qs, qrs, nq, d, k, io, dout,
-                 seed_d2 ? seed_d2 + q_begin : nullptr, centre, kth_out ? kth_out + q_begin : nullptr);
+                 seed_d2 ? seed_d2 + q_begin : nullptr, centre, kth_out ? kth_out + q_begin : nullptr, qcentre);
     if (ntiers > 0) ws.exact_total += ws.last_exact;
     if (ntiers > 0) ws.tier2_total += ws.last_flagged_tier[0] * (ntiers > 1 ? 1 : 0);
 }

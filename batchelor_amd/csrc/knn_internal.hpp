@@ -7,6 +7,7 @@
 //   knn_bf16.hip     tier 2: knn_topk_bf16 (producer role and final lists as functions, the consumer sweep in its body), launcher
 //   knn_bf16_shape.hpp ... the shape of its workgroup and its LDS layout (host + device, no HIP header), its tunables
 //   knn_prep.hip     the prep kernels of both tiers: the steps of a tile once, a number format per tier
+//   knn_order.hip    tier 1, ordered references: the image's two index arrays from the rows' keys (knn_order.hpp: the pure part)
 //   knn_tier.hpp     what the two tiers share on the device: work-item decode, LDS word loads, stamps
 //   knn_refine.hip   the FP64 re-rank and certificate behind either tier
 //   knn_exact.hip    the bounded FP64 sweep, the full FP64 scan, exact_search
@@ -48,10 +49,23 @@ bool bf16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const Pas
 int f16_pick_ns(int d, int KS);
 int f16_rows_per_slot(int NS, int KS);  // reference rows a ring slot of the fp16 tier holds (ranges are multiples of it)
 int f16_pick_shape(int NS, int KS);     // MFMA shape of the sweep: 0 = 32x32x16, 1 = 16x16x32 (table, or the "mfma_shape" hook)
+// ordered references of one search (knn_order.hpp): what goes in, the scratch, the two index arrays that come out
+struct RefOrder {
+    const double* qcentre;  // [d] a point near the middle of the queries
+    float* key;             // [nr] |r - qcentre|^2 per reference position (knn_prep_f16_norms)
+    uint32_t* scratch;      // [ref_order_scratch_words(nr)]
+    int32_t* img_src;       // [nr] row of X behind image row i
+    int32_t* img_pos;       // [nr] reference position behind image row i
+};
+size_t ref_order_scratch_words(int nr);
+// img_src / img_pos from the keys and their range (second word of the prep kernels' slots): knn_order.hip
+void ref_order_build(hipStream_t stream, const float* key, int nr, const int32_t* ref_rows, const unsigned long long* slots,
+                     uint32_t* scratch, int32_t* img_src, int32_t* img_pos);
 void f16_prep_all(hipStream_t stream, const double* X, const int32_t* rrows, int nr, int nr_pad, const double* Q,
                   const int32_t* qrows, int nq, int nq_pad, int d, int NS, int shape, const double* mean, uint16_t* Pr, uint16_t* Pq,
                   double* rn2, double* qn2, unsigned long long* maxbits, unsigned long long* slots, int32_t* flagged0,
-                  float* margin, const sel::PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init);
+                  float* margin, const sel::PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init,
+                  const RefOrder* ord = nullptr);
 bool f16_launch(hipStream_t stream, KnnWorkspace& ws, int NS, int KS, const PassLaunch& L);
 void f16_sample_merge(hipStream_t stream, const float* lists, int nranges, int KS, int nq, int k, const float* margin,
                       uint32_t* tau_g);
@@ -66,18 +80,20 @@ int candidate_tiers(int d, int k, int nr, Tier out[2]);
 // queries (Qs, qrs)[0, nq) through the tiers tiers[t ...], then the exact paths
 void search_tiers(hipStream_t stream, KnnWorkspace& ws, const Tier* tiers, int ntiers, int t, const double* X,
                   const int32_t* ref_rows, int nr, const double* Qs, const int32_t* qrs, int nq, int d, int k, int32_t* io,
-                  double* dout, const float* seed_d2 = nullptr, const double* centre = nullptr, double* kth_out = nullptr);
+                  double* dout, const float* seed_d2 = nullptr, const double* centre = nullptr, double* kth_out = nullptr,
+                  const double* qcentre = nullptr);
 // one device word to the host (a count that decides what is launched next)
 int read_count(hipStream_t stream, KnnWorkspace& ws, const int32_t* dev);
 
 // ---- knn_refine.hip ------------------------------------------------------------------------------------------------------
 // what a candidate pass left on the device for its re-rank
 struct PassLists {
-    const int32_t* cand;   // [nq_pad][C * KS] candidate positions, -1 = empty
+    const int32_t* cand;   // [nq_pad][C * KS] candidate positions (image rows), -1 = empty
     const float* cand_v;   // their approximate values
     const float* tau;      // [nq_pad][C] final thresholds
     const double* qn2;     // squared norms of the centred queries
     const unsigned long long* maxbits;  // largest squared norm of the centred references (bit pattern)
+    const int32_t* img_pos = nullptr;   // ordered references: cand holds image rows, img_pos[row] is the position (null: cand holds positions)
 };
 // FP64 re-rank and certificate of the queries (Qs, qrs)[0, nq): certified rows of io / dout are final; the others are listed
 // in `flagged` with their k-th candidate distance in flag_bound.  zero_slots (nullable): left zeroed for the next search.

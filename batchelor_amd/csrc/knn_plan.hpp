@@ -16,6 +16,10 @@ constexpr int MAX_CHUNKS = 8;  // reference ranges a query's lists can hold: a p
 #define BMX_SEEDED_SAMPLE 4096
 #endif
 
+#ifndef BMX_ORDERED_SAMPLE
+#define BMX_ORDERED_SAMPLE 8192
+#endif
+
 struct PassPlan {
     int unit;              // queries per workgroup
     int nq_pad, nqb;       // queries padded to whole workgroups; query blocks
@@ -28,8 +32,10 @@ struct PassPlan {
 
 // tier_id: 1 = fp16 single product, 2 = split bf16.  rows_per_slot: what a range is a multiple of (the fp16 ring hands two
 // or four tiles over at a time: f16_rows_per_slot; 32 for the bf16 tier).
+// ordered: the reference image is in key order (knn_order.hpp) -- the sample then consists of the rows nearest the queries'
+// centre, and fewer of them do (BMX_ORDERED_SAMPLE: MEASUREMENTS.md has the series per size).
 inline PassPlan plan_candidate_pass(int tier_id, int NS, int KS, int unit, int rows_per_slot, int nq, int nr, bool seeded,
-                                    const DevKnobs& knobs) {
+                                    const DevKnobs& knobs, bool ordered = false) {
     PassPlan P{};
     P.unit = unit;
     P.nq_pad = (int)round_up(nq, unit);
@@ -49,6 +55,7 @@ inline PassPlan plan_candidate_pass(int tier_id, int NS, int KS, int unit, int r
     const bool no_margin_knob = knobs.no_margin != 0;
     int S_auto = nr >= 32768 ? 4096 : 0;
     if (tier_id == 1 && nr >= 4096) S_auto = std::max(1024, std::min(nr / 4, NS <= 4 ? 24576 : 12288));
+    if (ordered && tier_id == 1 && nr >= 4096) S_auto = std::min(S_auto, BMX_ORDERED_SAMPLE);
     // (a seeded search samples too, but a sixth of the rows: the odd query whose seed is loose -- a left cell listed by
     // one far-away right cell -- then starts from a sampled threshold instead of none; the tighter of the two counts)
     if (seeded && tier_id == 1) S_auto = std::min(S_auto, BMX_SEEDED_SAMPLE);

@@ -116,6 +116,22 @@ __device__ __forceinline__ void publish_slot_max(double s, bool live, int block,
     if ((threadIdx.x & 63) == 0)
         atomicMax(max_slots + (size_t)(block & 63) * 16, (unsigned long long)__double_as_longlong(m));
 }
+// Ordered references (knn_order.hpp): the smallest and the largest key of the launch, the same way, in the second 64-bit word
+// of the slots -- low half: the largest bit pattern, high half: the largest complement (keys are >= 0: patterns order like
+// values, and zero is the neutral start of both)
+__device__ __forceinline__ void publish_slot_key_range(float key, bool live, int block, unsigned long long* __restrict__ max_slots) {
+    const uint32_t bits = __float_as_uint(key);
+    uint32_t mx = live ? bits : 0u, mn = live ? ~bits : 0u;
+    for (int o = 8; o < 64; o <<= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+        mn = max(mn, (uint32_t)__shfl_xor((int)mn, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t* w = reinterpret_cast<uint32_t*>(max_slots + (size_t)(block & 63) * 16 + 1);
+        atomicMax(w, mx);
+        atomicMax(w + 1, mn);
+    }
+}
 __device__ __forceinline__ double fold_slots(const unsigned long long* __restrict__ slots) {  // threads 0 .. 63 (one wave)
     double m = __longlong_as_double((long long)slots[(size_t)threadIdx.x * 16]);
     for (int o = 1; o < 64; o <<= 1) m = fmax(m, __shfl_xor(m, o));
@@ -260,18 +276,42 @@ __device__ __forceinline__ void prep_rows_f16(char* smem_pp, int block, const do
         bad |= __shfl_xor((int)bad, 2) != 0;
         bad |= __shfl_xor((int)bad, 4) != 0;
         if (sub == 0 && live) n2[r0 + rr] = bad ? __builtin_nan("") : s;
+    } else if (n2) {
+        // references of an ordered search (n2 is null otherwise): the norms follow the image, like everything indexed by image row
+        if (sub == 0 && live) n2[r0 + rr] = s;
     }
     if (sub == 0) nrm[rr] = (float)(s * scale * scale);
     __syncthreads();
     write_tile_image(fmt, P, xs, nrm, r0, n, d, NS, is_query, shape);
 }
 
-// PHASE 0 over the references: norms + the 64 slot maxima (the slots are zero when the search starts)
+// PHASE 0 over the references: norms + the 64 slot maxima (the slots are zero when the search starts).  With a query centre
+// (ordered references, knn_order.hpp) also every row's key |r - qcentre|^2 from the rows already staged, and the keys' range:
+// f32 throughout -- the key only decides where a row goes in the image, its precision does not matter, that it is the same
+// number every time does (one fixed order of summation).
 __global__ __launch_bounds__(256) void knn_prep_f16_norms(const double* __restrict__ X, const int32_t* __restrict__ rows, int n,
                                                           int d, int NS, const double* __restrict__ mean,
-                                                          double* __restrict__ n2, unsigned long long* __restrict__ max_slots) {
+                                                          double* __restrict__ n2, unsigned long long* __restrict__ max_slots,
+                                                          const double* __restrict__ qcentre, float* __restrict__ key) {
     extern __shared__ __attribute__((aligned(16))) char smem_pp[];
     prep_rows_f16<0>(smem_pp, blockIdx.x, X, rows, n, d, NS, 0, mean, 0, nullptr, n2, max_slots, 1.0);
+    if (!key) return;
+    const float* xs = reinterpret_cast<const float*>(smem_pp);  // [32][d] as staged
+    float* dq = reinterpret_cast<float*>(smem_pp) + 32 * d + 32;  // [d] the query centre, relative to `mean` like the rows
+    for (int c = threadIdx.x; c < d; c += 256) dq[c] = (float)(qcentre[c] - mean[c]);
+    __syncthreads();
+    const int rr = threadIdx.x >> 3, sub = threadIdx.x & 7;
+    const bool live = blockIdx.x * 32 + rr < n;
+    float kq = 0.f;
+    for (int c = sub; c < d; c += 8) {
+        const float t = xs[rr * d + c] - dq[c];
+        kq += t * t;
+    }
+    kq += __shfl_xor(kq, 1);
+    kq += __shfl_xor(kq, 2);
+    kq += __shfl_xor(kq, 4);
+    if (sub == 0 && live) key[blockIdx.x * 32 + rr] = kq;
+    publish_slot_key_range(kq, live, blockIdx.x, max_slots);
 }
 
 // PHASE 1 of references AND queries in one launch (workgroups [0, nrb): reference tiles, the others: query tiles), with
@@ -329,15 +369,23 @@ __global__ __launch_bounds__(256) void knn_prep_f16_rq(const double* __restrict_
 
 // Tier 1: references (norm pass, then the scaled image) and queries (image, norm, margin, seed threshold) of one search: two
 // launches.  `slots` (64 x 16 words) must be zero on entry -- knn_refine leaves them so for the next search.
+// ord (nullable): ordered references -- the norm pass also leaves the keys, ref_order_build (knn_order.hip) the two index
+// arrays, and the image (Pr) is written in that order; the image launch then rewrites rn2 in image order too.
 void f16_prep_all(hipStream_t stream, const double* X, const int32_t* rrows, int nr, int nr_pad, const double* Q,
                   const int32_t* qrows, int nq, int nq_pad, int d, int NS, int shape, const double* mean, uint16_t* Pr, uint16_t* Pq,
                   double* rn2, double* qn2, unsigned long long* maxbits, unsigned long long* slots, int32_t* flagged0,
-                  float* margin, const PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init) {
+                  float* margin, const PassEps& pe, const float* seed_d2, uint32_t* tau_seed, uint32_t* tau_init,
+                  const RefOrder* ord) {
     const size_t lds = (size_t)32 * d * 4 + 128 + 16;
-    hipLaunchKernelGGL(knn_prep_f16_norms, dim3(nr_pad / 32), dim3(256), lds, stream, X, rrows, nr, d, NS, mean, rn2, slots);
+    hipLaunchKernelGGL(knn_prep_f16_norms, dim3(nr_pad / 32), dim3(256), lds + (ord ? (size_t)d * 4 : 0), stream, X, rrows, nr, d,
+                       NS, mean, rn2, slots, ord ? ord->qcentre : nullptr, ord ? ord->key : nullptr);
     BMX_LAUNCH_CHECK();
+    if (ord) {  // the image in key order: its tiles gather their rows of X through img_src
+        ref_order_build(stream, ord->key, nr, rrows, slots, ord->scratch, ord->img_src, ord->img_pos);
+        rrows = ord->img_src;
+    }
     hipLaunchKernelGGL(knn_prep_f16_rq, dim3(nr_pad / 32 + nq_pad / 32), dim3(256), lds, stream, X, rrows, nr, nr_pad / 32, Q, qrows,
-                       nq, d, NS, shape, mean, Pr, Pq, rn2, qn2, (const unsigned long long*)slots, maxbits, flagged0, margin, pe, seed_d2,
+                       nq, d, NS, shape, mean, Pr, Pq, ord ? rn2 : nullptr, qn2, (const unsigned long long*)slots, maxbits, flagged0, margin, pe, seed_d2,
                        tau_seed, tau_init);
     BMX_LAUNCH_CHECK();
 }

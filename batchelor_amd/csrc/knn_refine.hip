@@ -12,7 +12,8 @@ using namespace sel;
 
 // ---------------------------------------------------------------------------------------------------
 // refine: exact FP64 re-rank of the candidates + certification.  One wave per query.
-//   1. the candidates of all reference ranges are gathered into one dense list;
+//   1. the candidates of all reference ranges are gathered into one dense list (ordered references, knn_order.hpp: the
+//      pass lists image rows, which become reference positions here, through img_pos -- positions from there on);
 //   2. they are ranked by their approximate values: only the KS best go on (the first one cut bounds all the others
 //      from below and enters the certificate), and of those only the ones within twice the error bound of the k-th
 //      best -- a candidate further out is provably farther than k others, so its exact distance is never needed;
@@ -115,12 +116,16 @@ __global__ __launch_bounds__(256) void knn_refine(const double* __restrict__ X, 
                                                   double* __restrict__ dist_out, int32_t* __restrict__ flagged,
                                                   double* __restrict__ flag_bound,
                                                   unsigned long long* __restrict__ zero_slots, int q0,
-                                                  double* __restrict__ kth_out, int sq = 0) {
+                                                  double* __restrict__ kth_out, int sq = 0,
+                                                  const int32_t* __restrict__ img_pos = nullptr) {
     __shared__ __attribute__((aligned(16))) double sd[4][REFINE_MAXM];
     __shared__ int si[4][REFINE_MAXM];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // (the prep kernels' 64 slot maxima have been folded by now: left zeroed for the next search's norm pass)
-    if (zero_slots && blockIdx.x == 0 && threadIdx.x < 64) zero_slots[(size_t)threadIdx.x * 16] = 0ull;
+    if (zero_slots && blockIdx.x == 0 && threadIdx.x < 64) {
+        zero_slots[(size_t)threadIdx.x * 16] = 0ull;
+        zero_slots[(size_t)threadIdx.x * 16 + 1] = 0ull;  // (the keys' range of an ordered search)
+    }
     const int q = q0 + blockIdx.x * 4 + w;  // (queries [q0, nq): the ones in front go through knn_refine_half)
     if (q >= nq) return;
     const int Mall = nchunks * KS;
@@ -134,7 +139,8 @@ __global__ __launch_bounds__(256) void knn_refine(const double* __restrict__ X, 
     unsigned long long* sk = reinterpret_cast<unsigned long long*>(&sd[w][0]);
     for (int m0 = 0; m0 < Mall; m0 += 64) {
         const int m = m0 + lane;
-        const int id = m < Mall ? cand[(int64_t)q * Mall + m] : -1;
+        int id = m < Mall ? cand[(int64_t)q * Mall + m] : -1;
+        if (img_pos && id >= 0) id = img_pos[id];  // ordered references: image row -> reference position, positions from here on
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(id >= 0);
         const int pos = M + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
         if (id >= 0) {
@@ -271,13 +277,17 @@ __global__ __launch_bounds__(256) void knn_refine_half(const double* __restrict_
                                                        double* __restrict__ dist_out, int32_t* __restrict__ flagged,
                                                        double* __restrict__ flag_bound,
                                                        unsigned long long* __restrict__ zero_slots,
-                                                       double* __restrict__ kth_out, int sq = 0) {
+                                                       double* __restrict__ kth_out, int sq = 0,
+                                                       const int32_t* __restrict__ img_pos = nullptr) {
     constexpr int KS = 32;
     __shared__ __attribute__((aligned(16))) double sd[8][KS];
     __shared__ int si[8][KS];
     const int lane = threadIdx.x & 63, hl = lane & 31, half = lane >> 5;
     const int w = (threadIdx.x >> 6) * 2 + half;  // the half-wave's row of the LDS arrays
-    if (zero_slots && blockIdx.x == 0 && threadIdx.x < 64) zero_slots[(size_t)threadIdx.x * 16] = 0ull;
+    if (zero_slots && blockIdx.x == 0 && threadIdx.x < 64) {
+        zero_slots[(size_t)threadIdx.x * 16] = 0ull;
+        zero_slots[(size_t)threadIdx.x * 16 + 1] = 0ull;
+    }
     const int qraw = blockIdx.x * 8 + w;
     const bool live = qraw < nq;
     const int q = live ? qraw : nq - 1;  // (an idle half follows the last query and writes nothing: shuffles stay convergent)
@@ -290,7 +300,8 @@ __global__ __launch_bounds__(256) void knn_refine_half(const double* __restrict_
     unsigned long long* sk = reinterpret_cast<unsigned long long*>(&sd[w][0]);
     int M;
     {
-        const int id = cand[(int64_t)q * stride + hl];
+        int id = cand[(int64_t)q * stride + hl];
+        if (img_pos && id >= 0) id = img_pos[id];
         const uint32_t mask = half_ballot(id >= 0);
         const int pos = __builtin_popcount(mask & ((1u << hl) - 1u));
         if (id >= 0) {
@@ -400,12 +411,12 @@ void refine_launch(hipStream_t stream, KnnWorkspace& ws, const PassPlan& plan, i
         if (nq_half > 0)
             hipLaunchKernelGGL(knn_refine_half<NC>, dim3(cdiv(nq_half, 8)), dim3(256), 0, stream, X, ref_rows, Qs, qrs, nq_half, d,
                                k, nchunks, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den, pe.scaled, L.cand, L.cand_v, L.tau, L.qn2,
-                               L.maxbits, seed_d2, io, dout, flagged, flag_bound, zero_slots, kth_out, sq);
+                               L.maxbits, seed_d2, io, dout, flagged, flag_bound, zero_slots, kth_out, sq, L.img_pos);
         if (nq > nq_half)
             hipLaunchKernelGGL(knn_refine<NC>, dim3(cdiv(nq - nq_half, 4)), dim3(256), 0, stream, X, ref_rows, Qs, qrs, nq, d, k,
                                KS, nchunks, pe.eps_k, pe.eps_qr, pe.eps_split, pe.eps_den, pe.scaled, L.cand, L.cand_v, L.tau,
                                L.qn2, L.maxbits, seed_d2, io, dout, flagged, flag_bound, nq_half > 0 ? nullptr : zero_slots,
-                               nq_half, kth_out, sq);
+                               nq_half, kth_out, sq, L.img_pos);
     };
     if (need == 0 || need > 16) go(std::integral_constant<int, 0>{});
     else if (need <= 2) go(std::integral_constant<int, 2>{});

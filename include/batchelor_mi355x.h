@@ -153,6 +153,9 @@ void bmx_set_force_exact_knn(int32_t on);
  * "asv_strict" (-1 = every adjust_shift_variance call is strict where its caller says so, the default; 1 = every call is
  * strict: times strict mode on a workload whose driver has no switch for it), "mfma_shape" (fp16 tier: the MFMA shape of the
  * candidate sweep, 0 = 32x32x16, 1 = 16x16x32 where the row width has it; -1 = the library's table, the default),
+ * "ref_order" (fp16 tier: the reference image of a search in ascending order of the rows' squared distance from the centre of
+ * the queries, so that the rows nearest the queries are swept first; -1 = where the search has a threshold sample, the default;
+ * 0 = never; 1 = wherever the tier runs; results do not depend on it),
  * "snn_lds_candidates" (SNN graph: candidates of a cell that one LDS window holds; 0 = 2048, the default; at least k + 1 and at
  * most 4096 are used; cells with more take several windows and give the same edges),
  * "reset" (all back to their defaults).
@@ -172,6 +175,8 @@ int32_t bmx_dev_set(const char* name, int32_t value);
  * added up since the thread's first: "knn_exact_fallbacks" (queries finished by the FP64 paths) and "knn_tier2_queries" (queries
  * the first candidate tier handed to the second) -- what bmx_engine_profile_detail reports of an engine; "knn_mfma_shape"
  * (the MFMA shape the last fp16 candidate pass of those searches ran with: 0 = 32x32x16, 1 = 16x16x32, -1 = none yet).
+ * Of the whole process, engines and single primitives alike: "knn_ordered_searches" / "knn_unordered_searches" (candidate passes
+ * that ran with the reference image in key order / without).
  * Of this thread's last bmx_snn_graph / bmx_make_snn_graph: "snn_spilled_cells" (cells whose candidates took more than one LDS
  * window), "snn_graph_us" (microseconds between HIP events around the graph's kernels, the search excluded). */
 int32_t bmx_dev_get(const char* name, int64_t* value);
